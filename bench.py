@@ -2,15 +2,18 @@
 """bench.py - throughput of the CDNet hot path on MI355X.
 
   python bench.py --gpus N --steps K --warmup W [--mode train|infer|image|roofline] [--dtype bf16|fp32] [--batch B]
+                  [--dump-outputs DIR] [--full]
 
 One rank per GPU (the driver launches N>1 through torch.distributed.run); RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* come
 from the environment.  W untimed warm-up steps, then exactly K steps bracketed by barrier + synchronize; the step time
-is the max over ranks; rank 0 prints ONE JSON line (see DESIGN.md "Measurement").
+is the max over ranks; rank 0 prints ONE JSON line (see DESIGN.md "Measurement").  `--dump-outputs DIR`: rank 0 writes what the
+last timed step computed as DIR/<name>.npy.
 
 The line's `value` is the training rate of BASELINE config 2 in the arithmetic named by `dtype`.  The default is `fp32` - the
 like-for-like mode: fp32 storage and accumulation as in the reference, every product a*b as three bf16 MFMAs over split operands
-("bf16x3", <= 2^-16 relative error per product; gfx950 has no TF32 path and its fp32 MFMA runs at 1/16 of the bf16 rate).  Beside it
-(same protocol, fewer steps): `inference` (tiles/s incl. post-processing), `bf16` = the same two rates on the 16-bit fast path
+("bf16x3", <= 2^-16 relative error per product; gfx950 has no TF32 path and its fp32 MFMA runs at 1/16 of the bf16 rate).  A plain run
+measures that headline and nothing else.  With `--full`, beside it (same protocol, fewer steps): `box` (what this GPU grants),
+`inference` (tiles/s incl. post-processing), `bf16` = the same two rates on the 16-bit fast path
 (bf16 / fp16 activations, bf16 MFMA operands, fp32 accumulation; legitimate only behind the label-level gate
 tests/test_gpu_label_gate.py), `image` = BASELINE config 3 (one 1000x1000 image, 8 TTA views x 25 windows), `roofline` (dominant
 kernel of the headline arithmetic), `roofline_path` (whole-step fractions in SURVEY 8d's units) and `cpu_baseline`.
@@ -58,8 +61,14 @@ def parse():
     ap.add_argument('--dtype', default=os.environ.get('CDNET_BENCH_DTYPE', 'fp32'), choices=['bf16', 'fp32'],
                     help='arithmetic of the headline value; the other precision is reported beside it')
     ap.add_argument('--batch', type=int, default=None, help='tiles per GPU per step')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy, float32 or float64, at most 64 MB in all '
+                         '(a fixed, seeded sample of the elements of a larger array)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beside the headline: the box record, the other legs and arithmetic, rooflines, the CPU baselines, the forced '
+                         'all-reduce leg (the --no-* options below trim this)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='only the headline measurement (+ roofline)')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: only the headline measurement (+ box, roofline, CPU baseline)')
     ap.add_argument('--no-infer-extra', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--no-forced-allreduce', action='store_true', help='skip the 1-rank forced all-reduce leg (it creates a one-rank RCCL group at the end of the run)')
     ap.add_argument('--no-live-pmc', action='store_true', help='quote the dominant kernel\'s HBM traffic from the committed summary instead of two rocprofv3 --pmc child passes')
@@ -512,6 +521,31 @@ def cpu_baseline_hrnet(n_tiles=1):
                        '(forward, 5 losses, autograd backward, Adam; %d threads), median of %d repetitions after 1 warm-up' % (n_tiles, cores, reps))
 
 
+DUMP_BYTES = 60 << 20                   # array data of --dump-outputs (+ the .npy headers: under 64 MB in all)
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: every tensor / number of `outputs` as out_dir/<name>.npy, float64 when the source is float64 or a 32/64-bit integer
+    (exact), float32 otherwise.  An array larger than its share of DUMP_BYTES is replaced by a sample of its flattened elements: the same
+    seeded, sorted indices for the same shape in every run, so that two builds compare element for element."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(outputs))
+    for name, v in outputs.items():
+        if torch.is_tensor(v):
+            v = v.detach()
+            if v.dtype not in (torch.float64, torch.float32, torch.int32, torch.int64):
+                v = v.float()                       # (bf16 / f16 / u8 / bool: float32 holds each value exactly)
+            v = v.cpu().numpy()
+        a = np.asarray(v)
+        a = a.astype(np.float64 if a.dtype in (np.float64, np.int32, np.int64) else np.float32)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(2022).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
 def main():
     a = parse()
     import numpy as np
@@ -543,10 +577,11 @@ def main():
         print(json.dumps({'roofline': time_dominant_conv(torch, a.batch or 16, steps=a.steps, precision=a.dtype)}), flush=True)
         return
 
-    def timed(step, steps, warmup, settle_s=1.0):
+    def timed(step, steps, warmup, settle_s=1.0, reset=None):
         """(settling: >= settle_s seconds of the same load first - the chip lowers its clock under load over about a second, and a
         timed region that starts cold reads high) then W warm-ups, then exactly K steps between barrier + synchronize on both sides;
-        max over ranks"""
+        max over ranks.  `reset` (a step that changes state, training): called once the settling steps are done - their number follows
+        the clock - so that the warm-up and timed steps start from the same state in every run"""
         step()                                      # (allocations, kernel attributes, weight packs)
         torch.cuda.synchronize()
         t_s = time.perf_counter()
@@ -557,6 +592,9 @@ def main():
             dist.all_reduce(t1, op=dist.ReduceOp.MAX)      # every rank settles for the same number of steps (collectives inside)
         for _ in range(min(2000, int(settle_s / max(float(t1.item()), 1e-4)))):
             step()
+        if reset is not None:
+            torch.cuda.synchronize()                # (every stream: the trainer packs weights on a side stream)
+            reset()
         for _ in range(warmup):
             step()
         torch.cuda.synchronize()
@@ -582,10 +620,22 @@ def main():
         return Unet(backbone_name='vgg16_bn', pretrained=False, classes=3).to(dev)
 
     def run_train(precision, B, steps, warmup):
+        """trainer.make_bench_step's step, with the trainer at hand: model and optimiser state go back to their start after settling"""
         cdnet_amd.set_precision(precision)
-        step, metric, workload = trainer.make_bench_step(new_model(), B, dev, rank, world)
-        dt = timed(step, steps, warmup)
-        return dict(metric=metric, workload=workload, value=world * B * steps / dt, ms_per_step=dt / steps * 1e3, tiles=B, steps=steps)
+        model = new_model()
+        tr = trainer.Trainer(model, world_size=world)
+        batch = trainer.synthetic_batch(B, dev, seed=2022 + rank)
+        start = ({k: v.clone() for k, v in model.state_dict().items()}, tr.state_dict())
+
+        def reset():
+            model.load_state_dict(start[0])         # (the parameters are views of the trainer's flat buffer: packed copies follow)
+            tr.load_state_dict(start[1])            # Adam moments and step count
+        dt = timed(lambda: tr.train_step(*batch), steps, warmup, reset=reset)
+        outputs = {'losses': tr.losses, 'parameters': torch.cat([p.detach().reshape(-1) for p in model.parameters()])}
+        return dict(metric='tiles/sec (train fwd+bwd+Adam), 256x256',
+                    workload='CDNet UNet2RevA1_vgg16 (UNet+DAM) training step: forward, 5-term loss, backward, %s fused Adam; 256x256x3 synthetic '
+                             'tiles, batch %d per GPU' % ('RCCL gradient all-reduce,' if world > 1 else '', B),
+                    value=world * B * steps / dt, ms_per_step=dt / steps * 1e3, tiles=B, steps=steps, outputs=outputs)
 
     def run_infer(precision, B, steps, warmup):
         cdnet_amd.set_precision(precision)
@@ -603,18 +653,24 @@ def main():
         return dict(metric='tiles/sec inference incl. post-proc, 256x256',
                     workload='CDNet UNet2RevA1_vgg16 (UNet+DAM) inference + direction-diff/CC post-processing, 256x256x3 synthetic tiles '
                              '(post-processing of batch i on a second stream beside the forward of batch i+1)',
-                    value=world * B * steps / dt, ms_per_step=dt / steps * 1e3, tiles=B, steps=steps)
+                    value=world * B * steps / dt, ms_per_step=dt / steps * 1e3, tiles=B, steps=steps,
+                    outputs={k: v for k, v in last['r'].items() if torch.is_tensor(v)})
 
     def run_image(precision, steps, warmup):
         """BASELINE config 3: one 1000x1000 image per rank and step, 8 TTA views x 25 sliding windows (256/40), per-view DDM, CC chain"""
         cdnet_amd.set_precision(precision)
         model = new_model().eval()
         img = torch.from_numpy(np.random.RandomState(2022 + rank).randint(0, 256, size=(3, 1000, 1000)).astype(np.float32) / 255.0).to(dev)
-        dt = timed(lambda: pipeline.infer_image(model, img, tta=True, all_img_test=0, patch_size=256, overlap=40), steps, warmup)
+        last = {}
+
+        def step():
+            last['r'] = pipeline.infer_image(model, img, tta=True, all_img_test=0, patch_size=256, overlap=40)
+        dt = timed(step, steps, warmup)
         return dict(metric='images/sec, 1000x1000 image, 8-view TTA x 25 sliding windows + post-proc',
                     workload='CDNet inference of 1000x1000 images (BASELINE config 3): 8 TTA views x 25 windows of 256/40, per-view '
                              'direction-difference maps, boost, CC chain',
-                    value=world * steps / dt, ms_per_step=dt / steps * 1e3, window_evaluations_per_s=world * 200 * steps / dt, steps=steps)
+                    value=world * steps / dt, ms_per_step=dt / steps * 1e3, window_evaluations_per_s=world * 200 * steps / dt, steps=steps,
+                    outputs={k: v for k, v in last['r'].items() if torch.is_tensor(v) or isinstance(v, (int, float))})
 
     def run_cdm(B, steps, warmup):
         """centripetal-direction-map generation (`LabelEncoding` + `get_centerpoint2`, my_transforms_direction.py:650-885) of
@@ -759,8 +815,9 @@ def main():
         print(json.dumps(fa), flush=True)
         return
     other = 'fp32' if a.dtype == 'bf16' else 'bf16'
-    extras = not a.no_extras
-    box = box_calibration(torch, dev)               # before anything else is timed: what this box grants (copy GB/s, MFMA TFLOP/s, clock)
+    extras = a.full and not a.no_extras
+    # before anything else is timed: what this box grants (copy GB/s, MFMA TFLOP/s, clock)
+    box = box_calibration(torch, dev) if a.full else None
     if mode == 'train':
         B = a.batch or 16
         head = run_train(a.dtype, B, a.steps, a.warmup)
@@ -770,6 +827,9 @@ def main():
     else:
         B = 1
         head = run_image(a.dtype, a.steps, a.warmup)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, head['outputs'])
+    del head['outputs']
     kind = 'train' if mode == 'train' else 'infer'
     line = {
         'metric': head['metric'], 'value': head['value'], 'unit': 'images/s' if mode == 'image' else 'tiles/s', 'n_gpus': world, 'steps': a.steps,
@@ -783,10 +843,11 @@ def main():
                                  'split operands (hi*hi + hi*lo + lo*hi), <= 2^-16 relative error per product ("bf16x3"; not IEEE-fp32 '
                                  'multiplication: gfx950 has no TF32 and its fp32 MFMA runs at 1/16 of the bf16 rate)')},
     }
-    line['box'] = box
-    # rates beside what the box itself grants: the fp32 / bf16 training steps are matrix-bound (per TFLOP/s of the box's MFMA loop), the
-    # inference steps lean on the memory side (per GB/s of the box's copy) - the columns of DESIGN section 0's per-round table
-    line['value_per_box_mfma'] = head['value'] / box['mfma_TFLOPs']
+    if box is not None:
+        line['box'] = box
+        # rates beside what the box itself grants: the fp32 / bf16 training steps are matrix-bound (per TFLOP/s of the box's MFMA loop), the
+        # inference steps lean on the memory side (per GB/s of the box's copy) - the columns of DESIGN section 0's per-round table
+        line['value_per_box_mfma'] = head['value'] / box['mfma_TFLOPs']
     line['config']['process_group'] = ('%s, %d rank(s)' % (dist.get_backend(), dist.get_world_size())) if dist.is_initialized() else None
     rp = {}
     if mode != 'image':
@@ -835,7 +896,7 @@ def main():
     if rp:
         line['roofline_path'] = rp
     line['config']['side_stream_probe'] = next((p_ for p_ in reversed(streams.PROBES) if p_.get('k', 0) == 0), None)       # (the trainer's / pipeline's second stream)
-    if rank == 0:
+    if rank == 0 and a.full:
         cdnet_amd.set_precision(a.dtype)
         line['roofline'] = time_dominant_conv(torch, 16, precision=a.dtype, live_pmc=(world == 1 and extras and not a.no_live_pmc))
         if extras and world == 1:
@@ -864,6 +925,7 @@ def main():
                 line['cpu_baseline_image_postproc'] = cpu_baseline_image_postproc()
                 line['cpu_baseline_unet_cfg1'] = cpu_baseline_unet()
                 line['cpu_baseline_hrnet'] = cpu_baseline_hrnet()
+    if rank == 0:
         sys.stdout.flush()
         os.dup2(fd_out, 1)
         print(json.dumps(line), flush=True)

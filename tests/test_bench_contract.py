@@ -185,3 +185,28 @@ def test_box_and_step_roofline_helpers():
     assert r['bound'] == 'hbm' and abs(r['roofline_ms'] - 1.0) < 1e-12 and abs(r['frac'] - 0.5) < 1e-12 and r['mfma_work_per_product'] == 1
     r = bench.step_roofline(5000.0, 800.0, 4.0, 'fp32')
     assert r['bound'] == 'mfma' and abs(r['frac'] - 0.5) < 1e-12 and r['mfma_work_per_product'] == 3
+
+
+def test_dump_outputs_writes_float_arrays_under_64_mb_with_a_fixed_sample(tmp_path):
+    """bench.dump_outputs (--dump-outputs): float32 / float64 .npy files, exact for integers, at most 64 MB in all; an array above its share
+    is a sample of its flattened elements at the same indices in every run"""
+    import sys
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    big = torch.arange(12_000_000, dtype=torch.float32)
+    outs = {'losses': torch.tensor([1.5, 2.5]), 'labels': torch.tensor([[0, 7], [70000, 3]], dtype=torch.int32),
+            'pred': torch.tensor([0, 1, 2], dtype=torch.uint8), 'half': torch.tensor([0.5], dtype=torch.bfloat16), 'count': 17, 'big': big}
+    for run in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / run), outs)
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == sorted(n + '.npy' for n in outs)
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in files) <= 64 << 20
+    ld = lambda run, n: np.load(tmp_path / run / (n + '.npy'))
+    assert ld('a', 'losses').dtype == np.float32 and ld('a', 'losses').tolist() == [1.5, 2.5]
+    assert ld('a', 'labels').dtype == np.float64 and ld('a', 'labels').tolist() == [[0, 7], [70000, 3]]
+    assert ld('a', 'pred').dtype == np.float32 and ld('a', 'half').tolist() == [0.5] and ld('a', 'count') == 17
+    s = ld('a', 'big')
+    assert s.dtype == np.float32 and 0 < s.size < big.numel() and np.all(np.diff(s) > 0)       # (values = their indices: sorted, distinct)
+    assert np.array_equal(s, ld('b', 'big'))

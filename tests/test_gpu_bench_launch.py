@@ -34,7 +34,7 @@ def _run(cmd, timeout=600):
 
 
 def test_bench_under_torch_distributed_run_with_one_rank():
-    args = ['bench.py', '--gpus', '1', '--steps', '4', '--warmup', '1', '--no-extras', '--no-cpu-baseline']
+    args = ['bench.py', '--gpus', '1', '--steps', '4', '--warmup', '1', '--full', '--no-extras', '--no-cpu-baseline']
     plain = _run([sys.executable] + args)
     launched = _run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
                      '--master-port', str(_free_port())] + args)
@@ -52,3 +52,27 @@ def test_bench_under_torch_distributed_run_with_one_rank():
     # the side stream was probed AFTER the process group existed (RCCL's streams change the stream -> hardware-queue deal)
     assert launched['config']['side_stream_probe']['group'] is True and launched['config']['side_stream_probe']['probed']
     assert plain['config']['side_stream_probe']['group'] is False
+
+
+def test_plain_run_times_the_headline_alone_and_dumps_its_last_step(tmp_path):
+    """without --full the line holds the headline and nothing measured beside it; --steps sets the timed steps; --dump-outputs writes the last
+    timed step's losses and a fixed sample of the parameters it left, under 64 MB, the same in two runs (the warm-up and timed steps start
+    from the initial state whatever the number of settling steps)"""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        out = tmp_path / ('run%d' % i)
+        d = _run([sys.executable, 'bench.py', '--gpus', '1', '--steps', '3', '--warmup', '1', '--dump-outputs', str(out)])
+        assert d['steps'] == 3 and d['warmup'] == 1 and d['dtype'] == 'fp32' and d['unit'] == 'tiles/s' and d['higher_is_better'] is True
+        assert d['metric'] == 'tiles/sec (train fwd+bwd+Adam), 256x256' and d['config']['tiles_per_gpu_per_step'] == 16
+        assert abs(d['value'] - 16 / d['ms_per_step'] * 1e3) < 1e-6 * d['value']
+        for k in ('box', 'roofline', 'cpu_baseline', 'inference', 'bf16', 'image', 'dp1_forced_allreduce'):
+            assert k not in d, k
+        names = sorted(os.listdir(out))
+        assert names == ['losses.npy', 'parameters.npy'] and sum(os.path.getsize(out / n) for n in names) <= 64 << 20
+        dumps.append({n: np.load(out / n) for n in names})
+    a, b = dumps
+    assert a['losses.npy'].shape == (11,) and a['losses.npy'].dtype == np.float32 and np.isfinite(a['losses.npy']).all()
+    assert a['parameters.npy'].size > 1 << 20 and np.isfinite(a['parameters.npy']).all()
+    for n in a:
+        np.testing.assert_allclose(a[n], b[n], rtol=1e-5, atol=1e-6, err_msg=n)

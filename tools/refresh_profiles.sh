@@ -10,10 +10,10 @@ OUT=$ROOT/gpurun_out/refresh_$R
 RAW=$OUT/raw
 mkdir -p $OUT $RAW
 cd /tmp && export TMPDIR=/tmp
-python3 $ROOT/bench.py --steps 20 --warmup 5 > $OUT/bench_default_line.json 2> $RAW/bench_default.err
+python3 $ROOT/bench.py --steps 20 --warmup 5 --full > $OUT/bench_default_line.json 2> $RAW/bench_default.err
 prof() {   # prof <name> <bench.py args...>
   local name=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $RAW/$name -o t -- python3 $ROOT/bench.py "$@" --no-extras --no-cpu-baseline > $OUT/${name}_bench_line.json 2> $RAW/$name.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $RAW/$name -o t -- python3 $ROOT/bench.py "$@" --full --no-extras --no-cpu-baseline > $OUT/${name}_bench_line.json 2> $RAW/$name.err
   cp $RAW/$name/t_kernel_stats.csv $OUT/${name}_kernel_stats.csv
 }
 prof train_b16_fp32 --mode train --dtype fp32 --steps 10 --warmup 3
