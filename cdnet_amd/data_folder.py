@@ -2,15 +2,20 @@
 
   img_loader(path, num_channels), get_imgs_list(dir_list, post_fix), DataFolder(dir_list, post_fix, num_channels,
   data_transform)                     same names / arguments / pairing rule as the reference (host side, PIL)
-  TileBatches(dataset, opt, device)   the MI355X input pipeline: crops / flips on the host (cheap), then ONE
+  TileBatches(dataset, opt, device, augment=False)
+                                      the MI355X input pipeline: crops / flips on the host (cheap), then ONE
                                       cdnet_label_encoding launch per batch makes the 3-class label, the centre-point map and
                                       the centripetal direction classes (the reference does this per sample in DataLoader
-                                      workers, seconds per sample: SURVEY 8f.1)
+                                      workers, seconds per sample: SURVEY 8f.1).  With augment=True the reference's whole
+                                      default recipe runs on the device (cdnet_amd/augment.py: random_color, flips,
+                                      random_elastic, random_chooseAug and random_crop in one cdnet_augment_batch call per
+                                      batch, the sources resident there)
 
 Samples leave TileBatches in the layout train_util_dam.train expects: (input f32 [B,3,H,W], weight u8 [B,1,H,W],
-label i64 [B,1,H,W] in {0,127,255}, point f16 [B,H,W], direction u8 [B,H,W]).  The photometric / elastic augmentations of
-the reference (albumentations, PIL RNG streams: my_transforms_direction.py:38-630) are not reproduced - their random streams
-cannot be pinned ("parity unpinned"); random crop and flips are, with a numpy RandomState."""
+label i64 [B,1,H,W] in {0,127,255}, point f16 [B,H,W], direction u8 [B,H,W]).  Without `augment` the photometric / elastic
+augmentations of the reference (my_transforms_direction.py:155-473) are skipped and logged; crop and flips are drawn with a numpy
+RandomState.  Neither path reproduces the reference's random streams (Python random, np.random, albumentations' RandomState over
+DataLoader workers): the contract is the same distributions and the same operation for given parameters."""
 import os
 
 import numpy as np
@@ -98,15 +103,23 @@ class TileBatches:
     unless the images share one size)."""
 
     SKIPPED = ('random_color', 'random_elastic', 'random_chooseAug', 'random_resize', 'random_affine', 'random_rotation')
+    AUGMENTED = ('random_color', 'random_elastic', 'random_chooseAug')          # what augment=True adds (cdnet_amd/augment.py)
 
-    def __init__(self, dataset, transform, batch_size, device, seed=0, shuffle=True, drop_last=False, logger=None):
+    def __init__(self, dataset, transform, batch_size, device, seed=0, shuffle=True, drop_last=False, logger=None, augment=False,
+                 elastic=None):
         self.ds, self.B, self.dev = dataset, batch_size, device
         self.rs = np.random.RandomState(seed)
         self.shuffle, self.drop_last = shuffle, drop_last
         self.crop = transform.get('random_crop')
         self.hflip, self.vflip = bool(transform.get('horizontal_flip')), bool(transform.get('vertical_flip'))
         self.normalize = transform.get('normalize')
-        skipped = [k for k in transform if k in self.SKIPPED]
+        self.recipe = None
+        if augment:
+            if not self.crop:
+                raise ValueError('augment=True needs a random_crop transform')
+            from .augment import Recipe                                          # elastic: elastic_alpha / _sigma / _alpha_affine
+            self.recipe = Recipe.from_transform(transform, **(elastic or {}))
+        skipped = [k for k in transform if k in self.SKIPPED and not (augment and k in self.AUGMENTED)]
         if skipped and logger is not None:
             logger.info('input pipeline: augmentations {} are not reproduced (parity unpinned); crop / flips / label encoding are'.format(skipped))
         unknown = [k for k in transform if k not in self.SKIPPED + ('random_crop', 'horizontal_flip', 'vertical_flip', 'label_encoding',
@@ -120,6 +133,10 @@ class TileBatches:
         if len(kinds) > 1:
             raise ValueError('the label directory mixes instance-level and 3-class label images')
         self.instance_labels = bool(kinds and kinds.pop())
+        self.sources = None
+        if self.recipe is not None and torch.device(device).type == 'cuda':
+            from .augment import Source                                          # uploaded once, resident on the device
+            self.sources = [Source(*it, device) for it in self.items]
 
     def __len__(self):
         n = len(self.items)
@@ -127,6 +144,16 @@ class TileBatches:
 
     def _draw(self, img, weight, label):
         H, W = label.shape[:2]
+        if self.recipe is not None:
+            # the whole recipe on the host (device='cpu'), re-drawn while the label crop holds one value
+            from .augment import augment_host, draw_params
+            lab0 = label if label.ndim == 2 else label[:, :, 0]
+            w0 = weight if weight.ndim == 2 else weight[:, :, 0]
+            for _ in range(50):
+                out = augment_host(img, w0, lab0, draw_params(self.rs, H, W, self.recipe), self.recipe.size)
+                if len(np.unique(out[2])) > 1:
+                    break
+            return out
         if not self.crop and not self.hflip and not self.vflip:
             # the reference's validation transform {label_encoding, to_tensor, normalize} (options.py:358): the whole image, untouched -
             # validate() then takes it whole or through split_forward_dam (train_util_dam.py:474)
@@ -153,16 +180,40 @@ class TileBatches:
         order = self.rs.permutation(len(self.items)) if self.shuffle else np.arange(len(self.items))
         for b in range(len(self)):
             idx = order[b * self.B:(b + 1) * self.B]
-            crops = [self._draw(*self.items[i]) for i in idx]
-            img = torch.from_numpy(np.stack([c[0] for c in crops])).to(self.dev).permute(0, 3, 1, 2).float().div(255)
-            if self.normalize:
-                mean, std = self.normalize
-                img = (img - torch.tensor(mean, device=self.dev).view(1, 3, 1, 1)) / torch.tensor(std, device=self.dev).view(1, 3, 1, 1)
-            weight = torch.from_numpy(np.stack([c[1] if c[1].ndim == 2 else c[1][:, :, 0] for c in crops])).to(self.dev)
-            lab0 = torch.from_numpy(np.stack([c[2] if c[2].ndim == 2 else c[2][:, :, 0] for c in crops])).to(self.dev)
+            if self.sources is not None:
+                img, weight, lab0 = self._augment_device(idx)
+            else:
+                img, weight, lab0 = self._host_batch(idx)
             if self.instance_labels:
                 from .my_transforms_direction import label_encoding_instances_batch
                 l3, point, direction = label_encoding_instances_batch(lab0.to(torch.int32).contiguous())
             else:
                 l3, point, direction = label_encoding_batch(lab0.to(torch.uint8).contiguous())
             yield img.contiguous(), weight.to(torch.uint8).unsqueeze(1), l3.to(torch.int64).unsqueeze(1), point, direction
+
+    def _host_batch(self, idx):
+        crops = [self._draw(*self.items[i]) for i in idx]
+        img = torch.from_numpy(np.stack([c[0] for c in crops])).to(self.dev).permute(0, 3, 1, 2).float().div(255)
+        if self.normalize:
+            mean, std = self.normalize
+            img = (img - torch.tensor(mean, device=self.dev).view(1, 3, 1, 1)) / torch.tensor(std, device=self.dev).view(1, 3, 1, 1)
+        weight = torch.from_numpy(np.stack([c[1] if c[1].ndim == 2 else c[1][:, :, 0] for c in crops])).to(self.dev)
+        lab0 = torch.from_numpy(np.stack([c[2] if c[2].ndim == 2 else c[2][:, :, 0] for c in crops])).to(self.dev)
+        return img, weight, lab0
+
+    def _augment_device(self, idx):
+        """one cdnet_augment_batch call for the batch; samples whose label crop holds one value are re-drawn and re-run together, up to
+        50 tries in all (the DataFolder rule)"""
+        from .augment import augment_batch, draw_params
+        srcs = [self.sources[i] for i in idx]
+        draw = lambda s: draw_params(self.rs, s.H, s.W, self.recipe)
+        img, weight, lab0, varied = augment_batch(srcs, [draw(s) for s in srcs], self.recipe.size, self.normalize)
+        redo = [k for k, v in enumerate(varied.tolist()) if v == 0]
+        for _ in range(49):
+            if not redo:
+                break
+            r = augment_batch([srcs[k] for k in redo], [draw(srcs[k]) for k in redo], self.recipe.size, self.normalize)
+            sel = torch.tensor(redo, device=img.device)
+            img[sel], weight[sel], lab0[sel] = r[0], r[1], r[2]
+            redo = [k for k, v in zip(redo, r[3].tolist()) if v == 0]
+        return img, weight, lab0

@@ -5,8 +5,9 @@
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m cdnet_amd.train ...   # one process per GPU, RCCL all-reduce
 
 The reference's augmentation pipeline (albumentations / PIL RNG streams) and its CSV / tensorboard logging are outside
-the accelerated path: with a real dataset the loader below applies only random 256x256 crops,
-`LabelEncoding` (on the GPU) and `ToTensor`; `nn.DataParallel` (train.py:185) is replaced by one process per GPU."""
+the accelerated path: with a real dataset the loader below applies random 256x256 crops and flips,
+`LabelEncoding` (on the GPU) and `ToTensor` - with --device-augment the reference's whole default recipe (colour, flips, elastic,
+filter, crop) on the GPU; `nn.DataParallel` (train.py:185) is replaced by one process per GPU."""
 import argparse
 import logging
 import os
@@ -60,6 +61,11 @@ def main(argv=None):
     ap.add_argument('--synthetic', type=int, default=0, help='number of synthetic batches per epoch (0 = read the dataset folders)')
     ap.add_argument('--synthetic-val', type=int, default=0, help='synthetic validation batches per epoch (with --synthetic and --validation 1)')
     ap.add_argument('--trusted-pickle', action='store_true', help='resume from a legacy checkpoint that needs full unpickling (trusted source only)')
+    ap.add_argument('--device-augment', action='store_true',
+                    help="run the reference's whole training augmentation recipe on the device (cdnet_amd/augment.py)")
+    ap.add_argument('--elastic-alpha', type=float, default=1.0, help='random_elastic displacement scale (with --device-augment)')
+    ap.add_argument('--elastic-sigma', type=float, default=50.0, help='random_elastic displacement smoothing (with --device-augment)')
+    ap.add_argument('--elastic-alpha-affine', type=float, default=50.0, help='random_elastic affine point offsets (with --device-augment)')
     own, rest = ap.parse_known_args(argv)
     opt = Options(isTrain=True).parse(rest)
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -99,7 +105,9 @@ def main(argv=None):
         from .data_folder import DataFolder, TileBatches
         dir_list, post_fix = _dataset_layout(opt, 'train', logger)
         dset = DataFolder(dir_list, post_fix, [3, 1, 3])
-        loader = TileBatches(dset, opt.transform['train'], B, dev, seed=opt.train['seed'] + 1000 * rank, logger=logger)
+        elastic = dict(elastic_alpha=own.elastic_alpha, elastic_sigma=own.elastic_sigma, elastic_alpha_affine=own.elastic_alpha_affine)
+        loader = TileBatches(dset, opt.transform['train'], B, dev, seed=opt.train['seed'] + 1000 * rank, logger=logger,
+                             augment=own.device_augment, elastic=elastic)
         logger.info('{:d} training images in {:s}'.format(len(dset), dir_list[0]))
     # validation set (train.py:262-290: <img_dir>/val etc.) for the best-checkpoint / early-stopping logic of train.py:348-447
     val_loader = None

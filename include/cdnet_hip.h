@@ -511,6 +511,42 @@ int cdnet_window_stitch(const float *tiles, int K, int tile_h, int tile_w, int s
                         int Wv, float *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Training augmentation of the reference's default recipe, per sample on its whole source image, evaluated only where the crop needs it.
+ * Replaces my_transforms_direction.py:155-181 (RandomColor: Color, Brightness, Contrast, Sharpness blends), :224-259 (random horizontal /
+ * vertical flip), :262-352 (RandomElasticDeform, do_albu = 1: albumentations ElasticTransform(alpha, sigma, alpha_affine, nearest, zero
+ * border) = random affine + Gaussian-smoothed displacement field), :445-473 (RandomChooseAug: BLUR / GaussianBlur / MedianFilter / none)
+ * and :496-540 (RandomCrop; a source smaller than the crop is zero-padded with weight 0 instead of resized).
+ *   cdnet_aug_sample: one source (device pointers, row strides: img in bytes, weight in bytes, label in elements) and its drawn parameters:
+ *     minv = the inverse of the affine M (row-major 2 x 3, destination -> source pixel, in the flipped frame), color = the four factors,
+ *     filter 0 none / 1 BLUR / 2 GaussianBlur(2) / 3 MedianFilter(3), (y0, x0) the crop origin, alpha = 0: no displacement field,
+ *     seed: the field's counter-based noise.  label_i32 = 1: the label is an i32 instance-id plane, else u8 (channel 0 of the label image).
+ *   samples: the table in device memory; samples_host: the same table in host memory (validation and launch geometry).
+ *   norm_host: NULL or f32 [6] = mean[3], std[3] (the `normalize` transform).
+ * Outputs: image f32 [B][3][size][size] (/ 255, normalised), weight u8 [B][size][size], label u8 or i32 [B][size][size] (label_i32),
+ *   varied i32 [B] (0: the label crop holds one value - the DataFolder re-draw rule, data_folder.py:103-105), field NULL or
+ *   f32 [B][2][size + 12][size + 12] (dx, dy over the crop + 6 px, origin (y0 - 6, x0 - 6); else kept in the workspace).
+ * cdnet_augment_workspace_bytes: max_radius = the largest int(4 sigma + 0.5) of a sample with alpha != 0 (0 = none, at most 768); 0 for
+ *   bad sizes.
+ * Four launches (stats, two field passes when some alpha != 0, one tile pass).  The colour chain and the filters equal Pillow's bit for bit;
+ * the geometry restates OpenCV 4's nearest warpAffine / remap (cv2 parity unpinned).
+ * ---------------------------------------------------------------------------------------------------- */
+typedef struct cdnet_aug_sample {
+    double minv[6];
+    const uint8_t *img;
+    const uint8_t *weight;
+    const void *label;
+    int32_t H, W, img_stride, weight_stride, label_stride, label_i32;
+    float color[4];
+    int32_t hflip, vflip, filter, y0, x0;
+    float alpha, sigma;
+    uint32_t seed;
+} cdnet_aug_sample;
+size_t cdnet_augment_workspace_bytes(int B, int size, int max_radius);
+int cdnet_augment_batch(const cdnet_aug_sample *samples, const cdnet_aug_sample *samples_host, int B, int size, const float *norm_host,
+                        void *workspace, size_t workspace_bytes, float *image, uint8_t *weight, void *label, int label_i32, int32_t *varied,
+                        float *field, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * Training-target generation.  Replaces my_transforms_direction.py:687-885 `LabelEncoding.__call__` (3-class-PNG input,
  * do_direction = 1) with get_centerpoint2 (:650-685), Sobel.kernel (SegFix_offset_helper.py:97-132) and
  * DTOffsetHelper.align_angle / angle_to_vector / vector_to_label (:311-341, 423-450, 486-506).
