@@ -50,6 +50,10 @@ SIGNATURES = {
     'cdnet_tile_postproc': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _sz] + [_vp] * 10),
     'cdnet_cc_workspace_bytes': (_sz, [_i, _i, _i]),
     'cdnet_cc_chain': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'cdnet_mask_views_argmax': (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    'cdnet_tile_mask_postproc_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'cdnet_tile_mask_postproc': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _sz] + [_vp] * 8),
+    'cdnet_dilate_labels': (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     'cdnet_conv_packed_weight_elems': (_sz, [_i] * 6),
     'cdnet_pack_conv_weights': (_i, [_vp, _vp] + [_i] * 7 + [_vp]),
     'cdnet_pack_conv_weights_scaled': (_i, [_vp, _vp, _vp] + [_i] * 7 + [_vp]),

@@ -460,6 +460,55 @@ __global__ __launch_bounds__(256) void views_boost_kernel(const float *__restric
 }
 
 // ------------------------------------------------------------------------------------------------------
+// Mask-only TTA (test.py:216-275 with get_probmaps' softmax, :634) for networks without point / direction heads: the mean over V views of
+// the softmax of K mask logits, and its class, for whole images in ONE launch.  Tiles, lanes and the LDS transpose of rotated views are
+// views_boost_kernel's; the softmax is cdnet_probmaps' (mask_softmax); the mean is numpy's float32 `(p + p_hf + ... + p_r90_hvf) / 8`
+// (:267-268: view 0 initialises, later views add in view order, then one division); the class is mask_class (np.argmax / `>= 0.5`).
+// grid (ceil(W/32), ceil(H/32), I), block 256.  Scalar stores only (no alignment assumed).
+// ------------------------------------------------------------------------------------------------------
+template <int K>
+__global__ __launch_bounds__(256) void mask_views_kernel(const float *__restrict__ logits, int V, ViewXf xf, int H, int W,
+                                                         float *__restrict__ prob_mean, uint8_t *__restrict__ pred) {
+    __shared__ float s_tile[VT * (VT + 1)];
+    const int img = blockIdx.z;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int x0 = blockIdx.x * VT, y0 = blockIdx.y * VT;
+    const size_t plane = (size_t)H * W;
+    const float *lg = logits + (size_t)img * V * K * plane;
+    float s[K][4];
+    for (int v = 0; v < V; ++v) {
+        const float *q = lg + (size_t)v * K * plane;
+        float a[K][4];
+#pragma unroll
+        for (int c = 0; c < K; ++c) view_tile_load(q + (size_t)c * plane, xf.v[v], H, W, y0, x0, tx, ty, s_tile, a[c]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float l[K], p[K];
+#pragma unroll
+            for (int c = 0; c < K; ++c) l[c] = a[c][j];
+            mask_softmax<K>(l, p);
+#pragma unroll
+            for (int c = 0; c < K; ++c) s[c][j] = v == 0 ? p[c] : s[c][j] + p[c];
+        }
+    }
+    const float fv = (float)V;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int y = y0 + ty + 8 * j, x = x0 + tx;
+        if (y >= H || x >= W) continue;
+        const size_t p = (size_t)y * W + x;
+        float m[K];
+#pragma unroll
+        for (int c = 0; c < K; ++c) m[c] = s[c][j] / fv;
+        if (prob_mean) {
+#pragma unroll
+            for (int c = 0; c < K; ++c) prob_mean[((size_t)img * K + c) * plane + p] = m[c];
+        }
+        pred[(size_t)img * plane + p] = (uint8_t)mask_class<K>(m);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------
 // Connected components: union-find over pixel indices, roots = smallest (raster-first) index of a component.
 // One wave = 64 consecutive pixels of one row: the row runs come from a ballot, so only run heads talk to
 // the forest.  Block (64,4); grid (ceil(W/64), ceil(H/4), N).  L: int32 per pixel, -1 = not in the mask.
@@ -874,6 +923,35 @@ extern "C" int cdnet_tta_boost_argmax(const float *probs, const float *points, c
                                                ddm16, pred);
     }
     return check_launch("cdnet_tta_boost_argmax");
+}
+
+extern "C" int cdnet_mask_views_argmax(const float *logits, int I, int V, int K, const int *view_xform_host, int H, int W, float *prob_mean,
+                                       uint8_t *pred, void *stream) {
+    CDNET_REQUIRE(logits && view_xform_host && pred, "cdnet_mask_views_argmax: null pointer");
+    CDNET_REQUIRE(I > 0 && H > 0 && W > 0 && V >= 1 && V <= 16, "cdnet_mask_views_argmax: bad size I=%d V=%d H=%d W=%d", I, V, H, W);
+    CDNET_REQUIRE(K >= 1 && K <= 3, "cdnet_mask_views_argmax: K=%d mask channels not in {1,2,3}", K);
+    CDNET_REQUIRE((size_t)H * W < (1u << 30), "cdnet_mask_views_argmax: image too large");
+    ViewXf xf;
+    for (int v = 0; v < 16; ++v) {
+        xf.v[v] = v < V ? view_xform_host[v] : 0;
+        CDNET_REQUIRE(xf.v[v] >= 0 && xf.v[v] < 8, "cdnet_mask_views_argmax: view_xform[%d]=%d", v, xf.v[v]);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 gt(cdiv(W, VT), cdiv(H, VT), I);
+    if (K == 3) mask_views_kernel<3><<<gt, 256, 0, st>>>(logits, V, xf, H, W, prob_mean, pred);
+    else if (K == 2) mask_views_kernel<2><<<gt, 256, 0, st>>>(logits, V, xf, H, W, prob_mean, pred);
+    else mask_views_kernel<1><<<gt, 256, 0, st>>>(logits, V, xf, H, W, prob_mean, pred);
+    return check_launch("cdnet_mask_views_argmax");
+}
+
+extern "C" int cdnet_dilate_labels(const int32_t *label, int N, int H, int W, int radius, int32_t *out, void *stream) {
+    CDNET_REQUIRE(label && out, "cdnet_dilate_labels: null pointer");
+    CDNET_REQUIRE(N > 0 && H > 0 && W > 0, "cdnet_dilate_labels: bad size N=%d H=%d W=%d", N, H, W);
+    CDNET_REQUIRE(radius >= 0 && radius <= 8, "cdnet_dilate_labels: radius %d not in [0,8]", radius);
+    const size_t n = (size_t)N * H * W;
+    CDNET_REQUIRE(out + n <= label || label + n <= out, "cdnet_dilate_labels: out overlaps label (the dilation reads neighbours: no in-place form)");
+    dilate_disk_kernel<<<grid_rows(N, H, W), dim3(64, 4), 0, (hipStream_t)stream>>>(label, H, W, radius, out);
+    return check_launch("cdnet_dilate_labels");
 }
 
 // workspace layout (per call): L i32[N*P] | aux i32[N*P] | A u8[N*P] | B u8[N*P] | chunk i32[N*nchunk]

@@ -733,6 +733,37 @@ __global__ __launch_bounds__(1024) void tile_label8_kernel(const uint8_t *__rest
 
 }  // namespace
 
+// ------------------------------------------------------------------------------------------------------
+// Mask-only tiles (test.py:270-277 for one view, get_probmaps' softmax :634): softmax of K mask logits (mask_softmax), class (mask_class),
+// pred plane + foreground bit plane for tile_chain_kernel - tile_pred_kernel's output layout.  grid (P / 1024, B), block 256; P a multiple
+// of 64.  Scalar stores only (no alignment assumed beyond the 8-byte words of the bit plane).
+// ------------------------------------------------------------------------------------------------------
+template <int K>
+__global__ __launch_bounds__(256) void tile_mask_pred_kernel(const float *__restrict__ ml, int P, float *__restrict__ prob,
+                                                             uint8_t *__restrict__ pred, u64 *__restrict__ fgbits) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int n = blockIdx.y;
+    const size_t base = (size_t)n * P;
+    const float *m = ml + base * K;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int p = blockIdx.x * 1024 + k * 256 + tid;
+        if (p >= P) break;                                   // (P is a multiple of 64: whole waves leave together)
+        float a[K], q[K];
+#pragma unroll
+        for (int c = 0; c < K; ++c) a[c] = m[(size_t)c * P + p];
+        mask_softmax<K>(a, q);
+        if (prob) {
+#pragma unroll
+            for (int c = 0; c < K; ++c) prob[base * K + (size_t)c * P + p] = q[c];
+        }
+        const int cls = mask_class<K>(q);
+        pred[base + p] = (uint8_t)cls;
+        const u64 b = __ballot(cls == 1);
+        if (lane == 0) fgbits[(base + p) >> 6] = b;
+    }
+}
+
 #ifdef CDNET_TILE_STAMPS
 extern "C" int cdnet_debug_tile_stamps(unsigned long long *host_out) {
     return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_tile_stamps), sizeof(unsigned long long) * 64 * 32) == hipSuccess ? 0 : 3;
@@ -776,6 +807,28 @@ static bool tile_shape_ok(int B, int C, int H, int W) {
     return B > 0 && H > 0 && W > 0 && (C == 5 || C == 9 || C == 17) && W % 64 == 0 && (long long)H * W <= 65536;
 }
 
+// launch 3 of both tile chains (DAM and mask-only): tile_chain_kernel<R> on the foreground bit plane
+static int launch_tile_chain(const u64 *bits, int B, int H, int W, int min_area, int radius, int *area, uint8_t *fill, uint8_t *small,
+                             int32_t *label, int32_t *final_, int32_t *counts, hipStream_t st) {
+    constexpr int SMEM = 131072 + 3 * 8192 + (1024 + 64) * 4;
+    static bool attr = false;
+    if (!attr) {
+        const void *ks[4] = {reinterpret_cast<const void *>(tile_chain_kernel<0>), reinterpret_cast<const void *>(tile_chain_kernel<1>),
+                             reinterpret_cast<const void *>(tile_chain_kernel<2>), reinterpret_cast<const void *>(tile_chain_kernel<-1>)};
+        for (const void *k : ks)
+            if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM) != hipSuccess)
+                return check_launch("hipFuncSetAttribute(tile_chain)");
+        attr = true;
+    }
+#define CDNET_TILE_CHAIN(R_) tile_chain_kernel<R_><<<B, 1024, SMEM, st>>>(bits, H, W, min_area, radius, area, fill, small, label, final_, counts)
+    if (radius == 2) CDNET_TILE_CHAIN(2);
+    else if (radius == 1) CDNET_TILE_CHAIN(1);
+    else if (radius == 0) CDNET_TILE_CHAIN(0);
+    else CDNET_TILE_CHAIN(-1);
+#undef CDNET_TILE_CHAIN
+    return CDNET_OK;
+}
+
 extern "C" size_t cdnet_tile_postproc_workspace_bytes(int B, int C, int H, int W) {
     if (!tile_shape_ok(B, C, H, W)) return 0;
     size_t a, b, c, d, e;
@@ -814,21 +867,48 @@ extern "C" int cdnet_tile_postproc(const float *mask_logits, const float *dir_lo
     else if (C == 5) tile_maps_kernel<5><<<g1, b1, 0, st>>>(mask_logits, dir_logits, point, H, W, lut, nbr, extra_zero, prob, dcm, code, pmm, ppm);
     else tile_maps_kernel<17><<<g1, b1, 0, st>>>(mask_logits, dir_logits, point, H, W, lut, nbr, extra_zero, prob, dcm, code, pmm, ppm);
     tile_pred_kernel<<<dim3(cdiv(H * W, 1024), B), 256, 0, st>>>(mask_logits, point, code, pmm, ppm, nb, H, W, minmax, pred, bits);
-    constexpr int SMEM = 131072 + 3 * 8192 + (1024 + 64) * 4;
-    static bool attr = false;
-    if (!attr) {
-        const void *ks[4] = {reinterpret_cast<const void *>(tile_chain_kernel<0>), reinterpret_cast<const void *>(tile_chain_kernel<1>),
-                             reinterpret_cast<const void *>(tile_chain_kernel<2>), reinterpret_cast<const void *>(tile_chain_kernel<-1>)};
-        for (const void *k : ks)
-            if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM) != hipSuccess)
-                return check_launch("hipFuncSetAttribute(tile_chain)");
-        attr = true;
+    const int rc = launch_tile_chain(bits, B, H, W, min_area, radius, area, fill, small, label, final_, counts, st);
+    return rc != CDNET_OK ? rc : check_launch("cdnet_tile_postproc");
+}
+
+// workspace of the mask-only chain: area i32 [B*P] | fg bit plane u64 [B*P/64]
+static size_t tile_mask_ws_layout(int B, int H, int W, size_t *oArea, size_t *oBits) {
+    const size_t P = (size_t)H * W;
+    size_t off = 0;
+    *oArea = off; off = align_up(off + (size_t)B * P * 4, 256);
+    *oBits = off; off = align_up(off + (size_t)B * P / 8, 256);
+    return off;
+}
+
+extern "C" size_t cdnet_tile_mask_postproc_workspace_bytes(int B, int K, int H, int W) {
+    if (!tile_shape_ok(B, 9, H, W) || K < 1 || K > 3) return 0;
+    size_t a, b;
+    return tile_mask_ws_layout(B, H, W, &a, &b);
+}
+
+extern "C" int cdnet_tile_mask_postproc(const float *logits, int B, int K, int H, int W, int min_area, int radius, void *workspace,
+                                        size_t workspace_bytes, float *prob, uint8_t *pred, uint8_t *fill, uint8_t *small, int32_t *label,
+                                        int32_t *final_, int32_t *counts, void *stream) {
+    CDNET_REQUIRE(logits && workspace && pred && final_, "cdnet_tile_mask_postproc: null pointer");
+    CDNET_REQUIRE(K >= 1 && K <= 3, "cdnet_tile_mask_postproc: K=%d mask channels not in {1,2,3}", K);
+    CDNET_REQUIRE(tile_shape_ok(B, 9, H, W), "cdnet_tile_mask_postproc: B=%d H=%d W=%d: the fused tile chain takes W a multiple of 64 and at most "
+                  "65536 pixels per tile (cdnet_tile_mask_postproc_workspace_bytes returns 0 for other shapes: take cdnet_mask_views_argmax + "
+                  "cdnet_cc_chain)", B, H, W);
+    CDNET_REQUIRE(radius >= 0 && radius <= 8, "cdnet_tile_mask_postproc: radius %d not in [0,8]", radius);
+    size_t oArea, oBits;
+    const size_t need = tile_mask_ws_layout(B, H, W, &oArea, &oBits);
+    if (workspace_bytes < need) {
+        set_error("cdnet_tile_mask_postproc: workspace %zu < %zu bytes", workspace_bytes, need);
+        return CDNET_E_WORKSPACE;
     }
-#define CDNET_TILE_CHAIN(R_) tile_chain_kernel<R_><<<B, 1024, SMEM, st>>>(bits, H, W, min_area, radius, area, fill, small, label, final_, counts)
-    if (radius == 2) CDNET_TILE_CHAIN(2);
-    else if (radius == 1) CDNET_TILE_CHAIN(1);
-    else if (radius == 0) CDNET_TILE_CHAIN(0);
-    else CDNET_TILE_CHAIN(-1);
-#undef CDNET_TILE_CHAIN
-    return check_launch("cdnet_tile_postproc");
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    int *area = (int *)(ws + oArea);
+    u64 *bits = (u64 *)(ws + oBits);
+    const dim3 g1(cdiv(H * W, 1024), B);
+    if (K == 3) tile_mask_pred_kernel<3><<<g1, 256, 0, st>>>(logits, H * W, prob, pred, bits);
+    else if (K == 2) tile_mask_pred_kernel<2><<<g1, 256, 0, st>>>(logits, H * W, prob, pred, bits);
+    else tile_mask_pred_kernel<1><<<g1, 256, 0, st>>>(logits, H * W, prob, pred, bits);
+    const int rc = launch_tile_chain(bits, B, H, W, min_area, radius, area, fill, small, label, final_, counts, st);
+    return rc != CDNET_OK ? rc : check_launch("cdnet_tile_mask_postproc");
 }

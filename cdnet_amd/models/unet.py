@@ -82,12 +82,20 @@ class UNet(nn.Module):
         self._rt = rt
 
     def forward(self, x):
-        if self._rt is None:
-            self._build_runtime()
         if not x.is_cuda:
             raise RuntimeError('cdnet_amd.models.unet.UNet runs on the MI355X only (no CPU fallback)')
+        return self._forward_nhwc(runtime.input_pack(x.float()))
+
+    def forward_packed(self, x16):
+        """forward on already packed NHWC windows [N,H,W,16] (3 real channels; bf16, or fp32 in the fp32 precision mode) - what cdnet_window_pack
+        produces (sliding-window / TTA inference, cdnet_amd.utils.split_forward_views).  Returns `(logits,)`: the one output as a tuple."""
+        return (self._forward_nhwc(x16),)
+
+    def _forward_nhwc(self, x16):
+        if self._rt is None:
+            self._build_runtime()
         training = self.training
-        t = Src(runtime.input_pack(x.float()))
+        t = Src(x16)
         t.is_input = True
         self._rt['down'][0][0].needs_input_grad = False
         skips = []
@@ -103,7 +111,7 @@ class UNet(nn.Module):
             u.off = pad_offsets(u.logical_hw(), (sh, sw))
             t = c2.forward([c1.forward([skip, u], training, H=sh, W=sw)], training)   # cat([x_copy, x]) (:48)
         N, H, W, _ = t.x.shape
-        out = torch.empty((N, self.num_classes, H, W), dtype=torch.float32, device=x.device)
+        out = torch.empty((N, self.num_classes, H, W), dtype=torch.float32, device=x16.device)
         hf = runtime.head_feat(t)
         _lib.call('cdnet_final_conv1x1', C.byref(hf), _lib.ptr(self.final_conv.weight.detach().reshape(self.num_classes, 64).contiguous()),
                   _lib.ptr(self.final_conv.bias.detach()), self.num_classes, N, H, W, _lib.ptr(out), _lib.stream_ptr())

@@ -5,9 +5,12 @@ boost/argmax -> connected-component chain, without leaving the GPU (only the fin
 `infer_image`   : the reference's per-image procedure of test_dam.py:297-563: 8 dihedral TTA views, whole-image
                   forward (all_img_test == 1) or sliding windows (utils.split_forward_dam), per-view DDM, mean,
                   point-guided boost, CC chain.
+`infer_tiles_mask` / `infer_image_mask`: the same for networks with one mask output (UNet, output[0] of the model_unet_MandD* heads) -
+                  test.py:216-296: mean of the views' softmax, arg-max, CC chain (or the watershed variant with postproc 1).
 """
 import contextlib
 
+import numpy as np
 import torch
 
 from . import postproc
@@ -116,4 +119,97 @@ def infer_image(model, image, opt=None, tta=True, all_img_test=1, patch_size=256
     out = {k: (v[0] if torch.is_tensor(v) and v.dim() > 0 and v.shape[0] == 1 else v) for k, v in r.items()}
     if not defer:
         out['count'] = int(r['counts'][0])
+    return out
+
+
+def mask_channels(model):
+    """K, the number of mask logits of a network with a mask output (UNet: final_conv; the Unet family: mask_conv)"""
+    conv = getattr(model, 'mask_conv', None) or getattr(model, 'final_conv')
+    return int(conv.out_channels)
+
+
+def _mask_logits(out):
+    """the mask output of a forward: UNet's tensor, output[0] of the model_unet_MandD* heads' (mask, direction) (test.py:629-630)"""
+    if torch.is_tensor(out):
+        return out
+    if len(out) > 2:
+        raise ValueError('a network with %d outputs (mask, point, direction) is evaluated by cdnet_amd.test_dam, not the mask-only path' % len(out))
+    return out[0]
+
+
+@torch.no_grad()
+def infer_tiles_mask(model, x, min_area=20, radius=2, post_stream=None, want_stages=False, fused=True):
+    """Mask-only counterpart of infer_tiles: x float32 NCHW [B,3,H,W] on the GPU through a network with one mask output, then softmax, class
+    (arg-max; `>= 0.5` for one channel) and the CC chain - TWO launches (cdnet_tile_mask_postproc) when the shape allows (W a multiple of 64,
+    at most 65536 pixels per tile), else `mask_views_argmax` (one view) + `cc_chain`; `fused=False` takes that per-step form for every shape.
+    Returns dict(final int32 [B,H,W], counts int32 [B], pred u8 [B,H,W] [, prob, fill, small, label with want_stages]).
+    `post_stream`: as for infer_tiles - the post-processing is queued on that stream after this batch's forward and the call returns at once;
+    wait for `r['done']` before reading the results on another stream."""
+    assert not model.training
+    logits = _mask_logits(model(x))
+    B, K, H, W = logits.shape
+    ctx = contextlib.nullcontext()
+    if post_stream is not None:
+        post_stream.wait_stream(torch.cuda.current_stream())
+        logits.record_stream(post_stream)
+        ctx = torch.cuda.stream(post_stream)
+    with ctx:
+        if fused and postproc.tile_mask_postproc_eligible(B, K, H, W):
+            r = postproc.tile_mask_postproc(logits, min_area, radius, want_stages=want_stages)
+        else:
+            m = postproc.mask_views_argmax(logits, [0], H, W, want_prob=want_stages)
+            r = postproc.cc_chain(m['pred'], 1, min_area, radius, want_stages=want_stages)
+            r['pred'] = m['pred']
+            if want_stages:
+                r['prob'] = m['prob_mean']
+        if post_stream is not None:
+            r['done'] = torch.cuda.Event()
+            r['done'].record(post_stream)
+    return r
+
+
+@torch.no_grad()
+def infer_image_mask(model, image, opt=None, tta=True, all_img_test=1, patch_size=256, overlap=40, min_area=20, radius=2, postproc=0,
+                     model_mode='UNet', want_prob=False, defer=False):
+    """The reference's per-image procedure of test.py:213-296 for one image tensor [3,H,W] float32 on the GPU (already ToTensor'd /
+    normalised) and a network with one mask output: the eight dihedral views (TTA) - whole image (all_img_test == 1) or sliding windows
+    (utils.split_forward, :627) - stitched into ONE buffer, then ONE launch for every view's softmax, the mean and the class
+    (postproc.mask_views_argmax), then
+      postproc == 0: fill holes, remove small objects, 8-connected label, dilate (cc_chain on pred == 1, :277-295);
+      postproc == 1: postproc_other.process(pred_inside, model_mode, min_size=min_area) on the raw `pred == 1` (BEFORE fill holes, as
+                     :289-290 passes it), then the disk dilation (:295).  The reference passes model_mode = opt.model['modelName'] = 'UNet',
+                     and 'UNet' != 'unet' (postproc_other.py:35), so the watershed branch IS taken there: kept.
+    Returns dict(final int32 [H,W], pred u8 [H,W] [, prob_mean f32 [K,H,W] with want_prob] [, counts int32 [1] with postproc 0]; `count`
+    unless defer).  `defer=True`: nothing is read back (test.main pipelines images with this form)."""
+    from . import postproc as postproc_mod, postproc_other, utils          # (`postproc` is the reference's option name here)
+    if opt is not None:
+        tta, all_img_test = opt.test['tta'], opt.all_img_test
+        patch_size, overlap = opt.test['patch_size'], opt.test['overlap']
+        min_area, radius, postproc =  opt.post['min_area'], opt.post['radius'], int(opt.post['postproc'])
+        model_mode = opt.model['modelName']
+    assert not model.training and image.dim() == 3
+    _, H, W = image.shape
+    xforms = list(postproc_mod.TTA_XFORMS) if tta else [0]
+    V, K = len(xforms), mask_channels(model)
+    mask_all = torch.empty((V, K, H * W), dtype=torch.float32, device=image.device)
+    if all_img_test == 1:
+        utils.split_forward_views(model, image, max(H, W), 0, xforms, out=(mask_all,))
+    else:
+        utils.split_forward_views(model, image, patch_size, overlap, xforms, out=(mask_all,))
+    m = postproc_mod.mask_views_argmax(mask_all[None], xforms, H, W, want_prob=want_prob)
+    pred = m['pred']
+    if int(postproc) == 1:
+        lab = postproc_other.process((pred == 1).to(torch.uint8), model_mode, min_size=min_area)
+        out = dict(final=postproc_mod.dilate_labels(lab, radius)[0], pred=pred[0])
+    else:
+        cc = postproc_mod.cc_chain(pred, 1, min_area, radius)
+        out = dict(final=cc['final'][0], counts=cc['counts'], pred=pred[0])
+    if want_prob:
+        out['prob_mean'] = m['prob_mean'][0]
+    if not defer:
+        if 'counts' in out:
+            out['count'] = int(out['counts'][0])
+        else:                                              # (watershed labels keep their marker ids: count the distinct ones)
+            f = out['final'].cpu().numpy()
+            out['count'] = int(len(np.unique(f[f > 0])))
     return out

@@ -181,6 +181,73 @@ def tile_postproc(mask_logits, dir_logits, point, min_area=20, radius=2, want_st
     return out
 
 
+def mask_views_argmax(logits, xforms, H, W, want_prob=False):
+    """Mask-only TTA of test.py:216-275 in one launch (cdnet_mask_views_argmax): logits f32 [I,V,K,h_v*w_v] (or any shape with that element
+    count; view v in its own frame, a rotated view as [K][W][H]) -> dict(pred u8 [I,H,W] [, prob_mean f32 [I,K,H,W]]).  pred is the arg-max of
+    the mean softmax for K = 2 / 3 and `mean >= 0.5` for K = 1; foreground is pred == 1."""
+    assert logits.dtype == torch.float32 and logits.is_cuda
+    I, V = logits.shape[0], len(xforms)
+    logits = logits.contiguous()
+    assert logits.numel() % (I * V * H * W) == 0
+    K = logits.numel() // (I * V * H * W)
+    dev = logits.device
+    pred = torch.empty((I, H, W), dtype=torch.uint8, device=dev)
+    prob = torch.empty((I, K, H, W), dtype=torch.float32, device=dev) if want_prob else None
+    xf = (C.c_int * V)(*[int(x) for x in xforms])
+    _lib.call('cdnet_mask_views_argmax', _lib.ptr(logits), I, V, K, C.cast(xf, C.c_void_p), H, W, _lib.ptr(prob), _lib.ptr(pred),
+              _lib.stream_ptr())
+    out = dict(pred=pred)
+    if want_prob:
+        out['prob_mean'] = prob
+    return out
+
+
+def tile_mask_postproc_eligible(B, K, H, W):
+    """the two-launch mask-only chain takes this batch of tiles (W a multiple of 64, at most 65536 pixels per tile, K in 1..3)"""
+    return _lib.load().cdnet_tile_mask_postproc_workspace_bytes(int(B), int(K), int(H), int(W)) > 0
+
+
+def tile_mask_postproc(logits, min_area=20, radius=2, want_stages=False, want_prob=False):
+    """Post-processing of a batch of mask-only tiles in TWO launches (cdnet_tile_mask_postproc): softmax + class + foreground bits, then fill
+    holes / remove small / label / dilate of a tile inside one workgroup.  logits f32 [B,K,H,W] (what UNet.forward returns).
+    Returns dict(final i32 [B,H,W], counts i32 [B], pred u8 [B,H,W] [, prob] [, fill, small, label]) - bit-identical to
+    mask_views_argmax (one view) -> cc_chain(pred, 1)."""
+    assert logits.dtype == torch.float32 and logits.dim() == 4
+    B, K, H, W = logits.shape
+    dev = logits.device
+    logits = logits.contiguous()
+    nbytes = _lib.load().cdnet_tile_mask_postproc_workspace_bytes(B, K, H, W)
+    assert nbytes > 0, 'shape not served by the fused tile chain: ask tile_mask_postproc_eligible first'
+    ws = _workspace(nbytes, dev, 'tile_mask')
+    u8 = lambda: torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+    i32 = lambda: torch.empty((B, H, W), dtype=torch.int32, device=dev)
+    prob = torch.empty_like(logits) if (want_prob or want_stages) else None
+    pred, final = u8(), i32()
+    counts = torch.empty((B,), dtype=torch.int32, device=dev)
+    fill = small = label = None
+    if want_stages:
+        fill, small, label = u8(), u8(), i32()
+    _lib.call('cdnet_tile_mask_postproc', _lib.ptr(logits), B, K, H, W, int(min_area), int(radius), _lib.ptr(ws), ws.numel(), _lib.ptr(prob),
+              _lib.ptr(pred), _lib.ptr(fill), _lib.ptr(small), _lib.ptr(label), _lib.ptr(final), _lib.ptr(counts), _lib.stream_ptr())
+    out = dict(final=final, counts=counts, pred=pred)
+    if prob is not None:
+        out['prob'] = prob
+    if want_stages:
+        out.update(fill=fill, small=small, label=label)
+    return out
+
+
+def dilate_labels(lab, radius):
+    """skimage.morphology.dilation(lab, disk(radius)) of int32 label maps [N,H,W] or [H,W] (cdnet_dilate_labels; test.py:295) into a new
+    tensor"""
+    assert lab.dtype == torch.int32 and lab.dim() in (2, 3)
+    lab = lab.contiguous()
+    N, H, W = (1,) + tuple(lab.shape) if lab.dim() == 2 else tuple(lab.shape)
+    out = torch.empty_like(lab)
+    _lib.call('cdnet_dilate_labels', _lib.ptr(lab), N, H, W, int(radius), _lib.ptr(out), _lib.stream_ptr())
+    return out
+
+
 def postprocess_views(probs, points, dcms, xforms=None, H=None, W=None, classes=9, min_area=20, radius=2,
                       want_stages=False, check=True):
     """Everything after get_probmaps for I images with V views each (test_dam.py:445-563).

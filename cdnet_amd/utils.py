@@ -43,9 +43,11 @@ def window_grid(h0, w0, size, overlap):
 
 def split_forward_views(model, image, size, overlap, xforms=(0,), direction_classes=9, max_batch=128, out=None):
     """Sliding-window forward of one image [3,H,W] (cuda float32) for several TTA views at once.
-    Returns a list (one entry per view) of stitched logits (mask [3,hv,wv], point [1,hv,wv], direction [9,hv,wv]).
-    `out` = (mask f32 [V,3,H*W], point f32 [V,1,H*W], direction f32 [V,K,H*W]): the views are stitched straight into these buffers (a rotated
-    view as [K][W][H]: the same element count) - pipeline.infer_image's one get_probmaps launch over all views reads them in place."""
+    Returns a list (one entry per view) of the stitched logits of every output `model.forward_packed` returns: (mask [3,hv,wv], point [1,hv,wv],
+    direction [9,hv,wv]) for the DAM networks, (mask [K,hv,wv], direction) for the model_unet_MandD* heads, (mask [K,hv,wv],) for UNet.
+    `out` = one buffer per output, e.g. (mask f32 [V,3,H*W], point f32 [V,1,H*W], direction f32 [V,K,H*W]): the views are stitched straight
+    into these buffers (a rotated view as [K][W][H]: the same element count) - pipeline.infer_image's one get_probmaps launch over all views
+    reads them in place; pipeline.infer_image_mask passes the mask buffer alone and only the first output is stitched."""
     assert image.dim() == 3 and image.is_cuda and image.dtype == torch.float32
     Cc, H0, W0 = image.shape
     image = image.contiguous()
@@ -67,6 +69,8 @@ def split_forward_views(model, image, size, overlap, xforms=(0,), direction_clas
         n = ny * nx
         st = []
         for j_, t_ in enumerate(logits):
+            if out is not None and j_ >= len(out):
+                break                                      # (outputs the caller gave no buffer for are not stitched)
             K = t_.shape[1]
             o = torch.empty((K, hv, wv), dtype=torch.float32, device=image.device) if out is None else out[j_][i].view(K, hv, wv)
             src = t_[off:off + n]                          # (a batch slice of a contiguous tensor is contiguous)
@@ -106,6 +110,15 @@ def split_forward_views(model, image, size, overlap, xforms=(0,), direction_clas
             logits = [torch.cat([r[k] for r in res], 0) for k in range(len(res[0]))]
             outs[i] = stitch(i, logits, 0)
     return outs
+
+
+def split_forward(model, input, size, overlap, opt=None):
+    """split the input image for forward process (reference signature, utils.py:603-654): the sliding-window forward of a network with ONE
+    mask output (UNet; output[0] of the model_unet_MandD* heads).  input [1,C,H,W]; returns output [1,out_c,H,W] on the GPU."""
+    assert input.shape[0] == 1, 'the reference calls this with one image at a time'
+    with torch.no_grad():
+        outs, = split_forward_views(model, input[0].cuda().float(), size, overlap, (0,))
+    return outs[0][None]
 
 
 def split_forward_dam(model, input, size, overlap, opt=None):

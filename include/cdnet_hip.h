@@ -156,6 +156,35 @@ int cdnet_cc_chain(const uint8_t *pred, int fg_value, int N, int H, int W, int m
                    uint8_t *fill, uint8_t *small, int32_t *label, int32_t *final_, int32_t *counts,
                    void *stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Mask-only inference (networks with one mask output: UNet, and output[0] of the model_unet_MandD* ablation heads).  Replaces test.py:216-275
+ * (8-view TTA: per-view softmax of get_probmaps :634, np.flip / np.rot90(k=3) back to the image frame, the float32 mean
+ * `(p + p_hf + ... + p_r90_hvf) / 8` :267-268, `np.argmax(prob, 0)` :274 or `prob[0] >= 0.5` :270-272) and, for tiles, :277-295 too.
+ *
+ * cdnet_mask_views_argmax: ONE launch for I images of V views each.
+ *   logits f32 [I][V][K][h_v][w_v], K in {1,2,3}: view v in its own frame ([W][H] when rotated; view_xform_host as for
+ *   cdnet_tta_boost_argmax) - the buffer utils.split_forward_views(..., out=) stitches.  prob_mean f32 [I][K][H][W] or NULL (the mean
+ *   probabilities, test.py:376 saves plane 1); pred u8 [I][H][W]: K = 2 / 3 the arg-max with numpy's rules (first maximum, the first NaN wins),
+ *   K = 1 `mean >= 0.5` - a one-channel softmax is 1 wherever the logit is finite, so such a model marks every finite pixel foreground, as the
+ *   reference does.  Foreground is pred == 1 in every case.  Scalar stores: no alignment is assumed.
+ * cdnet_tile_mask_postproc: B independent tiles, one view each, in TWO launches: softmax / class / foreground bit plane, then the
+ *   connected-component chain of cdnet_tile_postproc's second launch (fill holes, remove small objects, 8-connected label, disk dilation:
+ *   test.py:277-295 with postproc 0).  logits f32 [B][K][H][W] (NCHW, as UNet.forward returns them); prob f32 [B][K][H][W] or NULL; pred u8;
+ *   fill / small u8 and label i32 or NULL (stage outputs); final i32 [B][H][W]; counts i32 [B].  Bit-identical to cdnet_mask_views_argmax
+ *   (V = 1, view 0) followed by cdnet_cc_chain(pred, fg_value = 1).  Shapes: W a multiple of 64 and H * W <= 65536 -
+ *   cdnet_tile_mask_postproc_workspace_bytes returns 0 for every other shape (and K); the bit plane's 8-byte words need an 8-byte aligned
+ *   workspace, the other stores are scalar.
+ * cdnet_dilate_labels: out = skimage.morphology.dilation(label, disk(radius)) (test.py:295 after postproc_other.process, :288-290), radius
+ *   0..8, label / out i32 [N][H][W]; out must not overlap label.  Scalar stores: no alignment is assumed.
+ * ---------------------------------------------------------------------------------------------------- */
+int cdnet_mask_views_argmax(const float *logits, int I, int V, int K, const int *view_xform_host, int H, int W, float *prob_mean,
+                            uint8_t *pred, void *stream);
+size_t cdnet_tile_mask_postproc_workspace_bytes(int B, int K, int H, int W);
+int cdnet_tile_mask_postproc(const float *logits, int B, int K, int H, int W, int min_area, int radius, void *workspace, size_t workspace_bytes,
+                             float *prob, uint8_t *pred, uint8_t *fill, uint8_t *small, int32_t *label, int32_t *final_, int32_t *counts,
+                             void *stream);
+int cdnet_dilate_labels(const int32_t *label, int N, int H, int W, int radius, int32_t *out, void *stream);
+
 
 /* ------------------------------------------------------------------------------------------------------
  * Convolution stack (MFMA implicit GEMM, NHWC bf16, fp32 accumulate).   Replaces the cuDNN/MIOpen calls behind
