@@ -89,6 +89,8 @@ SIGNATURES = {
     'cdnet_dam_val_sums_classes_workspace_floats': (_sz, [_i, _i, _i]),
     'cdnet_dam_val_sums_classes': (_i, [_vp] * 8 + [_i, _i, _i, _i, _vp, _sz, _vp, _vp]),
     'cdnet_adam_step': (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _i, _f, _vp]),
+    'cdnet_moment_step': (_i, [_vp, _vp, _vp, _vp, _vp, _sz, C.c_double, C.c_double, _f, _i, _i, _f, _f, _f, _f, _i, _f, _vp]),
+    'cdnet_sgd_step': (_i, [_vp, _vp, _vp, _sz, _f, _f, _f, _i, _f, _vp]),
     'cdnet_window_pack': (_i, [_vp] + [_i] * 9 + [_vp, _vp]),
     'cdnet_window_pack_f32': (_i, [_vp] + [_i] * 9 + [_vp, _vp]),
     'cdnet_window_stitch': (_i, [_vp] + [_i] * 9 + [_vp, _vp]),

@@ -1,5 +1,6 @@
 """Training entry point with the reference's shape (train.py:59-530, the part that is the hot path): options -> seeds ->
-`chooseModel` -> optimiser -> epochs of `train_util_dam.train` (or the plain-UNet step) -> checkpoint.
+`chooseModel` -> optimiser and scheduler (`utils.get_optimizer`) -> epochs of `train_util_dam.train` (or the plain-UNet step), each
+followed by the scheduler step -> checkpoint.
 
     python -m cdnet_amd.train --synthetic 64 --epochs 2              # synthetic tiles (no dataset needed)
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m cdnet_amd.train ...   # one process per GPU, RCCL all-reduce
@@ -19,7 +20,7 @@ import torch
 
 from . import checkpoint, synth, train_util_dam, utils
 from .options import Options
-from .trainer import synthetic_batch, UNetTrainer
+from .trainer import synthetic_batch
 
 
 class _SyntheticLoader:
@@ -83,10 +84,7 @@ def main(argv=None):
     np.random.seed(opt.train['seed'])
     model = utils.chooseModel(opt).to(dev)
     plain_unet = opt.model['modelName'] == 'UNet'
-    if plain_unet:
-        trainer = UNetTrainer(model, lr=opt.train['lr'], weight_decay=opt.train['weight_decay'], world_size=world)
-    else:
-        trainer, _ = utils.get_optimizer(opt, model, world_size=world)
+    trainer, scheduler = utils.get_optimizer(opt, model, world_size=world)       # train.py:191 (the plain UNet's trainer too)
     best_iou, best_loss = 0.0, float('inf')
     if opt.train['checkpoint']:                            # train.py:293-306: resume (weights, Adam moments, epoch, best values)
         if os.path.isfile(opt.train['checkpoint']):
@@ -149,6 +147,15 @@ def main(argv=None):
             val_loss, val_iou, val_F1 = float(res[0]), float(res[7]), float(res[10])
         is_best = val_iou > best_iou                       # train.py:385
         best_iou, new_best_loss = max(val_iou, best_iou), min(val_loss, best_loss)
+        # train.py:404-413: the rate of the next epoch - before the checkpoint is written, which therefore carries it.  val_loss is
+        # the cross-rank mean already, so every rank takes ReduceLROnPlateau's decision alike.
+        prev_lr = trainer.lr
+        if scheduler is None:
+            utils.adjust_learning_rate(opt, trainer, epoch)
+        else:
+            trainer.lr = scheduler.step(trainer.lr, val_loss)
+        if trainer.lr != prev_lr:
+            logger.info('===================== Updating learning rate from {} to {} ====================='.format(prev_lr, trainer.lr))
         if rank == 0 and opt.train.get('save_dir'):
             # train.py:406-427: checkpoint.pth.tar every epoch, numbered copies at checkpoint_freq, checkpoint_best on a new best
             if val_loader is None and plain_unet:

@@ -7,14 +7,15 @@ layer it (1) turns the consumers' gradients into the gradient of the raw convolu
 + max-pool/pad routing fused, cdnet_bn_backward), (2) computes dW on the matrix cores (cdnet_conv_backward_weight) and
 (3) computes the input gradient as a forward convolution with a flipped/transposed weight pack (cdnet_conv_forward).
 Parameters, gradients and the Adam moments live in flat fp32 buffers (one fused Adam launch, one all-reduce bucket
-sequence); the nn.Parameters of the model are views into them.
+sequence); the nn.Parameters of the model are views into them.  `Trainer(optimizer=)` selects the reference's other optimisers
+(utils.py:907-939: SGD, RAdam, RAdam_4step, AdamW, Ranger - csrc/optim.hip, cdnet_amd/optim.py) over the same buffers.
 """
 import ctypes as C
 import os
 
 import torch
 
-from . import _lib, engine, runtime, streams
+from . import _lib, engine, optim, runtime, streams
 from .engine import Src
 
 HEAD_PARAMS = ['point_conv.weight', 'direction_conv.weight', 'mask_conv.weight', 'point_conv.bias',
@@ -72,9 +73,11 @@ class _G:
 class FlatState:
     """fp32 flat buffers: parameters, gradients, Adam moments.  Head parameters first (in the kernel's block layout),
     then every other parameter that takes part in forward, then the reference's never-used parameters (no gradient,
-    never stepped - torch.optim.Adam skips parameters whose .grad is None)."""
+    never stepped - torch.optim.Adam skips parameters whose .grad is None).
+    The state buffers follow the optimiser: M is the first moment (SGD: the momentum buffer), V the second moment (none for SGD),
+    S Ranger's slow weights over the stepped parameters (none otherwise)."""
 
-    def __init__(self, model):
+    def __init__(self, model, optimizer='adam'):
         # a model that computes on zero-padded parameter copies (HRNet) hands those over; its own parameters stay views
         named = model.trainer_named_parameters() if hasattr(model, 'trainer_named_parameters') else dict(model.named_parameters())
         unused = [n for n in named if n.startswith(tuple(getattr(model, 'UNUSED_PREFIXES', ())))]
@@ -87,7 +90,8 @@ class FlatState:
         self.P = torch.empty((total,), dtype=torch.float32, device=dev)
         self.G = torch.zeros((total,), dtype=torch.float32, device=dev)
         self.M = torch.zeros((total,), dtype=torch.float32, device=dev)
-        self.V = torch.zeros((total,), dtype=torch.float32, device=dev)
+        self.V = None if optimizer == 'sgd' else torch.zeros((total,), dtype=torch.float32, device=dev)
+        self.S = None
         self.offsets = {}
         off = 0
         with torch.no_grad():
@@ -102,6 +106,8 @@ class FlatState:
             model.rebind_views()
         self.n_used = sum(named[n].numel() for n in head + rest)
         self.n_head = sum(named[n].numel() for n in head)
+        if optimizer == 'ranger':
+            self.S = self.P[:self.n_used].clone()            # (taken again when the first step starts, ranger.py:113-114)
         self.step_count = 0
 
 
@@ -125,16 +131,23 @@ class GradTerm(C.Structure):
 class Trainer:
     G = _G
 
-    def __init__(self, model, lr=1e-3, weight_decay=1e-4, betas=(0.9, 0.99), eps=1e-8, quirk_sample0=True,
-                 world_size=1, bucket_mb=25):
+    def __init__(self, model, lr=1e-3, weight_decay=1e-4, betas=(0.9, 0.99), eps=None, quirk_sample0=True,
+                 world_size=1, bucket_mb=25, optimizer='adam', momentum=0.95):
+        """optimizer: one of cdnet_amd.optim.OPTIMIZERS (utils.py:907-939, matched case-insensitively); momentum serves 'sgd' only;
+        eps None = the rule's own default (1e-5 for Ranger, ranger.py:28; 1e-8 otherwise)"""
         self.model = model
         self._pack_jobs = None
         self._ar = None
-        self.lr, self.wd, self.betas, self.eps = lr, weight_decay, betas, eps
+        self.optimizer = str(optimizer).lower()
+        if self.optimizer not in optim.OPTIMIZERS:
+            raise ValueError('Optimizer {} not available (one of {})'.format(optimizer, ', '.join(optim.OPTIMIZERS)))
+        if eps is None:
+            eps = optim.RANGER_EPS if self.optimizer == 'ranger' else 1e-8
+        self.lr, self.wd, self.betas, self.eps, self.momentum = lr, weight_decay, betas, eps, momentum
         self.quirk = int(quirk_sample0)
         self.world = world_size
         self.bucket = int(float(bucket_mb) * (1 << 20) // 4)
-        self.flat = FlatState(model)
+        self.flat = FlatState(model, self.optimizer)
         model._head_flat = self.flat.P[:self.flat.n_head] if self.flat.n_head == 855 else None
         self.dev = self.flat.P.device
         self._bufs = {}
@@ -171,7 +184,7 @@ class Trainer:
         if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
             return
         f = self.flat
-        works = [dist.broadcast(t, src=src, async_op=True) for t in (f.P, f.M, f.V)]
+        works = [dist.broadcast(t, src=src, async_op=True) for t in (f.P, f.M, f.V, f.S) if t is not None]
         meta = torch.tensor([float(f.step_count), float(self._bn_base + self._forwards)], dtype=torch.float64, device=self.dev)
         works.append(dist.broadcast(meta, src=src, async_op=True))
         bufs = [b for b in self.model.buffers() if b.is_floating_point()]
@@ -724,6 +737,8 @@ class Trainer:
             sl = slice(a, b)
             _lib.call('cdnet_adam_step', _lib.ptr(f.P[sl]), _lib.ptr(f.G[sl]), _lib.ptr(f.M[sl]), _lib.ptr(f.V[sl]), b - a, self.lr,
                       self.betas[0], self.betas[1], self.eps, self.wd, f.step_count, gscale, _lib.stream_ptr())
+        if self.optimizer != 'adam':
+            adam = self._rule_stepper(gscale)
         if works is None:
             adam(0, f.n_used)
         else:
@@ -732,6 +747,34 @@ class Trainer:
                 adam(a, b)
         runtime.WEIGHTS_EPOCH[0] += 1
         self._repack_all()
+
+    def _rule_stepper(self, gscale):
+        """step(a, b) of the optimisers besides Adam over the range [a, b) of the flat buffers (cdnet_moment_step / cdnet_sgd_step,
+        csrc/optim.hip); the step's host scalars are computed once (optim.moment_scalars).  Buffers on the CPU take the host
+        restatement of the same two kernels."""
+        f, rule, t = self.flat, self.optimizer, self.flat.step_count
+        on_host = self.dev.type == 'cpu'
+        if rule == 'sgd':
+            def step(a, b):
+                if on_host:
+                    optim.sgd_step_host(f.P[a:b], f.G[a:b], f.M[a:b], t, self.lr, self.momentum, self.wd, gscale)
+                else:
+                    _lib.call('cdnet_sgd_step', _lib.ptr(f.P[a:b]), _lib.ptr(f.G[a:b]), _lib.ptr(f.M[a:b]), b - a, self.lr, self.momentum,
+                              self.wd, t, gscale, _lib.stream_ptr())
+            return step
+        s = optim.moment_scalars(rule, t, self.lr, self.wd, self.betas, self.eps)
+        if rule == 'ranger' and t == 1:
+            f.S.copy_(f.P[:f.n_used])                    # the slow weights start as the parameters of the first step
+
+        def step(a, b):
+            slow = f.S[a:b] if s['sync'] else None
+            if on_host:
+                optim.moment_step_host(f.P[a:b], f.G[a:b], f.M[a:b], f.V[a:b], slow, s, self.betas, gscale)
+            else:
+                _lib.call('cdnet_moment_step', _lib.ptr(f.P[a:b]), _lib.ptr(f.G[a:b]), _lib.ptr(f.M[a:b]), _lib.ptr(f.V[a:b]), _lib.ptr(slow),
+                          b - a, self.betas[0], self.betas[1], gscale, s['move'], s['rect'], s['decay'], s['step_size'], s['v_div'], s['eps'],
+                          s['sync'], s['alpha'], _lib.stream_ptr())
+        return step
 
     def _repack_all(self):
         """Re-pack every layer's forward / backward-data weights in one launch (they would otherwise be re-packed one by
@@ -811,42 +854,113 @@ class Trainer:
             self.model._ensure_runtime()
         runtime.WEIGHTS_EPOCH[0] += 1
 
+    def _gather(self, buf, n, p):
+        """CPU copy, in the model's own shape, of parameter `n`'s part of the flat state buffer `buf`"""
+        t = torch.empty(p.shape, dtype=torch.float32)
+        for idx, piece in self._real_pieces(buf, n, p):
+            t[idx] = piece.cpu()
+        return t
+
+    def _scatter(self, buf, n, p, value):
+        for idx, piece in self._real_pieces(buf, n, p):
+            piece.copy_(value[idx])
+
+    # state buffers of one parameter under the reference classes' own key names (torch.optim.SGD, hhl_utils/radam.py, ranger.py)
+    def _state_buffers(self):
+        f = self.flat
+        if self.optimizer == 'sgd':
+            return [('momentum_buffer', f.M)]
+        return [('exp_avg', f.M), ('exp_avg_sq', f.V)] + ([('slow_buffer', f.S)] if self.optimizer == 'ranger' else [])
+
     def state_dict(self):
+        """the optimiser entry of a checkpoint in the layout of the reference's object for this optimiser: torch.optim.Adam / SGD,
+        RAdam, RAdam_4step, AdamW (hhl_utils/radam.py) or Ranger (hhl_utils/ranger.py).  'step' is a tensor for Adam (torch's own
+        format) and an int for the reference's classes; torch's SGD keeps no step (see load_state_dict)."""
         f = self.flat
         params = list(self.model.named_parameters())
         state = {}
+        rule = self.optimizer
         if f.step_count > 0:
             for i, (n, p) in enumerate(params):
                 if f.offsets[n][0] >= f.n_used:
                     continue                                        # the reference's never-used parameters: no gradient, no state
-                m, v = torch.empty(p.shape, dtype=torch.float32), torch.empty(p.shape, dtype=torch.float32)
-                for idx, piece in self._real_pieces(f.M, n, p):
-                    m[idx] = piece.cpu()
-                for idx, piece in self._real_pieces(f.V, n, p):
-                    v[idx] = piece.cpu()
-                state[i] = {'step': torch.tensor(float(f.step_count)), 'exp_avg': m, 'exp_avg_sq': v}
-        group = dict(lr=self.lr, betas=tuple(self.betas), eps=self.eps, weight_decay=self.wd, amsgrad=False, maximize=False, foreach=None,
-                     capturable=False, differentiable=False, fused=None, params=list(range(len(params))))
+                if rule == 'adam':
+                    state[i] = {'step': torch.tensor(float(f.step_count)), 'exp_avg': self._gather(f.M, n, p), 'exp_avg_sq': self._gather(f.V, n, p)}
+                    continue
+                st = {} if rule == 'sgd' else {'step': int(f.step_count)}
+                for key, buf in self._state_buffers():
+                    st[key] = self._gather(buf, n, p)
+                state[i] = st
+        ids = list(range(len(params)))
+        if rule == 'adam':
+            group = dict(lr=self.lr, betas=tuple(self.betas), eps=self.eps, weight_decay=self.wd, amsgrad=False, maximize=False, foreach=None,
+                         capturable=False, differentiable=False, fused=None, params=ids)
+        elif rule == 'sgd':
+            # torch's own group, whatever keys the installed torch writes
+            group = torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=self.lr, momentum=self.momentum,
+                                    weight_decay=self.wd).state_dict()['param_groups'][0]
+            group['params'] = ids
+        else:
+            group = dict(lr=self.lr, betas=tuple(self.betas), eps=self.eps, weight_decay=self.wd)
+            if rule == 'adamw':
+                group.update(use_variance=True, warmup=optim.ADAMW_WARMUP)
+            if rule == 'ranger':
+                group.update(alpha=optim.RANGER_ALPHA, k=optim.RANGER_K, step_counter=0, N_sma_threshhold=optim.RANGER_THRESHOLD)
+            group['params'] = ids
         return {'state': state, 'param_groups': [group]}
 
+    @staticmethod
+    def _layout_of(sd):
+        """which optimiser family wrote `sd`: read off the keys only that family's object has"""
+        group = sd['param_groups'][0]
+        keys = set(group)
+        for st in sd['state'].values():
+            keys |= set(st)
+            break
+        if 'momentum_buffer' in keys or 'nesterov' in keys:
+            return 'sgd'
+        if 'slow_buffer' in keys or 'N_sma_threshhold' in keys:
+            return 'ranger'
+        if 'warmup' in keys:
+            return 'adamw'
+        if 'amsgrad' in keys:
+            return 'adam'
+        return 'radam' if 'betas' in keys else 'unknown'
+
     def load_state_dict(self, sd):
+        """Takes the state of the reference's object for THIS optimiser (RAdam and RAdam_4step share one layout); a state written by
+        another optimiser raises instead of silently starting from zero moments.  torch.optim.SGD stores no step count and the rule
+        only asks whether a momentum buffer exists yet (buf = g on the very first step): a loaded SGD state with momentum buffers
+        continues at step_count 1, one without them at 0."""
         f = self.flat
         params = list(self.model.named_parameters())
         group = sd['param_groups'][0]
         assert len(sd['param_groups']) == 1 and len(group['params']) == len(params), 'optimizer state of a different model'
-        self.lr, self.betas, self.eps, self.wd = group['lr'], tuple(group['betas']), group['eps'], group['weight_decay']
-        f.M.zero_()
-        f.V.zero_()
+        rule = self.optimizer
+        mine, theirs = ('radam' if rule == 'radam4s' else rule), self._layout_of(sd)
+        if theirs != mine:
+            raise ValueError("optimizer state with the layout of '{}' cannot continue a '{}' run (param group keys: {})".format(
+                theirs, rule, ', '.join(sorted(k for k in group if k != 'params'))))
+        if rule == 'sgd':
+            self.lr, self.wd, self.momentum = group['lr'], group['weight_decay'], group['momentum']
+        else:
+            self.lr, self.betas, self.eps, self.wd = group['lr'], tuple(group['betas']), group['eps'], group['weight_decay']
+        bufs = self._state_buffers()
+        for _, buf in bufs:
+            if buf is not f.S:
+                buf.zero_()
+        if f.S is not None:
+            f.S.copy_(f.P[:f.n_used])
         steps = set()
         for i, st in sd['state'].items():
             n, p = params[int(i)]
             assert f.offsets[n][0] < f.n_used, 'state for a parameter that is never stepped: ' + n
-            for idx, piece in self._real_pieces(f.M, n, p):
-                piece.copy_(st['exp_avg'][idx])
-            for idx, piece in self._real_pieces(f.V, n, p):
-                piece.copy_(st['exp_avg_sq'][idx])
-            steps.add(int(st['step']))
-        assert len(steps) <= 1, 'per-parameter step counts differ: not a state of torch.optim.Adam over the whole model'
+            for key, buf in bufs:
+                if key not in st or st[key] is None:
+                    raise ValueError("optimizer state of parameter {} lacks '{}': not a state of '{}'".format(n, key, rule))
+                self._scatter(buf, n, p, st[key])
+            steps.add(1 if rule == 'sgd' else int(st['step']))
+        assert len(steps) <= 1, 'per-parameter step counts differ: not a state of one optimiser over the whole model'
         f.step_count = steps.pop() if steps else 0
 
     def train_step(self, x, label, dirlab, point_t, weight):

@@ -2,7 +2,7 @@
 
   chooseModel(opt)                                     utils.py:816-886
   split_forward_dam(model, input, size, overlap, opt)  utils.py:658-726
-  get_optimizer(args, model)                           utils.py:907-962   (Adam path; returns the fused device optimiser)
+  get_optimizer(args, model)                           utils.py:907-962   (returns the fused device optimiser and the scheduler)
   AverageMeter                                         utils.py:755-774
   adjust_learning_rate                                 utils.py:965-977
 """
@@ -152,19 +152,39 @@ class AverageMeter(object):
         self.avg = self.sum / self.count
 
 
+def trainer_class(model):
+    """the Trainer that serves `model`: the plain UNet's (one mask output), the ablation heads' (plain classifiers instead of the gated
+    head, model_unet_MandD / model_unet_MandDandP), the DAM networks'"""
+    from .models.unet import UNet
+    from .trainer import Trainer, AblationTrainer, UNetTrainer
+    if isinstance(model, UNet):
+        return UNetTrainer
+    return AblationTrainer if getattr(model, 'VARIANT', 'rev1') != 'rev1' else Trainer
+
+
 def get_optimizer(args, model, world_size=1):
-    """utils.py:907-962 for the default 'adam' (lr, betas=(0.9, 0.99), weight_decay): returns (Trainer, None) - the
-    fused device optimiser lives inside cdnet_amd.trainer.Trainer."""
-    if args.train['optimizer'].lower() != 'adam':
-        raise NotImplementedError("only the reference's default optimizer 'adam' is on the hot path")
-    from .trainer import Trainer, AblationTrainer
-    # the ablation heads (model_unet_MandD / model_unet_MandDandP) train with plain classifiers instead of the gated head
-    cls = AblationTrainer if getattr(model, 'VARIANT', 'rev1') != 'rev1' else Trainer
-    return cls(model, lr=args.train['lr'], weight_decay=args.train['weight_decay'], world_size=world_size), None
+    """utils.py:907-962: returns (Trainer, scheduler).  The fused device optimiser lives inside cdnet_amd.trainer.Trainer - 'adam'
+    (lr, betas=(0.9, 0.99), weight_decay; cdnet_adam_step) or one of 'sgd' (momentum = args.momentum), 'radam', 'radam4s', 'adamw',
+    'ranger' (cdnet_sgd_step / cdnet_moment_step), matched case-insensitively.  An unknown name raises ValueError (the reference's
+    `raise '<str>'` is a TypeError by accident).  The scheduler is an optim.LRSchedule for the four torch schedulers of :941-957 and None
+    otherwise (the epoch loop then calls adjust_learning_rate, train.py:404-405)."""
+    from . import optim
+    name = str(args.train['optimizer']).lower()
+    if name not in optim.OPTIMIZERS:
+        raise ValueError('Optimizer {} not available'.format(args.train['optimizer']))
+    trainer = trainer_class(model)(model, lr=args.train['lr'], weight_decay=args.train['weight_decay'], world_size=world_size,
+                                   optimizer=name, momentum=getattr(args, 'momentum', 0.95))
+    scheduler = None
+    if args.train['scheduler'] in optim.SCHEDULERS:
+        scheduler = optim.LRSchedule(args.train['scheduler'], args.train['lr'], step=args.train['step'], lr_decay=args.train['lr_decay'])
+    return trainer, scheduler
 
 
 def adjust_learning_rate(args, trainer, epoch):
-    """utils.py:965-977: scheduler 'None' keeps the learning rate constant"""
+    """utils.py:965-977: scheduler 'None' keeps the learning rate constant; any other name (the four of get_optimizer have a scheduler
+    object and never come here) sets lr * 0.9 ** (epoch // step)"""
+    if args.train['scheduler'] != 'None':
+        trainer.lr = args.train['lr'] * (0.9 ** (epoch // args.train['step']))
     return trainer.lr
 
 

@@ -522,6 +522,30 @@ int cdnet_dam_val_sums_classes(const float *mask, const float *point, const floa
 int cdnet_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, size_t n, float lr, float beta1,
                     float beta2, float eps, float weight_decay, int step, float grad_scale, void *stream);
 
+/* The reference's other optimisers (utils.py:907-939) on flat fp32 buffers.  The step-dependent coefficients are host
+ * scalars: the caller computes them in double, as the reference does with math.sqrt and **, and passes them as float
+ * (cdnet_amd/optim.py: moment_scalars).  Any 4-byte aligned slice of the flat buffers is served (16-byte accesses on the
+ * aligned body when the buffers share one alignment).
+ *
+ * cdnet_moment_step - one update of the four moment rules, per element:
+ *     g = grad * grad_scale;  v = v * beta2 + (1 - beta2) * g * g;  m = m * beta1 + (1 - beta1) * g       (always)
+ *     move: p = p + (-decay) * p;  p = rect ? p - step_size * m / (sqrt(v) / v_div + eps) : p - step_size * m
+ *     sync: slow = slow + alpha * (p - slow);  p = slow
+ *   RAdam (hhl_utils/radam.py:6-81): rect = N_sma >= 5, decay = weight_decay * lr, v_div = 1, eps 1e-8.
+ *   RAdam_4step(update_all=False, additional_four=False) (radam.py:84-180, utils.py:923-928): move = 0 for steps 1-4 (the moments
+ *     advance, the parameters stay), then always rectified with v_div = sqrt(1 - beta2^t) and no (1 - beta2^t) in step_size.
+ *   AdamW(warmup=4000) (radam.py:183-252, utils.py:929-932): rect = 1, step_size and decay from the warm-up rate lr_t, v_div = 1.
+ *   Ranger (hhl_utils/ranger.py:26-165, utils.py:933-935): RAdam with rect = N_sma > 5, eps 1e-5, and the lookahead sync every
+ *     k = 6 steps with alpha = 0.5; `slow` holds the parameters as they were when the first step started (ranger.py:113-114).
+ *   `slow` may be NULL unless sync is set.  beta1 / beta2 are doubles so that (1 - beta) rounds to float as torch rounds it.
+ * cdnet_sgd_step - torch.optim.SGD(lr, momentum, weight_decay), dampening 0, no Nesterov (utils.py:910-914): g = grad * grad_scale +
+ *   weight_decay * p; buf = g at step 1, else momentum * buf + g; p = p - lr * buf.  `step` is 1-based. */
+int cdnet_moment_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, float *slow, size_t n, double beta1,
+                      double beta2, float grad_scale, int move, int rect, float decay, float step_size, float v_div, float eps,
+                      int sync, float alpha, void *stream);
+int cdnet_sgd_step(float *param, const float *grad, float *momentum_buffer, size_t n, float lr, float momentum, float weight_decay,
+                   int step, float grad_scale, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Sliding-window inference.  Replaces utils.split_forward_dam (utils.py:658-726) and the construction of the eight
  * test-time-augmentation views (test_dam.py:313-385) without ever materialising a flipped / rotated / padded image.
