@@ -142,6 +142,11 @@ def call(name, *args):
     check(getattr(load(), name)(*args), name)
 
 
+def entry(name, f32):
+    """the fp32 twin `<name>_f32` of an entry point that exists once per activation type, or `name` itself (the 16-bit one)"""
+    return name + '_f32' if f32 else name
+
+
 _RAW_STREAM = None
 
 

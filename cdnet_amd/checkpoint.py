@@ -5,7 +5,7 @@ The reference saves {'epoch', 'state_dict', 'best_iou', 'best_loss', 'optimizer'
 checkpoint_best.pth.tar (save_checkpoint, train.py:461-480) and loads them with load_state_dict (train.py:297-302,
 test_dam.py:163-165).  The files written here load in the reference and vice versa: parameter names and shapes are the
 reference's, and the optimiser entry is the state_dict of the reference's optimiser object - torch.optim.Adam by default, torch.optim.SGD,
-RAdam / RAdam_4step / AdamW or Ranger for the other --optimizer values (cdnet_amd.trainer.Trainer.state_dict)."""
+RAdam / RAdam_4step / AdamW or Ranger for the other --optimizer values (cdnet_amd.optim.state_dict through Trainer.state_dict)."""
 import os
 import shutil
 

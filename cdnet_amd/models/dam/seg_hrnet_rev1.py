@@ -276,7 +276,7 @@ class HighResolutionNet(nn.Module):
         return super().state_dict(*args, **kwargs)
 
     def trainer_named_parameters(self):
-        """name -> compute parameter, in forward order where it matters to the trainer (cdnet_amd.trainer.FlatState)"""
+        """name -> compute parameter, in forward order where it matters to the trainer (cdnet_amd.optim.FlatState)"""
         self._ensure_runtime()
         return {n: self._pmap.get(id(p), p) for n, p in self.named_parameters()}
 

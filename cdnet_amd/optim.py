@@ -1,5 +1,9 @@
 """Host side of the reference's optimisers and learning-rate schedulers (utils.py:907-977).
 
+  FlatState                           the flat fp32 buffers of a trainer: parameters, gradients, the optimiser's state
+  stepper(tr, grad_scale)             step(a, b) of the trainer's rule over a range of the flat buffers: cdnet_adam_step (csrc/train.hip),
+                                      cdnet_sgd_step / cdnet_moment_step (csrc/optim.hip)
+  state_dict / load_state_dict        the optimiser entry of a checkpoint in the layout of the reference's object for the rule
   moment_scalars(rule, t, lr, wd)     the host scalars of step t of 'radam' / 'radam4s' / 'adamw' / 'ranger', computed in
                                       Python float like the reference's math.sqrt / ** (hhl_utils/radam.py, hhl_utils/ranger.py);
                                       cdnet_moment_step (csrc/optim.hip) takes them as float
@@ -10,6 +14,9 @@
 import math
 
 import numpy as np
+import torch
+
+from . import _lib
 
 OPTIMIZERS = ('sgd', 'adam', 'radam', 'radam4s', 'adamw', 'ranger')            # utils.py:910-935, matched case-insensitively
 MOMENT_RULES = ('radam', 'radam4s', 'adamw', 'ranger')
@@ -91,6 +98,215 @@ def sgd_step_host(p, g, buf, t, lr, momentum, wd, grad_scale=1.0):
     p[:] = p + f(-lr) * buf
 
 
+# the order of cdnet_dam_head_backward's weight block (csrc/train.hip), which FlatState puts first
+HEAD_PARAMS = ['point_conv.weight', 'direction_conv.weight', 'mask_conv.weight', 'point_conv.bias',
+               'direction_conv.bias', 'mask_conv.bias', 'directionAtt.Conv1x1.weight', 'maskAtt.Conv1x1.weight']
+
+
+class FlatState:
+    """fp32 flat buffers: parameters, gradients, Adam moments.  Head parameters first (in the kernel's block layout),
+    then every other parameter that takes part in forward, then the reference's never-used parameters (no gradient,
+    never stepped - torch.optim.Adam skips parameters whose .grad is None).
+    The state buffers follow the optimiser: M is the first moment (SGD: the momentum buffer), V the second moment (none for SGD),
+    S Ranger's slow weights over the stepped parameters (none otherwise)."""
+
+    def __init__(self, model, optimizer='adam'):
+        # a model that computes on zero-padded parameter copies (HRNet) hands those over; its own parameters stay views
+        named = model.trainer_named_parameters() if hasattr(model, 'trainer_named_parameters') else dict(model.named_parameters())
+        unused = [n for n in named if n.startswith(tuple(getattr(model, 'UNUSED_PREFIXES', ())))]
+        head = [n for n in HEAD_PARAMS if n in named and n not in unused]
+        rest = [n for n in named if n not in head and n not in unused]
+        self.order = head + rest + unused
+        sizes = [named[n].numel() for n in self.order]
+        total = sum(sizes)
+        dev = next(model.parameters()).device
+        self.P = torch.empty((total,), dtype=torch.float32, device=dev)
+        self.G = torch.zeros((total,), dtype=torch.float32, device=dev)
+        self.M = torch.zeros((total,), dtype=torch.float32, device=dev)
+        self.V = None if optimizer == 'sgd' else torch.zeros((total,), dtype=torch.float32, device=dev)
+        self.S = None
+        self.offsets = {}
+        off = 0
+        with torch.no_grad():
+            for n, sz in zip(self.order, sizes):
+                p = named[n]
+                self.P[off:off + sz].copy_(p.detach().reshape(-1))         # one-time host-side setup
+                p.data = self.P[off:off + sz].view(p.shape)
+                p.grad = self.G[off:off + sz].view(p.shape)
+                self.offsets[n] = (off, sz)
+                off += sz
+        if hasattr(model, 'rebind_views'):
+            model.rebind_views()
+        self.n_used = sum(named[n].numel() for n in head + rest)
+        self.n_head = sum(named[n].numel() for n in head)
+        if optimizer == 'ranger':
+            self.S = self.P[:self.n_used].clone()            # (taken again when the first step starts, ranger.py:113-114)
+        self.step_count = 0
+
+
+def stepper(tr, grad_scale):
+    """step(a, b): step `tr.flat.step_count` of the trainer's rule over the range [a, b) of its flat buffers, the gradients times
+    grad_scale.  `tr` gives flat, optimizer, lr, wd, betas, eps, momentum and dev.  The step's host scalars are computed once
+    (moment_scalars).  Buffers on the CPU take the host restatement of cdnet_sgd_step / cdnet_moment_step."""
+    f, rule, t = tr.flat, tr.optimizer, tr.flat.step_count
+    on_host = tr.dev.type == 'cpu'
+    if rule == 'adam':
+        def step(a, b):
+            _lib.call('cdnet_adam_step', _lib.ptr(f.P[a:b]), _lib.ptr(f.G[a:b]), _lib.ptr(f.M[a:b]), _lib.ptr(f.V[a:b]), b - a, tr.lr,
+                      tr.betas[0], tr.betas[1], tr.eps, tr.wd, t, grad_scale, _lib.stream_ptr())
+        return step
+    if rule == 'sgd':
+        def step(a, b):
+            if on_host:
+                sgd_step_host(f.P[a:b], f.G[a:b], f.M[a:b], t, tr.lr, tr.momentum, tr.wd, grad_scale)
+            else:
+                _lib.call('cdnet_sgd_step', _lib.ptr(f.P[a:b]), _lib.ptr(f.G[a:b]), _lib.ptr(f.M[a:b]), b - a, tr.lr, tr.momentum,
+                          tr.wd, t, grad_scale, _lib.stream_ptr())
+        return step
+    s = moment_scalars(rule, t, tr.lr, tr.wd, tr.betas, tr.eps)
+    if rule == 'ranger' and t == 1:
+        f.S.copy_(f.P[:f.n_used])                    # the slow weights start as the parameters of the first step
+
+    def step(a, b):
+        slow = f.S[a:b] if s['sync'] else None
+        if on_host:
+            moment_step_host(f.P[a:b], f.G[a:b], f.M[a:b], f.V[a:b], slow, s, tr.betas, grad_scale)
+        else:
+            _lib.call('cdnet_moment_step', _lib.ptr(f.P[a:b]), _lib.ptr(f.G[a:b]), _lib.ptr(f.M[a:b]), _lib.ptr(f.V[a:b]), _lib.ptr(slow),
+                      b - a, tr.betas[0], tr.betas[1], grad_scale, s['move'], s['rect'], s['decay'], s['step_size'], s['v_div'], s['eps'],
+                      s['sync'], s['alpha'], _lib.stream_ptr())
+    return step
+
+
+# ----------------------------------------------------------------------------------------------------------
+# Optimiser state in the state_dict format of the reference's optimiser object (what the reference stores under
+# checkpoint['optimizer'], train.py:421-427, and reads back at :302): parameter indices follow model.parameters(); parameters that
+# never received a gradient have no entry (the optimisers create state lazily).  `tr` is the trainer that owns the flat buffers.
+def _real_pieces(tr, buf, name, p):
+    """[(index into the real parameter, view of `buf`)] covering parameter `name` (the model's own shape), whether the flat
+    storage holds it as is, zero-padded (leading corner) or scattered over channel segments (HRNet)"""
+    off, sz = tr.flat.offsets[name]
+    slots = {id(real): (pp, segs) for real, pp, segs in getattr(tr.model, '_slots', [])}
+    if id(p) not in slots:
+        return [(Ellipsis, buf[off:off + sz].view(p.shape))]
+    pp, segs = slots[id(p)]
+    full = buf[off:off + sz].view(pp.shape)
+    if segs is None:
+        return [(Ellipsis, full[tuple(slice(0, n) for n in p.shape)])]
+    return [((slice(None), slice(r0, r0 + n)), full[:, p0:p0 + n]) for r0, n, p0 in segs]
+
+
+def _gather(tr, buf, n, p):
+    """CPU copy, in the model's own shape, of parameter `n`'s part of the flat state buffer `buf`"""
+    t = torch.empty(p.shape, dtype=torch.float32)
+    for idx, piece in _real_pieces(tr, buf, n, p):
+        t[idx] = piece.cpu()
+    return t
+
+
+def _scatter(tr, buf, n, p, value):
+    for idx, piece in _real_pieces(tr, buf, n, p):
+        piece.copy_(value[idx])
+
+
+def _state_buffers(tr):
+    """state buffers of one parameter under the reference classes' own key names (torch.optim.SGD, hhl_utils/radam.py, ranger.py)"""
+    f = tr.flat
+    if tr.optimizer == 'sgd':
+        return [('momentum_buffer', f.M)]
+    return [('exp_avg', f.M), ('exp_avg_sq', f.V)] + ([('slow_buffer', f.S)] if tr.optimizer == 'ranger' else [])
+
+
+def state_dict(tr):
+    """the optimiser entry of a checkpoint in the layout of the reference's object for this optimiser: torch.optim.Adam / SGD,
+    RAdam, RAdam_4step, AdamW (hhl_utils/radam.py) or Ranger (hhl_utils/ranger.py).  'step' is a tensor for Adam (torch's own
+    format) and an int for the reference's classes; torch's SGD keeps no step (see load_state_dict)."""
+    f = tr.flat
+    params = list(tr.model.named_parameters())
+    state = {}
+    rule = tr.optimizer
+    if f.step_count > 0:
+        for i, (n, p) in enumerate(params):
+            if f.offsets[n][0] >= f.n_used:
+                continue                                        # the reference's never-used parameters: no gradient, no state
+            st = {} if rule == 'sgd' else {'step': torch.tensor(float(f.step_count)) if rule == 'adam' else int(f.step_count)}
+            for key, buf in _state_buffers(tr):
+                st[key] = _gather(tr, buf, n, p)
+            state[i] = st
+    ids = list(range(len(params)))
+    if rule == 'adam':
+        group = dict(lr=tr.lr, betas=tuple(tr.betas), eps=tr.eps, weight_decay=tr.wd, amsgrad=False, maximize=False, foreach=None,
+                     capturable=False, differentiable=False, fused=None, params=ids)
+    elif rule == 'sgd':
+        # torch's own group, whatever keys the installed torch writes
+        group = torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=tr.lr, momentum=tr.momentum,
+                                weight_decay=tr.wd).state_dict()['param_groups'][0]
+        group['params'] = ids
+    else:
+        group = dict(lr=tr.lr, betas=tuple(tr.betas), eps=tr.eps, weight_decay=tr.wd)
+        if rule == 'adamw':
+            group.update(use_variance=True, warmup=ADAMW_WARMUP)
+        if rule == 'ranger':
+            group.update(alpha=RANGER_ALPHA, k=RANGER_K, step_counter=0, N_sma_threshhold=RANGER_THRESHOLD)
+        group['params'] = ids
+    return {'state': state, 'param_groups': [group]}
+
+
+def _layout_of(sd):
+    """which optimiser family wrote `sd`: read off the keys only that family's object has"""
+    group = sd['param_groups'][0]
+    keys = set(group)
+    for st in sd['state'].values():
+        keys |= set(st)
+        break
+    if 'momentum_buffer' in keys or 'nesterov' in keys:
+        return 'sgd'
+    if 'slow_buffer' in keys or 'N_sma_threshhold' in keys:
+        return 'ranger'
+    if 'warmup' in keys:
+        return 'adamw'
+    if 'amsgrad' in keys:
+        return 'adam'
+    return 'radam' if 'betas' in keys else 'unknown'
+
+
+def load_state_dict(tr, sd):
+    """Takes the state of the reference's object for THIS optimiser (RAdam and RAdam_4step share one layout); a state written by
+    another optimiser raises instead of silently starting from zero moments.  The loaded group's lr, weight decay, betas, eps and
+    momentum become the trainer's.  torch.optim.SGD stores no step count and the rule only asks whether a momentum buffer exists yet
+    (buf = g on the very first step): a loaded SGD state with momentum buffers continues at step_count 1, one without them at 0."""
+    f = tr.flat
+    params = list(tr.model.named_parameters())
+    group = sd['param_groups'][0]
+    assert len(sd['param_groups']) == 1 and len(group['params']) == len(params), 'optimizer state of a different model'
+    rule = tr.optimizer
+    mine, theirs = ('radam' if rule == 'radam4s' else rule), _layout_of(sd)
+    if theirs != mine:
+        raise ValueError("optimizer state with the layout of '{}' cannot continue a '{}' run (param group keys: {})".format(
+            theirs, rule, ', '.join(sorted(k for k in group if k != 'params'))))
+    if rule == 'sgd':
+        tr.lr, tr.wd, tr.momentum = group['lr'], group['weight_decay'], group['momentum']
+    else:
+        tr.lr, tr.betas, tr.eps, tr.wd = group['lr'], tuple(group['betas']), group['eps'], group['weight_decay']
+    bufs = _state_buffers(tr)
+    for _, buf in bufs:
+        if buf is not f.S:
+            buf.zero_()
+    if f.S is not None:
+        f.S.copy_(f.P[:f.n_used])
+    steps = set()
+    for i, st in sd['state'].items():
+        n, p = params[int(i)]
+        assert f.offsets[n][0] < f.n_used, 'state for a parameter that is never stepped: ' + n
+        for key, buf in bufs:
+            if key not in st or st[key] is None:
+                raise ValueError("optimizer state of parameter {} lacks '{}': not a state of '{}'".format(n, key, rule))
+            _scatter(tr, buf, n, p, st[key])
+        steps.add(1 if rule == 'sgd' else int(st['step']))
+    assert len(steps) <= 1, 'per-parameter step counts differ: not a state of one optimiser over the whole model'
+    f.step_count = steps.pop() if steps else 0
+
+
 class LRSchedule:
     """One of the four torch schedulers utils.get_optimizer builds (utils.py:941-957), torch's own object over a one-parameter proxy
     optimiser.  `step` is the reference's once-per-epoch call (train.py:406-411): it returns the rate that goes into `trainer.lr`.
@@ -98,7 +314,6 @@ class LRSchedule:
     the checkpoint's rate, as the reference's fresh scheduler acts on the loaded param group."""
 
     def __init__(self, name, lr, step=5, lr_decay=0.995):
-        import torch
         assert name in SCHEDULERS, name
         self.name = name
         self._proxy = torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=lr)

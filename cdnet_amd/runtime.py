@@ -348,7 +348,7 @@ class FuseNode:
         assert (o.dtype == torch.float32) == f32
         if DEBUG_NORELU:
             relu = False
-        _lib.call('cdnet_fuse_sum_f32' if f32 else 'cdnet_fuse_sum', C.byref(arr), len(terms), N, H, W, Cc, int(relu), _lib.ptr(o), cs, out_coff,
+        _lib.call(_lib.entry('cdnet_fuse_sum', f32), C.byref(arr), len(terms), N, H, W, Cc, int(relu), _lib.ptr(o), cs, out_coff,
                   _lib.stream_ptr())
         if training:
             self.saved = (list(terms), o, relu, H, W, Cc, out_coff)
@@ -382,7 +382,7 @@ class FuseNode:
                 add(t.x, tr.G(d, H, W, coff=dco, cstride=dcs))
             else:
                 din = tr.buf(('dup', self.name, k), (N, t.Hs, t.Ws, Cc), d.dtype)
-                _lib.call('cdnet_upsample_bilinear_backward_f32' if d.dtype == torch.float32 else 'cdnet_upsample_bilinear_backward', _lib.ptr(d),
+                _lib.call(_lib.entry('cdnet_upsample_bilinear_backward', d.dtype == torch.float32), _lib.ptr(d),
                           N, H, W, Cc, dcs, dco, t.Hs, t.Ws, _lib.ptr(din), _lib.stream_ptr())
                 add(t.x, tr.G(din, t.Hs, t.Ws))
 
@@ -434,7 +434,7 @@ def input_pack(x):
     x = x.contiguous()
     N, Cc, H, W = x.shape
     out = torch.empty((N, H, W, 16), dtype=act_dtype(), device=x.device)
-    _lib.call('cdnet_input_pack_f32' if PRECISION == 'fp32' else 'cdnet_input_pack', _lib.ptr(x), N, Cc, H, W, _lib.ptr(out),
+    _lib.call(_lib.entry('cdnet_input_pack', PRECISION == 'fp32'), _lib.ptr(x), N, Cc, H, W, _lib.ptr(out),
               _lib.stream_ptr())
     return out
 

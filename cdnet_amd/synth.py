@@ -1,9 +1,10 @@
 """Deterministic synthetic inputs (SURVEY.md section 8d recipe) shared by bench.py, the tests and the golden
-generator.  Pure numpy (RandomState streams are stable across numpy versions); no reference code, no oracle.
+generator.  Computed in numpy (RandomState streams are stable across numpy versions); no reference code, no oracle.
 
   tiles             uint8 RGB i.i.d. uniform, RandomState(2022) (2022 = reference default seed, options.py:78)
   instance labels   random non-overlapping ellipses
   network outputs   one-hot(3-class label) smoothed + noise, Gaussian centre heat-map, centripetal class map
+  training batch    synthetic_batch: the tiles and training targets of the benchmark's step as torch tensors (the one torch import)
 """
 import math
 import zlib
@@ -272,6 +273,22 @@ def render_nuclei(inst, rs):
     return np.clip(img, 0.0, 1.0).astype(np.float32)
 
 
+def instance_targets(inst):
+    """training targets of one instance map: label u8 {0,1,2} (2 = the border an 8-neighbour erosion removes), centripetal direction
+    classes 0..8 inside the eroded instances, point map f16 (Gaussian-blurred centroids)"""
+    inside = inst > 0
+    ero = erode8(inside)
+    lab = np.zeros(inst.shape, np.uint8)
+    lab[ero] = 1
+    lab[inside & ~ero] = 2
+    d, cents = centroid_direction(inst)
+    d[~ero] = 0
+    pt = np.zeros(inst.shape, np.float64)
+    for cy, cx in cents:
+        pt[cy, cx] = 255.0
+    return lab, d, gaussian_blur(pt, 2.0).astype(np.float16)
+
+
 def nuclei_batch(B, H, W, seed, n=60, rmin=5, rmax=12):
     """B rendered tiles with their training targets: x f32 [B,3,H,W], label u8 {0,1,2}, direction u8 0..8, point f16,
     weight u8 (constant 20), instance maps i32."""
@@ -285,16 +302,23 @@ def nuclei_batch(B, H, W, seed, n=60, rmin=5, rmax=12):
         inst = ellipse_instances(H, W, n, rs, rmin, rmax, 10)
         insts[b] = inst
         x[b] = render_nuclei(inst, rs)
-        inside = inst > 0
-        ero = erode8(inside)
-        lab[b][ero] = 1
-        lab[b][inside & ~ero] = 2
-        d, cents = centroid_direction(inst)
-        d[~ero] = 0
-        dirn[b] = d
-        pt = np.zeros((H, W), np.float64)
-        for cy, cx in cents:
-            pt[cy, cx] = 255.0
-        point[b] = gaussian_blur(pt, 2.0).astype(np.float16)
+        lab[b], dirn[b], point[b] = instance_targets(inst)
     weight = np.full((B, H, W), 20, np.uint8)
     return x, lab, dirn, point, weight, insts
+
+
+def synthetic_batch(B, dev, seed=2022, H=256, W=256):
+    """SURVEY 8d recipe: uniform RGB tiles, ellipse instances -> 3-class label / centripetal classes / point map,
+    constant weight map 20."""
+    import torch
+    rs = np.random.RandomState(seed)
+    x = (rs.randint(0, 256, size=(B, 3, H, W)).astype(np.float32) / 255.0)
+    lab = np.zeros((B, H, W), np.uint8)
+    dirn = np.zeros((B, H, W), np.uint8)
+    point = np.zeros((B, H, W), np.float16)
+    for b in range(B):
+        inst = ellipse_instances(H, W, 60, rs, 5, 12, 10)
+        lab[b], dirn[b], point[b] = instance_targets(inst)
+    weight = np.full((B, H, W), 20, np.uint8)
+    t = lambda a: torch.from_numpy(a).to(dev)
+    return t(x), t(lab), t(dirn), t(point), t(weight)

@@ -20,7 +20,6 @@ import torch
 
 from . import checkpoint, synth, train_util_dam, utils
 from .options import Options
-from .trainer import synthetic_batch
 
 
 class _SyntheticLoader:
@@ -29,7 +28,7 @@ class _SyntheticLoader:
     def __init__(self, n_batches, batch, dev, seed):
         self.items = []
         for k in range(n_batches):
-            x, lab, dirn, point, weight = synthetic_batch(batch, dev, seed=seed + k)
+            x, lab, dirn, point, weight = synth.synthetic_batch(batch, dev, seed=seed + k)
             target0 = (lab.to(torch.int64) * 127 + (lab == 2).to(torch.int64)).unsqueeze(1)      # {0,127,255} as ToTensor emits
             self.items.append((x, weight.unsqueeze(1), target0, point, dirn))
 

@@ -1,14 +1,17 @@
 """Training step of the CDNet model on the HIP kernels: forward (batch-statistics BatchNorm), the five-term loss,
-backward, gradient all-reduce over RCCL, fused Adam - the device-side replacement of the body of the reference's
+backward, gradient all-reduce over RCCL, optimiser step - the device-side replacement of the body of the reference's
 train_util_dam.train (train_util_dam.py:54-311) with the host loops (:73-142, :278-289) moved onto the GPU.
 
-No autograd: the forward records a tape of the convolution layers it ran; backward walks the tape in reverse.  For every
-layer it (1) turns the consumers' gradients into the gradient of the raw convolution output (BatchNorm + residual + ReLU
-+ max-pool/pad routing fused, cdnet_bn_backward), (2) computes dW on the matrix cores (cdnet_conv_backward_weight) and
-(3) computes the input gradient as a forward convolution with a flipped/transposed weight pack (cdnet_conv_forward).
-Parameters, gradients and the Adam moments live in flat fp32 buffers (one fused Adam launch, one all-reduce bucket
-sequence); the nn.Parameters of the model are views into them.  `Trainer(optimizer=)` selects the reference's other optimisers
-(utils.py:907-939: SGD, RAdam, RAdam_4step, AdamW, Ranger - csrc/optim.hip, cdnet_amd/optim.py) over the same buffers.
+This module is the tape walk.  No autograd: the forward records a tape of the convolution layers it ran; backward walks the
+tape in reverse.  For every layer it (1) turns the consumers' gradients into the gradient of the raw convolution output
+(BatchNorm + residual + ReLU + max-pool/pad routing fused, cdnet_bn_backward), (2) computes dW on the matrix cores
+(cdnet_conv_backward_weight, on a second stream, its split-K sums deferred and batched) and (3) computes the input gradient
+as a forward convolution with a flipped/transposed weight pack (cdnet_conv_forward); it tells the all-reduce which
+parameters' gradients are final, and re-packs the weights behind the optimiser step.
+
+What the step works on lives elsewhere: the flat fp32 buffers the nn.Parameters are views into, the step of the six
+optimisers over them and the optimiser entry of a checkpoint in cdnet_amd.optim (`Trainer(optimizer=)` selects the rule;
+`Trainer` holds the hyperparameters), the bucketed gradient all-reduce in cdnet_amd.allreduce.
 """
 import ctypes as C
 import os
@@ -16,10 +19,10 @@ import os
 import torch
 
 from . import _lib, engine, optim, runtime, streams
+from .allreduce import BucketReducer, bucketed_allreduce
 from .engine import Src
-
-HEAD_PARAMS = ['point_conv.weight', 'direction_conv.weight', 'mask_conv.weight', 'point_conv.bias',
-               'direction_conv.bias', 'mask_conv.bias', 'directionAtt.Conv1x1.weight', 'maskAtt.Conv1x1.weight']
+from .optim import HEAD_PARAMS, FlatState                    # noqa: F401 (HEAD_PARAMS: the tests import it from here)
+from .synth import synthetic_batch
 
 
 class GradIn(C.Structure):
@@ -33,7 +36,7 @@ class BnBwdArgs(C.Structure):
                 ('f16', C.c_int), ('relu', C.c_int), ('N', C.c_int), ('H', C.c_int), ('W', C.c_int), ('C', C.c_int)]
 
 
-# workgroups of one weight-gradient launch while it runs beside the input-gradient chain (bf16 mode; see _weight_backward):
+# workgroups of one weight-gradient launch while it runs beside the input-gradient chain (bf16 mode; see _wgrad_wgs):
 # layers of up to 128 x 128 pixels / larger ones
 _WGRAD_WGS_DEEP, _WGRAD_WGS_SHALLOW = 128, 160
 _WGRAD_WGS_KQ = 128                        # wgrad_ws_kernel<1, 1> on 512 x 512 layers (HRNet's branch 1)
@@ -70,47 +73,6 @@ class _G:
         self.event = None                    # produced on another stream: the consumer's stream waits for this event first
 
 
-class FlatState:
-    """fp32 flat buffers: parameters, gradients, Adam moments.  Head parameters first (in the kernel's block layout),
-    then every other parameter that takes part in forward, then the reference's never-used parameters (no gradient,
-    never stepped - torch.optim.Adam skips parameters whose .grad is None).
-    The state buffers follow the optimiser: M is the first moment (SGD: the momentum buffer), V the second moment (none for SGD),
-    S Ranger's slow weights over the stepped parameters (none otherwise)."""
-
-    def __init__(self, model, optimizer='adam'):
-        # a model that computes on zero-padded parameter copies (HRNet) hands those over; its own parameters stay views
-        named = model.trainer_named_parameters() if hasattr(model, 'trainer_named_parameters') else dict(model.named_parameters())
-        unused = [n for n in named if n.startswith(tuple(getattr(model, 'UNUSED_PREFIXES', ())))]
-        head = [n for n in HEAD_PARAMS if n in named and n not in unused]
-        rest = [n for n in named if n not in head and n not in unused]
-        self.order = head + rest + unused
-        sizes = [named[n].numel() for n in self.order]
-        total = sum(sizes)
-        dev = next(model.parameters()).device
-        self.P = torch.empty((total,), dtype=torch.float32, device=dev)
-        self.G = torch.zeros((total,), dtype=torch.float32, device=dev)
-        self.M = torch.zeros((total,), dtype=torch.float32, device=dev)
-        self.V = None if optimizer == 'sgd' else torch.zeros((total,), dtype=torch.float32, device=dev)
-        self.S = None
-        self.offsets = {}
-        off = 0
-        with torch.no_grad():
-            for n, sz in zip(self.order, sizes):
-                p = named[n]
-                self.P[off:off + sz].copy_(p.detach().reshape(-1))         # one-time host-side setup
-                p.data = self.P[off:off + sz].view(p.shape)
-                p.grad = self.G[off:off + sz].view(p.shape)
-                self.offsets[n] = (off, sz)
-                off += sz
-        if hasattr(model, 'rebind_views'):
-            model.rebind_views()
-        self.n_used = sum(named[n].numel() for n in head + rest)
-        self.n_head = sum(named[n].numel() for n in head)
-        if optimizer == 'ranger':
-            self.S = self.P[:self.n_used].clone()            # (taken again when the first step starts, ranger.py:113-114)
-        self.step_count = 0
-
-
 def _choose_ci_tiles(C_src, Cout):
     if Cout <= 32 and runtime.PRECISION != 'fp32':
         return 1            # 16-bit path: 32-input-channel blocks; with at most 32 output channels the library runs ONE 32 x 32 block per
@@ -122,6 +84,21 @@ def _choose_ci_tiles(C_src, Cout):
         if best_cost is None or cost < best_cost:
             best, best_cost = ci_t, cost
     return best
+
+
+def _wgrad_wgs(beside, HW, Cout):
+    """most workgroups of one weight-gradient launch over a layer of HW pixels; beside: it runs beside the input-gradient chain"""
+    # beside the input-gradient chain the weight-gradient kernels take fewer workgroups than there are CUs: a full grid of
+    # them holds every CU's LDS, and the chain's producer / consumer convolutions (one 157 KB workgroup per CU) then queue
+    # behind it - measured 1 663 -> 1 745 / 1 730 -> 1 813 tiles/s (two boxes).  fp32 mode: 160 workgroups since the
+    # end of round 3 (+0.7 %; with round 2's kernels the caps cost 1.7 %).
+    if not beside:
+        return 256                                      # (the first layer's weight gradient runs after the chain has ended: whole chip)
+    if runtime.PRECISION == 'fp32':
+        return _WGRAD_WGS_F32
+    if Cout <= 32 and HW > 65536:
+        return _WGRAD_WGS_KQ
+    return _WGRAD_WGS_DEEP if HW <= _WGRAD_DEEP_HW or HW > 65536 else _WGRAD_WGS_SHALLOW    # (512 x 512 layers of HRNet: 128 again)
 
 
 class GradTerm(C.Structure):
@@ -137,6 +114,7 @@ class Trainer:
         eps None = the rule's own default (1e-5 for Ranger, ranger.py:28; 1e-8 otherwise)"""
         self.model = model
         self._pack_jobs = None
+        self._pack_prec = None
         self._ar = None
         self.optimizer = str(optimizer).lower()
         if self.optimizer not in optim.OPTIMIZERS:
@@ -151,10 +129,7 @@ class Trainer:
         model._head_flat = self.flat.P[:self.flat.n_head] if self.flat.n_head == 855 else None
         self.dev = self.flat.P.device
         self._bufs = {}
-        self._ws_bn = None
-        self._ws_slab = None
-        self._ws_head = None
-        self._ws_loss = None
+        self._wss = {}
         self.losses = torch.zeros((11,), dtype=torch.float32, device=self.dev)     # 6 loss values + 5 pixel metrics
         self.tape = []
         self._cat_cache = {}
@@ -220,11 +195,14 @@ class Trainer:
             self._bufs[key] = b
         return b
 
-    def _bn_ws(self, Cc):
-        need = _lib.load().cdnet_bn_backward_workspace_floats(Cc)
-        if self._ws_bn is None or self._ws_bn.numel() < need:
-            self._ws_bn = torch.empty((need,), dtype=torch.float32, device=self.dev)
-        return self._ws_bn
+    def _ws(self, name, need, side=False):
+        """grow-only fp32 workspace `name` of at least `need` floats; side: the weight-gradient stream uses it too"""
+        ws = self._wss.get(name)
+        if ws is None or ws.numel() < need:
+            if side and self._wstream is not None:
+                self._wstream.synchronize()          # the old workspace may still be in use on the weight-gradient stream
+            ws = self._wss[name] = torch.empty((need,), dtype=torch.float32, device=self.dev)
+        return ws
 
     def grad_sum(self, gl, mask, npix, Cc, out):
         """out = [mask > 0] * sum of the gradient contributions `gl` (cdnet_grad_sum)"""
@@ -233,8 +211,8 @@ class Trainer:
         for k, g in enumerate(gl):
             assert not g.pooled and g.oy == 0 and g.ox == 0
             arr[k].g, arr[k].cstride, arr[k].coff = g.t.data_ptr(), g.cstride or Cc, g.coff
-        entry = 'cdnet_grad_sum_f32' if out.dtype == torch.float32 else 'cdnet_grad_sum'
-        _lib.call(entry, C.byref(arr), len(gl), None if mask is None else _lib.ptr(mask), npix, Cc, _lib.ptr(out), _lib.stream_ptr())
+        _lib.call(_lib.entry('cdnet_grad_sum', out.dtype == torch.float32), C.byref(arr), len(gl), None if mask is None else _lib.ptr(mask),
+                  npix, Cc, _lib.ptr(out), _lib.stream_ptr())
 
     def take(self, grads, key):
         """pop the gradient contributions of a stored tensor for a consumer on the CURRENT stream: a contribution computed beside the chain
@@ -263,13 +241,6 @@ class Trainer:
             self._cat_cache[key] = d
         return self._cat_cache[key]
 
-    def _slab(self, n):
-        if self._ws_slab is None or self._ws_slab.numel() < n:
-            if self._wstream is not None:
-                self._wstream.synchronize()          # the old workspace may still be in use on the weight-gradient stream
-            self._ws_slab = torch.empty((n,), dtype=torch.float32, device=self.dev)
-        return self._ws_slab
-
     # ------------------------------------------------------------------------------------------------
     def forward(self, x):
         m = self.model
@@ -287,9 +258,7 @@ class Trainer:
         B, _, H, W = mask.shape
         lib = _lib.load()
         ND = direction.shape[1]                       # 5 / 9 / 17 direction classes (options.py:45)
-        need = lib.cdnet_dam_loss_classes_workspace_floats(B, H * W, ND)
-        if self._ws_loss is None or self._ws_loss.numel() < need:
-            self._ws_loss = torch.empty((need,), dtype=torch.float32, device=self.dev)
+        ws = self._ws('loss', lib.cdnet_dam_loss_classes_workspace_floats(B, H * W, ND))
         dmask = self.buf('dmask', mask.shape, torch.float32)
         dpoint = self.buf('dpoint', point.shape, torch.float32)
         ddir = self.buf('ddir', direction.shape, torch.float32)
@@ -297,7 +266,7 @@ class Trainer:
         assert point_t.dtype == torch.float16
         _lib.call('cdnet_dam_loss_classes', _lib.ptr(mask), _lib.ptr(point), _lib.ptr(direction), _lib.ptr(label.contiguous()),
                   _lib.ptr(dirlab.contiguous()), _lib.ptr(point_t.contiguous()), _lib.ptr(weight.contiguous()), B, H, W, ND,
-                  self.quirk, _lib.ptr(self._ws_loss), self._ws_loss.numel(), _lib.ptr(self.losses), _lib.ptr(dmask),
+                  self.quirk, _lib.ptr(ws), ws.numel(), _lib.ptr(self.losses), _lib.ptr(dmask),
                   _lib.ptr(dpoint), _lib.ptr(ddir), _lib.stream_ptr())
         return dmask, dpoint, ddir
 
@@ -306,25 +275,39 @@ class Trainer:
         m = self.model
         f1, f2, f3 = m._last_feats
         N, H, W, _ = f1.x.shape
+        df = [self.buf('dF%d' % k, (N, H, W, 64), runtime.act_dtype()) for k in range(3)]
+        hf = [runtime.head_feat(f) for f in (f1, f2, f3)]
+        dhead = self.flat.G[:self.flat.n_head]
+        ws = self._ws('head', _lib.load().cdnet_dam_head_backward_workspace_floats(N, H, W))
+        _lib.call('cdnet_dam_head_backward', C.byref(hf[0]), C.byref(hf[1]), C.byref(hf[2]), _lib.ptr(m.head_weight_block()),
+                  _lib.ptr(dmask), _lib.ptr(dpoint), _lib.ptr(ddir), N, H, W, _lib.ptr(df[0]), _lib.ptr(df[1]),
+                  _lib.ptr(df[2]), _lib.ptr(ws), ws.numel(), _lib.ptr(dhead), _lib.stream_ptr())
+        self._run_tape([(getattr(f, 'grad_to', (f.x,))[0], _G(d, H, W)) for f, d in zip((f1, f2, f3), df)], None)
+
+    def _classifier_backward(self, key, f, conv, dl):
+        """backward of a plain 1x1 classifier `conv` on the 64-channel feature `f` (cdnet_final_conv1x1_backward): fills the gradients of
+        its weight and bias; returns the gradient of the feature as a _G"""
+        N, H, W, _ = f.x.shape
+        K = conv.out_channels
+        df = self.buf(key, (N, H, W, 64), runtime.act_dtype())
+        ws = self._ws('slab', _lib.load().cdnet_final_conv1x1_backward_workspace_floats(), side=True)
+        hf = runtime.head_feat(f)
+        w = conv.weight.detach().reshape(K, 64)
+        _lib.call('cdnet_final_conv1x1_backward', C.byref(hf), _lib.ptr(w), _lib.ptr(dl), K, N, H, W, _lib.ptr(df), _lib.ptr(ws),
+                  ws.numel(), _lib.ptr(conv.weight.grad), _lib.ptr(conv.bias.grad), _lib.stream_ptr())
+        return _G(df, H, W)
+
+    def _run_tape(self, heads, params):
+        """the rest of backward from the head gradients `heads` [(stored tensor, _G)]; `params`: the head's parameters, whose gradients
+        are final by now (None: the head block of the flat buffer)"""
         grads = {}                      # id(stored tensor) -> [_G]
 
         def add(t, g):
             grads.setdefault(id(t), []).append(g)
-
-        # head
-        df = [self.buf('dF%d' % k, (N, H, W, 64), runtime.act_dtype()) for k in range(3)]
-        hf = [runtime.head_feat(f) for f in (f1, f2, f3)]
-        dhead = self.flat.G[:self.flat.n_head]
-        need = _lib.load().cdnet_dam_head_backward_workspace_floats(N, H, W)
-        if self._ws_head is None or self._ws_head.numel() < need:
-            self._ws_head = torch.empty((need,), dtype=torch.float32, device=self.dev)
-        _lib.call('cdnet_dam_head_backward', C.byref(hf[0]), C.byref(hf[1]), C.byref(hf[2]), _lib.ptr(m.head_weight_block()),
-                  _lib.ptr(dmask), _lib.ptr(dpoint), _lib.ptr(ddir), N, H, W, _lib.ptr(df[0]), _lib.ptr(df[1]),
-                  _lib.ptr(df[2]), _lib.ptr(self._ws_head), self._ws_head.numel(), _lib.ptr(dhead), _lib.stream_ptr())
-        for f, d in zip((f1, f2, f3), df):
-            add(getattr(f, 'grad_to', (f.x,))[0], _G(d, H, W))
+        for t, g in heads:
+            add(t, g)
         self._overlap_begin()
-        self._overlap_done(None)
+        self._overlap_done(params)
         self._backward_tape(grads, add)
 
     def _backward_tape(self, grads, add):
@@ -413,11 +396,8 @@ class Trainer:
         self._rd_pending, self._rd_params, self._rd_bytes = [], [], 0
 
     def _layer_backward(self, k, L, gl, grads, add, side):
-        """one convolution layer: BatchNorm / residual / ReLU backward of its output, weight gradient (side stream), input gradient"""
-        for g_ in gl:
-            if g_.event is not None:         # a contribution computed beside the chain (_RU_1X1_SIDE)
-                torch.cuda.current_stream().wait_event(g_.event)
-                g_.event = None
+        """one convolution layer: BatchNorm / residual / ReLU backward of its output, weight gradient (side stream), input gradient.
+        `gl` comes from take() on this stream: the events of contributions computed beside the chain are already waited for"""
         srcs, out, Hl, Wl = L.saved
         No, Ho, Wo, Co = out.shape
         params = (L.weight, L.bias, None if L.bn is None else L.bn.weight, None if L.bn is None else L.bn.bias)
@@ -428,8 +408,6 @@ class Trainer:
             a, ktab = self._bn_backward_stats(L, out, gl[0], partial=part)
             g = self.buf(('draw', L.name), (No, Ho, Wo, Co), runtime.act_dtype())
             _lib.call('cdnet_bn_backward_apply', C.byref(a), _lib.ptr(ktab), _lib.ptr(g), _lib.stream_ptr())
-        if part is not None:
-            pass
         elif L.bn is not None or len(gl) > 1 or gl[0].pooled or gl[0].coff or (gl[0].cstride not in (0, Co)):
             g = self._bn_backward(L, out, gl, add)
         else:
@@ -466,20 +444,8 @@ class Trainer:
     def _bn_backward_stats(self, L, out, g, partial):
         """finalize pass over the partial channel sums a backward-data launch left (cdnet_conv_args.ws = 2, fp32 mode): dgamma, dbeta and
         the [7][C] table the second pass reads"""
-        a = BnBwdArgs()
-        No, Ho, Wo, Co = out.shape
-        a.raw = out.data_ptr()
-        a.res = None
-        a.scale, a.shift = L.scale.data_ptr(), L.shift.data_ptr()
-        a.mean, a.invstd = L.save_mean.data_ptr(), L.save_invstd.data_ptr()
-        a.ngin = 1
-        a.gin[0].g = g.t.data_ptr()
-        a.gin[0].Hg, a.gin[0].Wg, a.gin[0].oy, a.gin[0].ox = g.Hg, g.Wg, 0, 0
-        a.gin[0].pooled, a.gin[0].coff, a.gin[0].cstride = 0, 0, Co
-        a.f16 = {torch.bfloat16: 0, torch.float16: 1, torch.float32: 2}[out.dtype]
-        a.relu = 1
-        a.N, a.H, a.W, a.C = No, Ho, Wo, Co
-        ktab = self.buf(('ktab', L.name), (7, Co), torch.float32)
+        a = self._bn_args(L, out, [_G(g.t, g.Hg, g.Wg)], res=None, relu=1)          # (one plain source, BatchNorm + ReLU, no residual)
+        ktab = self.buf(('ktab', L.name), (7, out.shape[3]), torch.float32)
         bn = L.bn
         _lib.call('cdnet_bn_backward_finalize', C.byref(a), _lib.ptr(bn.weight.detach()), _lib.ptr(bn.weight.grad), _lib.ptr(bn.bias.grad),
                   _lib.ptr(partial), partial.shape[0], _lib.ptr(ktab), _lib.stream_ptr())
@@ -519,17 +485,30 @@ class Trainer:
             return None
         return P, hit
 
-    def _bn_backward(self, L, out, gl, add):
+    def _bn_args(self, L, out, gl, res, relu):
+        """cdnet_bn_bwd_args of layer L's stored output `out`: its gradient sources `gl` (at most 3), the residual branch `res`, the
+        ReLU mode"""
         a = BnBwdArgs()
-        No, Ho, Wo, Co = out.shape
         a.raw = out.data_ptr()
-        res = getattr(L, 'node_res', None)
         a.res = None if res is None else res.data_ptr()
+        if L.bn is not None:
+            a.scale, a.shift = L.scale.data_ptr(), L.shift.data_ptr()
+            a.mean, a.invstd = L.save_mean.data_ptr(), L.save_invstd.data_ptr()
+        a.ngin = len(gl)
+        assert 1 <= len(gl) <= 3, (L.name, len(gl))
+        for k, g in enumerate(gl):
+            a.gin[k].g = g.t.data_ptr()
+            a.gin[k].Hg, a.gin[k].Wg, a.gin[k].oy, a.gin[k].ox = g.Hg, g.Wg, g.oy, g.ox
+            a.gin[k].pooled, a.gin[k].coff, a.gin[k].cstride = int(g.pooled), g.coff, g.cstride or out.shape[3]
+        a.f16 = {torch.bfloat16: 0, torch.float16: 1, torch.float32: 2}[out.dtype]
+        a.relu = relu
+        a.N, a.H, a.W, a.C = out.shape
+        return a
+
+    def _bn_backward(self, L, out, gl, add):
+        No, Ho, Wo, Co = out.shape
+        res = getattr(L, 'node_res', None)
         has_bn = L.bn is not None
-        a.scale = L.scale.data_ptr() if has_bn else None
-        a.shift = L.shift.data_ptr() if has_bn else None
-        a.mean = L.save_mean.data_ptr() if has_bn else None
-        a.invstd = L.save_invstd.data_ptr() if has_bn else None
         if len(gl) > 3:
             # more consumers than the kernel takes gradient sources (an ablation head's first residual unit feeds two units, four
             # backward-data terms): fold the plain same-size terms beyond the second into one tensor first
@@ -539,20 +518,12 @@ class Trainer:
             d = self.buf(('gsum', L.name), (No, Ho, Wo, Co), runtime.act_dtype())
             self.grad_sum(plain, None, No * Ho * Wo, Co, d)
             gl = rest + [_G(d, Ho, Wo)]
-        a.ngin = len(gl)
-        assert 1 <= len(gl) <= 3, (L.name, len(gl))
-        for k, g in enumerate(gl):
-            a.gin[k].g = g.t.data_ptr()
-            a.gin[k].Hg, a.gin[k].Wg, a.gin[k].oy, a.gin[k].ox = g.Hg, g.Wg, g.oy, g.ox
-            a.gin[k].pooled, a.gin[k].coff, a.gin[k].cstride = int(g.pooled), g.coff, g.cstride or Co
-        a.f16 = {torch.bfloat16: 0, torch.float16: 1, torch.float32: 2}[out.dtype]
-        a.relu = int(getattr(L, 'node_relu', True))
-        a.N, a.H, a.W, a.C = No, Ho, Wo, Co
+        a = self._bn_args(L, out, gl, res, int(getattr(L, 'node_relu', True)))
         draw = self.buf(('draw', L.name), (No, Ho, Wo, Co), runtime.act_dtype())
         dz = None
         if res is not None:
             dz = self.buf(('dz', L.name), (No, Ho, Wo, Co), runtime.act_dtype())
-        ws = self._bn_ws(Co)
+        ws = self._ws('bn', _lib.load().cdnet_bn_backward_workspace_floats(Co))
         bn = L.bn
         _lib.call('cdnet_bn_backward', C.byref(a), _lib.ptr(bn.weight.detach()) if has_bn else None,
                   _lib.ptr(bn.weight.grad) if has_bn else None, _lib.ptr(bn.bias.grad) if has_bn else None,
@@ -587,28 +558,17 @@ class Trainer:
         cin_real = L.Cin
         mode = {'conv3': 0, 'conv1': 0, 'convT4': 2, 'convT2': 3, 'conv3s2': 6}[L.kind]
         taps, npar, ostride = L.taps, (4 if L.transposed else 1), (2 if L.transposed else 1)
+        cap = _wgrad_wgs(self._side_active and getattr(L, 'needs_input_grad', True), H * W, Cout)
         coff = 0
         for s in srcs:
             ci_t = _choose_ci_tiles(s.C, Cout)
             CI, CO = ci_t * 32, (4 // ci_t) * 32
             other = -(-s.C // CI) * -(-Cout // CO) * npar
             ntiles = N * (-(-H // 8)) * (-(-W // 16))
-            # beside the input-gradient chain the weight-gradient kernels take fewer workgroups than there are CUs: a full grid of
-            # them holds every CU's LDS, and the chain's producer / consumer convolutions (one 157 KB workgroup per CU) then queue
-            # behind it - measured 1 663 -> 1 745 / 1 730 -> 1 813 tiles/s (two boxes).  fp32 mode: 160 workgroups since the
-            # end of round 3 (+0.7 %; with round 2's kernels the caps cost 1.7 %).
-            if not self._side_active or not getattr(L, 'needs_input_grad', True):
-                cap = 256                                   # (the first layer's weight gradient runs after the chain has ended: whole chip)
-            elif runtime.PRECISION == 'fp32':
-                cap = _WGRAD_WGS_F32
-            else:
-                cap = _WGRAD_WGS_DEEP if H * W <= _WGRAD_DEEP_HW or H * W > 65536 else _WGRAD_WGS_SHALLOW    # (512 x 512 layers of HRNet: 128 again)
-                if Cout <= 32 and H * W > 65536:
-                    cap = _WGRAD_WGS_KQ
             ksplit = max(1, min(ntiles, cap // other if other < cap else 1))      # one 8-wave workgroup per CU
             nslab = lib.cdnet_conv_wgrad_slab_floats(s.C, Cout, taps, npar, ci_t, ksplit)
             defer = self._rd_mb > 0
-            slab = self.buf(('wslab', L.name, coff), (nslab,), torch.float32) if defer else self._slab(nslab)
+            slab = self.buf(('wslab', L.name, coff), (nslab,), torch.float32) if defer else self._ws('slab', nslab, side=True)
             cs = engine.ConvSrc()
             s.fill(cs)
             csrc_real = min(s.C, cin_real - coff) if cin_total != cin_real else s.C
@@ -627,9 +587,8 @@ class Trainer:
                 L.bias.grad.copy_(owner.bn.bias.grad)
             else:
                 # stand-alone biased convolution (plain UNet's ConvTranspose2d): db = sum of the output gradient
-                need = lib.cdnet_bias_grad_workspace_floats(Cout)
-                ws = self._slab(need)
-                _lib.call('cdnet_bias_grad_f32' if g.dtype == torch.float32 else 'cdnet_bias_grad', _lib.ptr(g), g.numel() // Cout, Cout,
+                ws = self._ws('slab', lib.cdnet_bias_grad_workspace_floats(Cout), side=True)
+                _lib.call(_lib.entry('cdnet_bias_grad', g.dtype == torch.float32), _lib.ptr(g), g.numel() // Cout, Cout,
                           _lib.ptr(ws), ws.numel(), _lib.ptr(L.bias.grad), _lib.stream_ptr())
 
     def _input_backward(self, L, srcs, g, H, W, add):
@@ -647,7 +606,7 @@ class Trainer:
             gs2d = self.buf(('ds2d', L.name), (N, H, W, cin_total), runtime.act_dtype())
             engine.conv_forward([Src(g)], wpb, cin_total, cfgb, taps=9, out=gs2d, H=H, W=W)
             gin = self.buf(('din', L.name), (N, 2 * H, 2 * W, Cp), runtime.act_dtype())
-            _lib.call('cdnet_s2d_to_nhwc_f32' if gin.dtype == torch.float32 else 'cdnet_s2d_to_nhwc', _lib.ptr(gs2d), N, H, W, Cp, _lib.ptr(gin),
+            _lib.call(_lib.entry('cdnet_s2d_to_nhwc', gin.dtype == torch.float32), _lib.ptr(gs2d), N, H, W, Cp, _lib.ptr(gin),
                       _lib.stream_ptr())
             add(srcs[0].x, _G(gin, 2 * H, 2 * W))
             return
@@ -715,9 +674,9 @@ class Trainer:
     def allreduce_and_step(self):
         f = self.flat
         gscale = 1.0
-        ranges = [(0, f.n_used)]
+        works = None
         if self._reduce_active():
-            if getattr(self, '_ar', None) is not None:
+            if self._ar is not None:
                 # whatever backward did not release yet; then the optimiser follows the collectives bucket by bucket (top-down, the
                 # order they were launched in): the last bucket's all-reduce - the first layers' gradients, complete only when backward
                 # ends - runs while Adam already updates the ranges above it
@@ -727,54 +686,22 @@ class Trainer:
                 self._ar = None
             else:
                 bucketed_allreduce(f.G, f.n_used, self.bucket)
-                works = None
             gscale = 1.0 / self.world
-        else:
-            works = None
         f.step_count += 1
-
-        def adam(a, b):
-            sl = slice(a, b)
-            _lib.call('cdnet_adam_step', _lib.ptr(f.P[sl]), _lib.ptr(f.G[sl]), _lib.ptr(f.M[sl]), _lib.ptr(f.V[sl]), b - a, self.lr,
-                      self.betas[0], self.betas[1], self.eps, self.wd, f.step_count, gscale, _lib.stream_ptr())
-        if self.optimizer != 'adam':
-            adam = self._rule_stepper(gscale)
+        step = self._rule_stepper(gscale)
         if works is None:
-            adam(0, f.n_used)
+            step(0, f.n_used)
         else:
             for w, (a, b) in zip(works, ranges):
                 w.wait()                                 # (the current stream waits, not the host)
-                adam(a, b)
+                step(a, b)
         runtime.WEIGHTS_EPOCH[0] += 1
         self._repack_all()
 
     def _rule_stepper(self, gscale):
-        """step(a, b) of the optimisers besides Adam over the range [a, b) of the flat buffers (cdnet_moment_step / cdnet_sgd_step,
-        csrc/optim.hip); the step's host scalars are computed once (optim.moment_scalars).  Buffers on the CPU take the host
-        restatement of the same two kernels."""
-        f, rule, t = self.flat, self.optimizer, self.flat.step_count
-        on_host = self.dev.type == 'cpu'
-        if rule == 'sgd':
-            def step(a, b):
-                if on_host:
-                    optim.sgd_step_host(f.P[a:b], f.G[a:b], f.M[a:b], t, self.lr, self.momentum, self.wd, gscale)
-                else:
-                    _lib.call('cdnet_sgd_step', _lib.ptr(f.P[a:b]), _lib.ptr(f.G[a:b]), _lib.ptr(f.M[a:b]), b - a, self.lr, self.momentum,
-                              self.wd, t, gscale, _lib.stream_ptr())
-            return step
-        s = optim.moment_scalars(rule, t, self.lr, self.wd, self.betas, self.eps)
-        if rule == 'ranger' and t == 1:
-            f.S.copy_(f.P[:f.n_used])                    # the slow weights start as the parameters of the first step
-
-        def step(a, b):
-            slow = f.S[a:b] if s['sync'] else None
-            if on_host:
-                optim.moment_step_host(f.P[a:b], f.G[a:b], f.M[a:b], f.V[a:b], slow, s, self.betas, gscale)
-            else:
-                _lib.call('cdnet_moment_step', _lib.ptr(f.P[a:b]), _lib.ptr(f.G[a:b]), _lib.ptr(f.M[a:b]), _lib.ptr(f.V[a:b]), _lib.ptr(slow),
-                          b - a, self.betas[0], self.betas[1], gscale, s['move'], s['rect'], s['decay'], s['step_size'], s['v_div'], s['eps'],
-                          s['sync'], s['alpha'], _lib.stream_ptr())
-        return step
+        """step(a, b) of this trainer's optimiser over the range [a, b) of the flat buffers.  The rules live in optim.stepper; this name
+        stays because tests/test_gpu_optim.py steps bucket ranges through it - nothing else belongs here"""
+        return optim.stepper(self, gscale)
 
     def _repack_all(self):
         """Re-pack every layer's forward / backward-data weights in one launch (they would otherwise be re-packed one by
@@ -782,7 +709,7 @@ class Trainer:
         has its packed buffers."""
         f = self.flat
         lo, hi = f.P.data_ptr(), f.P.data_ptr() + f.P.numel() * 4
-        if self._pack_jobs is not None and getattr(self, '_pack_prec', None) != runtime.PRECISION:
+        if self._pack_jobs is not None and self._pack_prec != runtime.PRECISION:
             self._pack_jobs = None                           # the layers re-made their packs for the other precision
         if self._pack_jobs is None:
             groups = ([], []), ([], [])                      # (jobs, owners) of the forward packs / the backward-data packs
@@ -822,22 +749,6 @@ class Trainer:
                 setattr(L, attr, (L.weight._version, runtime.WEIGHTS_EPOCH[0]))
 
     # ------------------------------------------------------------------------------------------------
-    # Optimiser state in torch.optim.Adam's state_dict format (what the reference stores under checkpoint['optimizer'],
-    # train.py:421-427, and reads back at :302): parameter indices follow model.parameters(); parameters that never received
-    # a gradient have no entry (Adam creates state lazily).
-    def _real_pieces(self, buf, name, p):
-        """[(index into the real parameter, view of `buf`)] covering parameter `name` (the model's own shape), whether the flat
-        storage holds it as is, zero-padded (leading corner) or scattered over channel segments (HRNet)"""
-        off, sz = self.flat.offsets[name]
-        slots = {id(real): (pp, segs) for real, pp, segs in getattr(self.model, '_slots', [])}
-        if id(p) not in slots:
-            return [(Ellipsis, buf[off:off + sz].view(p.shape))]
-        pp, segs = slots[id(p)]
-        full = buf[off:off + sz].view(pp.shape)
-        if segs is None:
-            return [(Ellipsis, full[tuple(slice(0, n) for n in p.shape)])]
-        return [((slice(None), slice(r0, r0 + n)), full[:, p0:p0 + n]) for r0, n, p0 in segs]
-
     def write_bn_counters(self):
         """nn.BatchNorm2d.num_batches_tracked of every BatchNorm that ran = the number of training forwards (PyTorch adds one per
         forward, `nn.BatchNorm2d.forward`); kept as a host counter during training and written out for checkpoints"""
@@ -854,114 +765,14 @@ class Trainer:
             self.model._ensure_runtime()
         runtime.WEIGHTS_EPOCH[0] += 1
 
-    def _gather(self, buf, n, p):
-        """CPU copy, in the model's own shape, of parameter `n`'s part of the flat state buffer `buf`"""
-        t = torch.empty(p.shape, dtype=torch.float32)
-        for idx, piece in self._real_pieces(buf, n, p):
-            t[idx] = piece.cpu()
-        return t
-
-    def _scatter(self, buf, n, p, value):
-        for idx, piece in self._real_pieces(buf, n, p):
-            piece.copy_(value[idx])
-
-    # state buffers of one parameter under the reference classes' own key names (torch.optim.SGD, hhl_utils/radam.py, ranger.py)
-    def _state_buffers(self):
-        f = self.flat
-        if self.optimizer == 'sgd':
-            return [('momentum_buffer', f.M)]
-        return [('exp_avg', f.M), ('exp_avg_sq', f.V)] + ([('slow_buffer', f.S)] if self.optimizer == 'ranger' else [])
-
     def state_dict(self):
-        """the optimiser entry of a checkpoint in the layout of the reference's object for this optimiser: torch.optim.Adam / SGD,
-        RAdam, RAdam_4step, AdamW (hhl_utils/radam.py) or Ranger (hhl_utils/ranger.py).  'step' is a tensor for Adam (torch's own
-        format) and an int for the reference's classes; torch's SGD keeps no step (see load_state_dict)."""
-        f = self.flat
-        params = list(self.model.named_parameters())
-        state = {}
-        rule = self.optimizer
-        if f.step_count > 0:
-            for i, (n, p) in enumerate(params):
-                if f.offsets[n][0] >= f.n_used:
-                    continue                                        # the reference's never-used parameters: no gradient, no state
-                if rule == 'adam':
-                    state[i] = {'step': torch.tensor(float(f.step_count)), 'exp_avg': self._gather(f.M, n, p), 'exp_avg_sq': self._gather(f.V, n, p)}
-                    continue
-                st = {} if rule == 'sgd' else {'step': int(f.step_count)}
-                for key, buf in self._state_buffers():
-                    st[key] = self._gather(buf, n, p)
-                state[i] = st
-        ids = list(range(len(params)))
-        if rule == 'adam':
-            group = dict(lr=self.lr, betas=tuple(self.betas), eps=self.eps, weight_decay=self.wd, amsgrad=False, maximize=False, foreach=None,
-                         capturable=False, differentiable=False, fused=None, params=ids)
-        elif rule == 'sgd':
-            # torch's own group, whatever keys the installed torch writes
-            group = torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=self.lr, momentum=self.momentum,
-                                    weight_decay=self.wd).state_dict()['param_groups'][0]
-            group['params'] = ids
-        else:
-            group = dict(lr=self.lr, betas=tuple(self.betas), eps=self.eps, weight_decay=self.wd)
-            if rule == 'adamw':
-                group.update(use_variance=True, warmup=optim.ADAMW_WARMUP)
-            if rule == 'ranger':
-                group.update(alpha=optim.RANGER_ALPHA, k=optim.RANGER_K, step_counter=0, N_sma_threshhold=optim.RANGER_THRESHOLD)
-            group['params'] = ids
-        return {'state': state, 'param_groups': [group]}
-
-    @staticmethod
-    def _layout_of(sd):
-        """which optimiser family wrote `sd`: read off the keys only that family's object has"""
-        group = sd['param_groups'][0]
-        keys = set(group)
-        for st in sd['state'].values():
-            keys |= set(st)
-            break
-        if 'momentum_buffer' in keys or 'nesterov' in keys:
-            return 'sgd'
-        if 'slow_buffer' in keys or 'N_sma_threshhold' in keys:
-            return 'ranger'
-        if 'warmup' in keys:
-            return 'adamw'
-        if 'amsgrad' in keys:
-            return 'adam'
-        return 'radam' if 'betas' in keys else 'unknown'
+        """the optimiser entry of a checkpoint, in the layout of the reference's object for this optimiser (optim.state_dict)"""
+        return optim.state_dict(self)
 
     def load_state_dict(self, sd):
-        """Takes the state of the reference's object for THIS optimiser (RAdam and RAdam_4step share one layout); a state written by
-        another optimiser raises instead of silently starting from zero moments.  torch.optim.SGD stores no step count and the rule
-        only asks whether a momentum buffer exists yet (buf = g on the very first step): a loaded SGD state with momentum buffers
-        continues at step_count 1, one without them at 0."""
-        f = self.flat
-        params = list(self.model.named_parameters())
-        group = sd['param_groups'][0]
-        assert len(sd['param_groups']) == 1 and len(group['params']) == len(params), 'optimizer state of a different model'
-        rule = self.optimizer
-        mine, theirs = ('radam' if rule == 'radam4s' else rule), self._layout_of(sd)
-        if theirs != mine:
-            raise ValueError("optimizer state with the layout of '{}' cannot continue a '{}' run (param group keys: {})".format(
-                theirs, rule, ', '.join(sorted(k for k in group if k != 'params'))))
-        if rule == 'sgd':
-            self.lr, self.wd, self.momentum = group['lr'], group['weight_decay'], group['momentum']
-        else:
-            self.lr, self.betas, self.eps, self.wd = group['lr'], tuple(group['betas']), group['eps'], group['weight_decay']
-        bufs = self._state_buffers()
-        for _, buf in bufs:
-            if buf is not f.S:
-                buf.zero_()
-        if f.S is not None:
-            f.S.copy_(f.P[:f.n_used])
-        steps = set()
-        for i, st in sd['state'].items():
-            n, p = params[int(i)]
-            assert f.offsets[n][0] < f.n_used, 'state for a parameter that is never stepped: ' + n
-            for key, buf in bufs:
-                if key not in st or st[key] is None:
-                    raise ValueError("optimizer state of parameter {} lacks '{}': not a state of '{}'".format(n, key, rule))
-                self._scatter(buf, n, p, st[key])
-            steps.add(1 if rule == 'sgd' else int(st['step']))
-        assert len(steps) <= 1, 'per-parameter step counts differ: not a state of one optimiser over the whole model'
-        f.step_count = steps.pop() if steps else 0
+        """continue from such an entry: the state buffers, the step count and the group's lr / weight decay / betas / eps / momentum
+        (optim.load_state_dict)"""
+        optim.load_state_dict(self, sd)
 
     def train_step(self, x, label, dirlab, point_t, weight):
         """x f32 [B,3,H,W]; label u8 [B,H,W] in {0,1,2}; dirlab u8 [B,H,W] 0..8; point_t f16 [B,H,W]; weight u8 [B,H,W]
@@ -999,25 +810,8 @@ class UNetTrainer(Trainer):
         return dmask
 
     def backward(self, dlogits):
-        m = self.model
-        feat = m._last_feat
-        N, H, W, _ = feat.x.shape
-        grads = {}
-
-        def add(t, g):
-            grads.setdefault(id(t), []).append(g)
-        K = m.num_classes
-        df = self.buf('dF', (N, H, W, 64), runtime.act_dtype())
-        lib = _lib.load()
-        ws = self._slab(lib.cdnet_final_conv1x1_backward_workspace_floats())
-        hf = runtime.head_feat(feat)
-        w = m.final_conv.weight.detach().reshape(K, 64)
-        _lib.call('cdnet_final_conv1x1_backward', C.byref(hf), _lib.ptr(w), _lib.ptr(dlogits), K, N, H, W, _lib.ptr(df), _lib.ptr(ws),
-                  ws.numel(), _lib.ptr(m.final_conv.weight.grad), _lib.ptr(m.final_conv.bias.grad), _lib.stream_ptr())
-        add(feat.x, _G(df, H, W))
-        self._overlap_begin()
-        self._overlap_done([m.final_conv.weight, m.final_conv.bias])
-        self._backward_tape(grads, add)
+        conv, feat = self.model.final_conv, self.model._last_feat
+        self._run_tape([(feat.x, self._classifier_backward('dF', feat, conv, dlogits))], [conv.weight, conv.bias])
 
     def train_step(self, x, label, weight):
         """x f32 [B,3,H,W]; label u8 [B,H,W] in {0,1,2}; weight u8 [B,H,W] (png weight map, /20 on the fly,
@@ -1056,28 +850,13 @@ class AblationTrainer(Trainer):
     def backward(self, dmask, dpoint, ddir):
         m = self.model
         f1m, f2, f3 = m._last_feats
-        N, H, W, _ = f1m.x.shape
-        grads = {}
-
-        def add(t, g):
-            grads.setdefault(id(t), []).append(g)
-        lib = _lib.load()
-        ws = self._slab(lib.cdnet_final_conv1x1_backward_workspace_floats())
-        params = []
+        heads, params = [], []
         for name, f, conv, dl in (('m', f1m, m.mask_conv, dmask), ('d', f2, m.direction_conv, ddir), ('p', f3, m.point_conv, dpoint)):
             if f is None or dl is None:
                 continue
-            K = conv.out_channels
-            df = self.buf('dF' + name, (N, H, W, 64), runtime.act_dtype())
-            hf = runtime.head_feat(f)
-            w = conv.weight.detach().reshape(K, 64)
-            _lib.call('cdnet_final_conv1x1_backward', C.byref(hf), _lib.ptr(w), _lib.ptr(dl), K, N, H, W, _lib.ptr(df), _lib.ptr(ws),
-                      ws.numel(), _lib.ptr(conv.weight.grad), _lib.ptr(conv.bias.grad), _lib.stream_ptr())
-            add(getattr(f, 'grad_to', (f.x,))[0], _G(df, H, W))
+            heads.append((getattr(f, 'grad_to', (f.x,))[0], self._classifier_backward('dF' + name, f, conv, dl)))
             params += [conv.weight, conv.bias]
-        self._overlap_begin()
-        self._overlap_done(params)
-        self._backward_tape(grads, add)
+        self._run_tape(heads, params)
 
     def train_step(self, x, label, dirlab, point_t, weight):
         out = self.forward(x)
@@ -1087,90 +866,7 @@ class AblationTrainer(Trainer):
         return self.losses
 
 
-class BucketReducer:
-    """Releases buckets of a flat gradient buffer to the all-reduce as soon as they are complete.
-    The buffer is laid out in forward order and backward fills it from the end: `pending` maps the start offset of
-    every tensor that still waits for its gradient to its end offset; a bucket [a, b) is launched (async all-reduce,
-    top-down) once no pending tensor reaches into or above it.  Bucket boundaries are counted from the TOP of the used
-    range (n, n - B, n - 2B, ..., 0): the remainder bucket is then the lowest one - the one that completes last, with the
-    first layers' gradients at the very end of backward, and whose collective nothing is left to hide (59 MB of
-    gradients in 25 MB buckets: a 6 MB tail instead of a 25 MB one).  Every rank runs the same schedule, so the
-    collectives are issued in the same order everywhere.  Backend-agnostic (RCCL on the GPUs, gloo in the CPU tests)."""
-
-    def __init__(self, flat, n_used, bucket_elems, pending):
-        self.flat, self.n, self.bucket = flat, n_used, bucket_elems
-        self.pending = dict(pending)
-        self.works = []
-        self.bounds = [n_used]                       # descending bucket boundaries
-        while self.bounds[-1] > 0:
-            self.bounds.append(max(0, self.bounds[-1] - bucket_elems))
-        self.next = 0                                # buckets [bounds[j + 1], bounds[j]) with j < next are in flight
-        self.early = 0                               # buckets released before finish() (overlap actually happened)
-
-    def _launch(self, top):
-        import torch.distributed as dist
-        while self.next + 1 < len(self.bounds) and self.bounds[self.next + 1] >= top:
-            a, b = self.bounds[self.next + 1], self.bounds[self.next]
-            self.works.append(dist.all_reduce(self.flat[a:b], op=dist.ReduceOp.SUM, async_op=True))
-            self.next += 1
-
-    def done(self, offsets):
-        for off in offsets:
-            self.pending.pop(off, None)
-        before = len(self.works)
-        self._launch(max(self.pending.values()) if self.pending else 0)
-        self.early += len(self.works) - before
-
-    def finish(self, wait=True):
-        """launch what is left; wait=False returns the buckets' ranges in launch order instead (the caller waits per bucket)"""
-        self._launch(0)
-        if wait:
-            for w in self.works:
-                w.wait()
-        return [(self.bounds[j + 1], self.bounds[j]) for j in range(len(self.works))]
-
-
-def bucketed_allreduce(flat, n, bucket_elems):
-    """Sum-all-reduce of the first n elements of a flat gradient buffer in fixed-size buckets (RCCL over xGMI on the GPU,
-    gloo in the CPU tests).  The reference's nn.DataParallel reduce_add of the replicas' gradients (train.py:185) becomes
-    one process per GPU + this call; unused parameters sit beyond n and are never communicated."""
-    import torch.distributed as dist
-    works = []
-    for off in range(0, n, bucket_elems):
-        works.append(dist.all_reduce(flat[off:min(n, off + bucket_elems)], op=dist.ReduceOp.SUM, async_op=True))
-    for w in works:
-        w.wait()
-
-
 # ----------------------------------------------------------------------------------------------------------
-def synthetic_batch(B, dev, seed=2022, H=256, W=256):
-    """SURVEY 8d recipe: uniform RGB tiles, ellipse instances -> 3-class label / centripetal classes / point map,
-    constant weight map 20."""
-    import numpy as np
-    from . import synth
-    rs = np.random.RandomState(seed)
-    x = (rs.randint(0, 256, size=(B, 3, H, W)).astype(np.float32) / 255.0)
-    lab = np.zeros((B, H, W), np.uint8)
-    dirn = np.zeros((B, H, W), np.uint8)
-    point = np.zeros((B, H, W), np.float16)
-    for b in range(B):
-        inst = synth.ellipse_instances(H, W, 60, rs, 5, 12, 10)
-        inside = inst > 0
-        ero = synth.erode8(inside)
-        lab[b][ero] = 1
-        lab[b][inside & ~ero] = 2
-        d, cents = synth.centroid_direction(inst)
-        d[~ero] = 0
-        dirn[b] = d
-        pt = np.zeros((H, W), np.float64)
-        for cy, cx in cents:
-            pt[cy, cx] = 255.0
-        point[b] = synth.gaussian_blur(pt, 2.0).astype(np.float16)
-    weight = np.full((B, H, W), 20, np.uint8)
-    t = lambda a: torch.from_numpy(a).to(dev)
-    return t(x), t(lab), t(dirn), t(point), t(weight)
-
-
 def make_bench_step(model, B, dev, rank, world):
     """the benchmark's training step on a fixed synthetic batch: eager launches (a HIP-graph replay of forward + loss + backward was measured
     6-20 % slower on this step - the GPU, not the launch path, bounds it; cdnet_amd.graphs stays for the launch-bound HRNet step,

@@ -61,7 +61,7 @@ def split_forward_views(model, image, size, overlap, xforms=(0,), direction_clas
 
     def pack(i, dst):
         hv, wv, stride, th, tw, ny, nx = geo[i]
-        _lib.call('cdnet_window_pack_f32' if f32 else 'cdnet_window_pack', _lib.ptr(image), Cc, H0, W0, int(xforms[i]), th, tw, stride, ny, nx,
+        _lib.call(_lib.entry('cdnet_window_pack', f32), _lib.ptr(image), Cc, H0, W0, int(xforms[i]), th, tw, stride, ny, nx,
                   _lib.ptr(dst), _lib.stream_ptr())
 
     def stitch(i, logits, off):
@@ -163,7 +163,7 @@ def trainer_class(model):
 
 
 def get_optimizer(args, model, world_size=1):
-    """utils.py:907-962: returns (Trainer, scheduler).  The fused device optimiser lives inside cdnet_amd.trainer.Trainer - 'adam'
+    """utils.py:907-962: returns (Trainer, scheduler).  cdnet_amd.trainer.Trainer steps the fused device optimiser (cdnet_amd.optim.stepper) - 'adam'
     (lr, betas=(0.9, 0.99), weight_decay; cdnet_adam_step) or one of 'sgd' (momentum = args.momentum), 'radam', 'radam4s', 'adamw',
     'ranger' (cdnet_sgd_step / cdnet_moment_step), matched case-insensitively.  An unknown name raises ValueError (the reference's
     `raise '<str>'` is a TypeError by accident).  The scheduler is an optim.LRSchedule for the four torch schedulers of :941-957 and None
