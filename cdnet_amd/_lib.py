@@ -80,6 +80,10 @@ SIGNATURES = {
     'cdnet_bn_backward': (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     'cdnet_dam_head_backward_workspace_floats': (_sz, [_i, _i, _i]),
     'cdnet_dam_head_backward': (_i, [_vp] * 7 + [_i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    'cdnet_dam_head_backward_fused_blocks': (_i, []),
+    'cdnet_dam_head_backward_fused_scratch_bytes': (_i, []),
+    'cdnet_dam_head_backward_fused_workspace_floats': (_sz, []),
+    'cdnet_dam_head_backward_fused': (_i, [_vp] * 7 + [_i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     'cdnet_dam_loss_workspace_floats': (_sz, [_i, _i]),
     'cdnet_dam_loss': (_i, [_vp] * 7 + [_i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     'cdnet_dam_loss_classes_workspace_floats': (_sz, [_i, _i, _i]),

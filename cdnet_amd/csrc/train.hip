@@ -1161,6 +1161,253 @@ __global__ __launch_bounds__(256) void dam_head_wgrad_kernel(HeadFeat f1, HeadFe
     }
 }
 
+// Kernels 1 and 2 in one pass over the features, for the fp32 training step: three plain stored fp32 features; f3 is the output of a
+// residual unit with the fused epilogue that the head alone reads, so its gradient leaves as dz3 = (f3 > 0) ? dF3 : 0 (the sums pass of
+// that unit's bn2 then reads one gradient tensor without the mask).  Every sum is taken in the order of the two-kernel path, so the
+// results are bit-identical to it:
+//   workgroup b (512 threads) owns the 32 pixel chains of dam_head_wgrad_kernel's workgroup b (pixels 32 b + j + 32768 it) and walks
+//   four of its iterations per 128-pixel group.  Per pixel (four lanes) the arithmetic of dam_head_bwd_kernel in the same order; the 13
+//   coefficients and the features go through LDS into dam_head_wgrad_kernel's mapping (thread = 8 channels x pixel chain; the 13 rows
+//   split over the two halves of the workgroup: 56 accumulators per thread, the same fma chain per accumulator, the same reduction at
+//   the end) - the coefficient tensor is never written, the features are read once.
+//   The 23 scalar sums: dam_head_bwd_kernel's chain (workgroup b', slot s') is the pixels 64 b' + s' + 65536 it', i.e. here the quads of
+//   iteration parity h & 1, alternately h < 2 and h >= 2: the quad with h < 2 keeps the chain and takes the other one's terms through LDS.
+//   The per-chain sums go to sgbuf[1024][64][24]; head_scalar_reduce_kernel adds the 64 slots of a workgroup in that kernel's order.
+// All of a pixel group's loads (three features, 13 gradient planes) are issued before the first use, indices clamped.
+constexpr int HEAD_FUSED_BLOCKS = 1024;           // = the grid of the two-kernel path (the partition of the sums depends on it)
+constexpr int HF_ROW = 68;                        // LDS floats per staged pixel (64 + 4: 16-byte aligned rows off the 64-float bank period)
+
+// rows R0 .. R0 + 6 of the 13 x 64 block (row 13: a zero coefficient) for one pixel: row 0 x F3, rows 1..9 x F2, rows 10..12 x F1
+template <int R0>
+__device__ __forceinline__ void head_wgrad_rows(float (&gw)[7][8], const float *cfrow, const float *f3p, const float *f2p, const float *f1p) {
+    const float4 *cr = reinterpret_cast<const float4 *>(cfrow);
+    const float4 c0 = cr[0], c1 = cr[1], c2 = cr[2], c3 = cr[3];
+    const float cf[16] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w, c2.x, c2.y, c2.z, c2.w, c3.x, c3.y, c3.z, c3.w};
+    float x3[8], x2[8], x1[8];
+    if (R0 == 0) ldf8(f3p, 0, x3);
+    ldf8(f2p, 0, x2);
+    if (R0 != 0) ldf8(f1p, 0, x1);
+#pragma unroll
+    for (int r = 0; r < 7; ++r) {
+        const int row = R0 + r;
+        if (row >= 13) continue;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const float x = row == 0 ? x3[k] : row < 10 ? x2[k] : x1[k];
+            gw[r][k] = fmaf(cf[row], x, gw[r][k]);
+        }
+    }
+}
+
+__global__ __launch_bounds__(512)
+void dam_head_bwd_fused_kernel(const float *__restrict__ f1, const float *__restrict__ f2, const float *__restrict__ f3,
+                               const HeadW *__restrict__ hw, const float *__restrict__ dmask, const float *__restrict__ dpoint,
+                               const float *__restrict__ ddir, int N, int plane, float *__restrict__ df1, float *__restrict__ df2,
+                               float *__restrict__ dz3, float *__restrict__ partial, float *__restrict__ sgbuf) {
+    __shared__ HeadW w;
+    __shared__ __attribute__((aligned(16))) float s_cf[128 * 16];
+    __shared__ __attribute__((aligned(16))) float s_f[3][128 * HF_ROW];     // (>= 4 x 13 x 64: the waves' weight-gradient blocks at the end)
+    __shared__ float s_sg[64 * 4][12];
+    const int tid = threadIdx.x;
+    {
+        const float *src = reinterpret_cast<const float *>(hw);
+        float *dst = reinterpret_cast<float *>(&w);
+        for (int i = tid; i < HEADW_FLOATS; i += 512) dst[i] = src[i];
+    }
+    __syncthreads();
+    const unsigned total = (unsigned)N * (unsigned)plane;          // (32-bit element indices: the entry checks total * 64 < 2^32)
+    const int q = tid & 3, slot = tid >> 2;          // per-pixel phase: lane of the pixel's quad, pixel slot of the group (0..127)
+    const int sh = slot >> 5, sj = slot & 31;        // ... = iteration of dam_head_wgrad_kernel within the group, and its chain
+    const int c8 = (tid & 7) * 8, pg = (tid & 255) >> 3, rs = tid >> 8;     // weight-gradient phase: that kernel's mapping, half of the rows
+    // the 23 scalar gradients dbm[3] | dbd[9] | dbp | da1 | da2[9] are the same on the four lanes of a pixel: lane q keeps those with
+    // index 4 s + q (6 registers instead of 23); sum = fma(x, y, sum) with y = 1 for the plain sums (exact)
+    float sgq[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) sgq[j] = 0.f;
+    float gw[7][8];
+#pragma unroll
+    for (int j = 0; j < 7; ++j)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) gw[j][k] = 0.f;
+    for (unsigned base = blockIdx.x * 32; base < total; base += 4 * 32768) {
+        const unsigned i = base + sj + sh * 32768;
+        const bool ok = i < total;
+        const unsigned ii = ok ? i : total - 1;
+        const unsigned n = ii / (unsigned)plane, p = ii - n * (unsigned)plane;
+        // (the head weights stay in LDS: without this fence the compiler hoists a lane's 208 weight reads out of the loop)
+        asm volatile("" ::: "memory");
+        float F3[16], F2[16], F1[16], v[16];
+        const unsigned e = ii * 64 + q * 16;
+        ldf8(f3, e, F3); ldf8(f3, e + 8, F3 + 8);
+        ldf8(f2, e, F2); ldf8(f2, e + 8, F2 + 8);
+        ldf8(f1, e, F1); ldf8(f1, e + 8, F1 + 8);
+        float go_m[3], go_d[9], go_p;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) go_m[k] = dmask[(n * 3 + k) * plane + p];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) go_d[k] = ddir[(n * 9 + k) * plane + p];
+        go_p = dpoint[n * plane + p];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) go_m[k] = ok ? go_m[k] : 0.f;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) go_d[k] = ok ? go_d[k] : 0.f;
+        go_p = ok ? go_p : 0.f;
+        // each feature goes to LDS for the weight-gradient phase as soon as its dot products are done (registers)
+        auto stage = [&](const float *F, int k) {
+            float *dst = s_f[k] + slot * HF_ROW + q * 16;
+#pragma unroll
+            for (int h = 0; h < 4; ++h) *reinterpret_cast<float4 *>(dst + 4 * h) = make_float4(F[4 * h], F[4 * h + 1], F[4 * h + 2], F[4 * h + 3]);
+        };
+        __syncthreads();                             // (the previous group's weight-gradient phase has read the slices)
+        const float pt = quad_sum(xf_dot16(w.wp + q * 16, F3)) + w.bp;
+        unsigned pos3 = 0;                           // the unit's ReLU mask, read from the stored output
+#pragma unroll
+        for (int j = 0; j < 16; ++j) pos3 |= F3[j] > 0.f ? 1u << j : 0u;
+        stage(F3, 0);
+        __builtin_amdgcn_sched_barrier(0);           // (phases kept apart: interleaved, their LDS weight reads overflow the registers)
+        const float sg1 = 1.f / (1.f + expf(-(w.a1 * pt)));
+        const float g1 = 1.f + sg1;
+        float u[9], d[9], q2 = 0.f;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            u[k] = quad_sum(xf_dot16(w.wd[k] + q * 16, F2));
+            d[k] = fmaf(g1, u[k], w.bd[k]);
+            q2 = fmaf(w.a2[k], d[k], q2);
+        }
+        stage(F2, 1);
+        __builtin_amdgcn_sched_barrier(0);
+        const float sg2 = 1.f / (1.f + expf(-q2));
+        const float g2 = 1.f + sg2;
+        float dm[3], dg2 = 0.f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float mk = quad_sum(xf_dot16(w.wm[k] + q * 16, F1));
+            const float go = go_m[k];
+            dg2 = fmaf(go, mk, dg2);
+            dm[k] = go * g2;
+        }
+        stage(F1, 2);
+        __builtin_amdgcn_sched_barrier(0);
+        xf_axpy16(dm[0], w.wm[0] + q * 16, v, false);
+        xf_axpy16(dm[1], w.wm[1] + q * 16, v, true);
+        xf_axpy16(dm[2], w.wm[2] + q * 16, v, true);
+        if (ok) { stf8(df1, e, v); stf8(df1, e + 8, v + 8); }
+        __builtin_amdgcn_sched_barrier(0);
+        const float dq2 = dg2 * sg2 * (1.f - sg2);
+        float du[9], dd[9], dg1 = 0.f;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            dd[k] = go_d[k] + dq2 * w.a2[k];
+            dg1 = fmaf(dd[k], u[k], dg1);
+            du[k] = dd[k] * g1;
+        }
+#pragma unroll
+        for (int k = 0; k < 9; ++k) xf_axpy16(du[k], w.wd[k] + q * 16, v, k != 0);
+        if (ok) { stf8(df2, e, v); stf8(df2, e + 8, v + 8); }
+        __builtin_amdgcn_sched_barrier(0);
+        const float dsg1 = dg1 * sg1 * (1.f - sg1);
+        const float dpt = go_p + dsg1 * w.a1;
+        // this pixel's terms of the scalar sums (x, y) -> sum = fma(x, y, sum): the 4 s + q-th of [go_m[3] | dd[9] | dpt | dsg1 pt | dq2 d[9]]
+        float sx[6], sy[6];
+        {
+            float tx[24], ty[24];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) { tx[j] = go_m[j]; ty[j] = 1.f; }
+#pragma unroll
+            for (int j = 0; j < 9; ++j) { tx[3 + j] = dd[j]; ty[3 + j] = 1.f; tx[14 + j] = dq2; ty[14 + j] = d[j]; }
+            tx[12] = dpt; ty[12] = 1.f; tx[13] = dsg1; ty[13] = pt; tx[23] = 0.f; ty[23] = 0.f;
+#pragma unroll
+            for (int s = 0; s < 6; ++s) {
+                sx[s] = q == 0 ? tx[4 * s] : q == 1 ? tx[4 * s + 1] : q == 2 ? tx[4 * s + 2] : tx[4 * s + 3];
+                sy[s] = q == 0 ? ty[4 * s] : q == 1 ? ty[4 * s + 1] : q == 2 ? ty[4 * s + 2] : ty[4 * s + 3];
+            }
+        }
+        if (sh < 2) {
+#pragma unroll
+            for (int s = 0; s < 6; ++s) sgq[s] = fmaf(sx[s], sy[s], sgq[s]);
+        } else {
+#pragma unroll
+            for (int s = 0; s < 6; ++s) { s_sg[tid - 256][s] = sx[s]; s_sg[tid - 256][6 + s] = sy[s]; }
+        }
+        xf_axpy16(dpt, w.wp + q * 16, v, false);
+        // v = dF3: through the unit's ReLU (mask from the stored output)
+#pragma unroll
+        for (int j = 0; j < 16; ++j) v[j] = (pos3 >> j & 1) ? v[j] : 0.f;
+        if (ok) { stf8(dz3, e, v); stf8(dz3, e + 8, v + 8); }
+        __builtin_amdgcn_sched_barrier(0);
+        // coefficient row [dpt | du[9] | dm[3] | 0 0 0] of the pixel: lane q writes floats 4q..4q+3
+        {
+            float4 cf;
+            if (q == 0) cf = make_float4(dpt, du[0], du[1], du[2]);
+            else if (q == 1) cf = make_float4(du[3], du[4], du[5], du[6]);
+            else if (q == 2) cf = make_float4(du[7], du[8], dm[0], dm[1]);
+            else cf = make_float4(dm[2], 0.f, 0.f, 0.f);
+            *reinterpret_cast<float4 *>(s_cf + slot * 16 + q * 4) = cf;
+        }
+        __syncthreads();
+        // the chain's next pixel (iteration h + 2 of this group) was computed by the quad 256 threads up
+        if (sh < 2) {
+#pragma unroll
+            for (int s = 0; s < 6; ++s) sgq[s] = fmaf(s_sg[tid][s], s_sg[tid][6 + s], sgq[s]);
+        }
+        // weight gradients: dam_head_wgrad_kernel's four iterations of this group, one pixel of chain pg each, in its order
+#pragma unroll 1
+        for (int h = 0; h < 4; ++h) {
+            if (base + pg + h * 32768 < total) {
+                const int s = h * 32 + pg;
+                if (rs == 0) head_wgrad_rows<0>(gw, s_cf + s * 16, s_f[0] + s * HF_ROW + c8, s_f[1] + s * HF_ROW + c8, s_f[2] + s * HF_ROW + c8);
+                else head_wgrad_rows<7>(gw, s_cf + s * 16, s_f[0] + s * HF_ROW + c8, s_f[1] + s * HF_ROW + c8, s_f[2] + s * HF_ROW + c8);
+            }
+        }
+    }
+    // the chain of scalar sums this quad kept: dam_head_bwd_kernel's workgroup (b >> 1) + 512 (h & 1), slot 32 (b & 1) + j
+    if (sh < 2) {
+        float *o = sgbuf + ((size_t)((blockIdx.x >> 1) + 512 * sh) * 64 + 32 * (blockIdx.x & 1) + sj) * 24;
+#pragma unroll
+        for (int s = 0; s < 6; ++s) o[4 * s + q] = sgq[s];
+    }
+    // dam_head_wgrad_kernel's reduction: the 8 chains of a wave, then the four waves
+#pragma unroll
+    for (int j = 0; j < 7; ++j)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            float t = gw[j][k];
+            t += __shfl_xor(t, 8); t += __shfl_xor(t, 16); t += __shfl_xor(t, 32);
+            gw[j][k] = t;
+        }
+    __syncthreads();
+    float *s_w = s_f[0];                             // [4][13][64]
+    if ((tid & 63) < 8) {
+#pragma unroll
+        for (int j = 0; j < 7; ++j)
+            if (rs * 7 + j < 13) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) s_w[((((tid & 255) >> 6) * 13) + rs * 7 + j) * 64 + c8 + k] = gw[j][k];
+            }
+    }
+    __syncthreads();
+    float *o = partial + (size_t)blockIdx.x * HEADW_FLOATS;
+    for (int idx = tid; idx < 13 * 64; idx += 512) o[idx] = (s_w[idx] + s_w[832 + idx]) + (s_w[2 * 832 + idx] + s_w[3 * 832 + idx]);
+}
+
+// dam_head_bwd_kernel's block reduction of the 23 scalar sums over the chains dam_head_bwd_fused_kernel left: workgroup = one workgroup
+// of that kernel, the 64 slots added in its order
+__global__ __launch_bounds__(64) void head_scalar_reduce_kernel(const float *__restrict__ sgbuf, float *__restrict__ partial) {
+    const int tid = threadIdx.x;
+    if (tid < 23) {
+        const float *sg = sgbuf + (size_t)blockIdx.x * 64 * 24;
+        float s = 0.f;
+        for (int k = 0; k < 64; ++k) s += sg[k * 24 + tid];
+        int dst;                                     // HeadW tail: bp, bd[9], bm[3], a1, a2[9]
+        if (tid < 3) dst = 832 + 10 + tid;
+        else if (tid < 12) dst = 832 + 1 + (tid - 3);
+        else if (tid == 12) dst = 832;
+        else if (tid == 13) dst = 832 + 13;
+        else dst = 832 + 14 + (tid - 14);
+        partial[(size_t)blockIdx.x * HEADW_FLOATS + dst] = s;
+    }
+}
+
 // ======================================================================================================
 // Loss (train_util_dam.py:167-276) - two passes over the logits
 // ======================================================================================================
@@ -1862,10 +2109,11 @@ extern "C" int cdnet_bn_backward(const cdnet_bn_bwd_args *a, const float *gamma,
 // residual, 16-bit tensors): `stats` = reduce + finalize and the [7][C] table scale | shift | mean | invstd | k1 | k2 | k3 that both
 // the apply pass and a fused consumer (cdnet_conv_src.relu = 3) read; `apply` = the second pass alone.  The trainer runs `stats`
 // on the main chain, backward-data with the fused source right behind it, and `apply` + the weight gradient on the side stream.
-static bool bn_plain_case(const BnBwdArgs &A) {
+// masked: the source may also be a gradient that already went through the ReLU (relu = 0: dz as a residual unit's sums pass stores it)
+static bool bn_plain_case(const BnBwdArgs &A, bool masked = false) {
     const GradIn &g = A.gin[0];
     return A.ngin == 1 && !g.pooled && g.oy == 0 && g.ox == 0 && g.Hg == A.H && g.Wg == A.W && A.mean && A.scale && A.shift && A.invstd && !A.res &&
-           A.relu == 1 && (g.cstride == 0 || g.cstride == A.C) && g.coff == 0;
+           (A.relu == 1 || (masked && A.relu == 0)) && (g.cstride == 0 || g.cstride == A.C) && g.coff == 0;
 }
 
 __global__ void bn_ktab_copy_kernel(const float *scale, const float *shift, const float *mean, const float *invstd, int C, float *ktab) {
@@ -1917,7 +2165,7 @@ extern "C" int cdnet_bn_backward_apply(const cdnet_bn_bwd_args *a, const float *
     BnBwdArgs A;
     int rc = fill_bn_args(a, A, "cdnet_bn_backward_apply");
     if (rc) return rc;
-    CDNET_REQUIRE(bn_plain_case(A) && ktab && draw, "cdnet_bn_backward_apply: plain case only");
+    CDNET_REQUIRE(bn_plain_case(A, true) && ktab && draw, "cdnet_bn_backward_apply: plain case only");
     const size_t npix = (size_t)A.N * A.H * A.W;
     const bool f32 = A.f16 == 2;                                 // fp32 tensors (gradient, raw output, dRaw): the flat32 kernel
     CDNET_REQUIRE(!f32 || A.C <= 1024, "cdnet_bn_backward_apply(f32): C=%d > 1024", A.C);
@@ -1974,6 +2222,40 @@ extern "C" int cdnet_dam_head_backward(const cdnet_head_feat *f1, const cdnet_he
 
 extern "C" size_t cdnet_dam_head_backward_workspace_floats(int N, int H, int W) {
     return (size_t)1024 * HEADW_FLOATS + (size_t)N * H * W * 16;
+}
+
+extern "C" int cdnet_dam_head_backward_fused_blocks(void) { return HEAD_FUSED_BLOCKS; }
+/* private (scratch) memory per lane of dam_head_bwd_fused_kernel as built: it holds 256 VGPRs only just - a test keeps this at 0 */
+extern "C" int cdnet_dam_head_backward_fused_scratch_bytes(void) {
+    hipFuncAttributes at;
+    if (hipFuncGetAttributes(&at, reinterpret_cast<const void *>(dam_head_bwd_fused_kernel)) != hipSuccess) return -1;
+    return (int)at.localSizeBytes;
+}
+extern "C" size_t cdnet_dam_head_backward_fused_workspace_floats(void) { return (size_t)HEAD_FUSED_BLOCKS * (HEADW_FLOATS + 64 * 24); }
+
+extern "C" int cdnet_dam_head_backward_fused(const cdnet_head_feat *f1, const cdnet_head_feat *f2, const cdnet_head_feat *f3,
+                                             const float *head_weights, const float *dmask, const float *dpoint, const float *ddir,
+                                             int N, int H, int W, float *df1, float *df2, float *dz3, float *workspace,
+                                             size_t workspace_floats, float *dhead_weights, void *stream) {
+    CDNET_REQUIRE(f1 && f2 && f3 && head_weights && dmask && dpoint && ddir && df1 && df2 && dz3 && workspace && dhead_weights,
+                  "cdnet_dam_head_backward_fused: null pointer");
+    auto plain32 = [](const cdnet_head_feat &f) { return f.raw && f.f16 == 2 && !f.scale && !f.shift && !f.relu && !f.res; };
+    CDNET_REQUIRE(plain32(*f1) && plain32(*f2) && plain32(*f3),
+                  "cdnet_dam_head_backward_fused: plain stored fp32 features only (f16 = 2, no scale / shift / relu / res)");
+    CDNET_REQUIRE(N >= 1 && H >= 1 && W >= 1, "cdnet_dam_head_backward_fused: N=%d H=%d W=%d", N, H, W);
+    CDNET_REQUIRE((size_t)N * H * W * 64 < ((size_t)1 << 32), "cdnet_dam_head_backward_fused: tensor too large for 32-bit element indexing");
+    static_assert(HEAD_FUSED_BLOCKS == 1024, "the chains of the two-kernel path: 1024 workgroups");
+    const int nb = HEAD_FUSED_BLOCKS;
+    const size_t need = (size_t)nb * (HEADW_FLOATS + 64 * 24);
+    if (workspace_floats < need) { set_error("cdnet_dam_head_backward_fused: workspace %zu < %zu floats", workspace_floats, need); return CDNET_E_WORKSPACE; }
+    hipStream_t st = (hipStream_t)stream;
+    float *partial = workspace, *sgbuf = workspace + (size_t)nb * HEADW_FLOATS;
+    auto fp = [](const cdnet_head_feat &f) { return reinterpret_cast<const float *>(f.raw); };
+    dam_head_bwd_fused_kernel<<<nb, 512, 0, st>>>(fp(*f1), fp(*f2), fp(*f3), reinterpret_cast<const HeadW *>(head_weights), dmask, dpoint, ddir,
+                                                  N, H * W, df1, df2, dz3, partial, sgbuf);
+    head_scalar_reduce_kernel<<<nb, 64, 0, st>>>(sgbuf, partial);
+    reduce_partials_kernel<<<cdiv(HEADW_FLOATS, 4), 256, 0, st>>>(workspace, nb, HEADW_FLOATS, dhead_weights);
+    return check_launch("cdnet_dam_head_backward_fused");
 }
 
 static int loss_nchunk(int P, int tpb) {

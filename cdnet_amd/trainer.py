@@ -43,6 +43,7 @@ _WGRAD_WGS_KQ = 128                        # wgrad_ws_kernel<1, 1> on 512 x 512 
 _WGRAD_WGS_F32 = 160                      # (128 / 160 / 256: 989 / 994 / 987 tiles/s, three runs each on one box)
 _RU_1X1_SIDE = True      # residual units' 1x1 backward-data beside the chain (tests flip it: same gradients either way)
 WGRAD_STREAM = True       # weight gradients on a second stream beside the input-gradient chain
+HEAD_BWD_FUSE = True      # fp32 mode, rev1 head: head backward + its weight gradients in one launch, dF3 behind the unit's ReLU (same bits)
 _WGRAD_DEFER = 0x100                       # CDNET_WGRAD_DEFER_REDUCE (include/cdnet_hip.h)
 _WGRAD_DEEP_HW = 16384
 
@@ -66,11 +67,13 @@ class _on_stream:
 
 class _G:
     """a gradient contribution for a stored tensor"""
-    __slots__ = ('t', 'Hg', 'Wg', 'oy', 'ox', 'pooled', 'coff', 'cstride', 'event')
+    __slots__ = ('t', 'Hg', 'Wg', 'oy', 'ox', 'pooled', 'coff', 'cstride', 'event', 'masked')
 
     def __init__(self, t, Hg, Wg, oy=0, ox=0, pooled=0, coff=0, cstride=0):
         self.t, self.Hg, self.Wg, self.oy, self.ox, self.pooled, self.coff, self.cstride = t, Hg, Wg, oy, ox, pooled, coff, cstride
         self.event = None                    # produced on another stream: the consumer's stream waits for this event first
+        self.masked = False                  # t is already dz of a residual unit's bn2: the consumer's gradient behind the unit's ReLU
+                                             # (cdnet_dam_head_backward_fused, _head_fusable)
 
 
 def _choose_ci_tiles(C_src, Cout):
@@ -138,6 +141,7 @@ class Trainer:
         self._packb_pending = False
         self._packb_stream = True              # backward-data re-packs beside the next forward
         self._side_active = False
+        self.head_fused = False                 # the last backward took cdnet_dam_head_backward_fused (_head_fusable)
         # split-K sums of the weight gradients: deferred and batched (one cdnet_wgrad_reduce_batch launch per ~CDNET_WGRAD_REDUCE_MB of
         # slabs instead of one reduce behind every weight-gradient launch; every call keeps its own slab buffer - 1.4 GB for the UNet)
         # Memory: with the default every weight-gradient call keeps its own split-K slab buffer for the trainer's lifetime (`buf(('wslab', ...))`,
@@ -278,11 +282,49 @@ class Trainer:
         df = [self.buf('dF%d' % k, (N, H, W, 64), runtime.act_dtype()) for k in range(3)]
         hf = [runtime.head_feat(f) for f in (f1, f2, f3)]
         dhead = self.flat.G[:self.flat.n_head]
+        owner = self._head_fusable(f1, f2, f3)
+        self.head_fused = owner is not None
+        if owner is not None:
+            # one launch instead of two (every feature read once, no coefficient tensor), bit-identical to them; dF3 leaves as dz3, behind
+            # the unit's ReLU - the tape walk runs point_feature.bn2's backward on it without the mask (_bn_backward_masked)
+            ws = self._ws('head', _lib.load().cdnet_dam_head_backward_fused_workspace_floats())
+            _lib.call('cdnet_dam_head_backward_fused', C.byref(hf[0]), C.byref(hf[1]), C.byref(hf[2]), _lib.ptr(m.head_weight_block()),
+                      _lib.ptr(dmask), _lib.ptr(dpoint), _lib.ptr(ddir), N, H, W, _lib.ptr(df[0]), _lib.ptr(df[1]), _lib.ptr(df[2]),
+                      _lib.ptr(ws), ws.numel(), _lib.ptr(dhead), _lib.stream_ptr())
+            heads = [(f.x, _G(d, H, W)) for f, d in zip((f1, f2, f3), df)]
+            heads[2][1].masked = True
+            self._run_tape(heads, None)
+            return
         ws = self._ws('head', _lib.load().cdnet_dam_head_backward_workspace_floats(N, H, W))
         _lib.call('cdnet_dam_head_backward', C.byref(hf[0]), C.byref(hf[1]), C.byref(hf[2]), _lib.ptr(m.head_weight_block()),
                   _lib.ptr(dmask), _lib.ptr(dpoint), _lib.ptr(ddir), N, H, W, _lib.ptr(df[0]), _lib.ptr(df[1]),
                   _lib.ptr(df[2]), _lib.ptr(ws), ws.numel(), _lib.ptr(dhead), _lib.stream_ptr())
         self._run_tape([(getattr(f, 'grad_to', (f.x,))[0], _G(d, H, W)) for f, d in zip((f1, f2, f3), df)], None)
+
+    def _head_fusable(self, f1, f2, f3):
+        """cdnet_dam_head_backward_fused's one case: fp32 mode, the rev1 head over three plain stored fp32 features, the third one the
+        output of a residual unit with the fused epilogue (BatchNorm + mask from the stored output) that nothing on the tape reads.
+        Returns that unit's conv2 layer or None"""
+        if not HEAD_BWD_FUSE or runtime.PRECISION != 'fp32' or getattr(self.model, 'VARIANT', None) != 'rev1':
+            return None
+        for f in (f1, f2, f3):
+            if f.x.dtype != torch.float32 or f.scale is not None or f.shift is not None or f.res is not None or f.relu or f.pool \
+                    or hasattr(f, 'grad_to') or tuple(f.off) != (0, 0) or f.C != 64:
+                return None
+        owner = None
+        for Lt in self.tape:
+            if isinstance(Lt, runtime.FuseNode):
+                if any(t.x is f3.x for t in Lt.saved[0]):
+                    return None
+                continue
+            if any(sx.x is f3.x or sx.res is f3.x for sx in Lt.saved[0]):
+                return None
+            if Lt.saved[1] is f3.x:
+                owner = getattr(Lt, 'fused_res_of', None) if Lt.kind == 'conv1' else None
+        if owner is None or owner.bn is None or getattr(owner, 'node_relu', True) != 2 or getattr(owner, 'node_res', None) is not f3.x \
+                or owner.saved[1].dtype != torch.float32 or tuple(owner.saved[1].shape) != tuple(f3.x.shape):
+            return None
+        return owner
 
     def _classifier_backward(self, key, f, conv, dl):
         """backward of a plain 1x1 classifier `conv` on the 64-channel feature `f` (cdnet_final_conv1x1_backward): fills the gradients of
@@ -402,7 +444,9 @@ class Trainer:
         No, Ho, Wo, Co = out.shape
         params = (L.weight, L.bias, None if L.bn is None else L.bn.weight, None if L.bn is None else L.bn.bias)
         part = self._bn_partials.pop(id(out), None)
-        if part is not None:
+        if len(gl) == 1 and gl[0].masked:
+            g = self._bn_backward_masked(L, out, gl[0], add)
+        elif part is not None:
             # the reader's backward-data launch left the channel sums: finalize + second pass only
             assert len(gl) == 1, (L.name, len(gl))
             a, ktab = self._bn_backward_stats(L, out, gl[0], partial=part)
@@ -450,6 +494,20 @@ class Trainer:
         _lib.call('cdnet_bn_backward_finalize', C.byref(a), _lib.ptr(bn.weight.detach()), _lib.ptr(bn.weight.grad), _lib.ptr(bn.bias.grad),
                   _lib.ptr(partial), partial.shape[0], _lib.ptr(ktab), _lib.stream_ptr())
         return a, ktab
+
+    def _bn_backward_masked(self, L, out, g, add):
+        """a residual unit's bn2 backward behind cdnet_dam_head_backward_fused: g.t is dz already (the consumer's gradient through the
+        unit's ReLU), so both passes take it as one plain relu = 0 source without residual - the sums pass reads two tensors instead of
+        three and stores none, the same sums in the same order as _bn_backward's; dz goes to the 1x1 branch as there"""
+        No, Ho, Wo, Co = out.shape
+        a = self._bn_args(L, out, [_G(g.t, g.Hg, g.Wg)], res=None, relu=0)
+        draw = self.buf(('draw', L.name), (No, Ho, Wo, Co), runtime.act_dtype())
+        ws = self._ws('bn', _lib.load().cdnet_bn_backward_workspace_floats(Co))
+        bn = L.bn
+        _lib.call('cdnet_bn_backward', C.byref(a), _lib.ptr(bn.weight.detach()), _lib.ptr(bn.weight.grad), _lib.ptr(bn.bias.grad),
+                  _lib.ptr(ws), ws.numel(), _lib.ptr(draw), None, _lib.stream_ptr())
+        add(L.node_res, _G(g.t, Ho, Wo))
+        return draw
 
     def _stats_fusable(self, L, srcs, H, W, N, wpb, cfgb, cin_total):
         """the single lazily transformed BatchNorm + ReLU source of a 3x3 convolution that is its only reader, and a backward-data

@@ -447,7 +447,8 @@ size_t cdnet_bn_backward_workspace_floats(int C);
 /* The two passes of cdnet_bn_backward as separate calls for the plain case (one same-size gradient source, BatchNorm + ReLU, no
  * residual branch).  cdnet_bn_backward_stats (16-bit tensors) = reduce + finalize; it also writes ktab f32 [7][C] =
  * scale | shift | mean | invstd | k1 | k2 | k3, the table cdnet_bn_backward_apply reads (the second pass alone: draw = k1 * (dz - k2 -
- * xhat * k3); 16-bit and fp32 tensors).  The trainer uses finalize + apply behind a backward-data launch that carried the sums
+ * xhat * k3); 16-bit and fp32 tensors; relu = 0 as well: the one source is a gradient that already passed the ReLU, the dz a
+ * residual unit's sums pass or cdnet_dam_head_backward_fused stored).  The trainer uses finalize + apply behind a backward-data launch that carried the sums
  * (cdnet_conv_args.ws = 2, fp32 mode). */
 int cdnet_bn_backward_stats(const cdnet_bn_bwd_args *args, const float *gamma, float *dgamma, float *dbeta, float *workspace,
                             size_t workspace_floats, float *ktab, void *stream);
@@ -470,6 +471,24 @@ int cdnet_dam_head_backward(const cdnet_head_feat *f1, const cdnet_head_feat *f2
                             const float *head_weights, const float *dmask, const float *dpoint, const float *ddir,
                             int N, int H, int W, uint16_t *df1, uint16_t *df2, uint16_t *df3, float *workspace,
                             size_t workspace_floats, float *dhead_weights, void *stream);
+/* The same in ONE pass over the features for the fp32 training step (model_unet_rev1.py:150-170 - the residual unit whose output is the
+ * third feature -, :258-263; loss.backward(), train_util_dam.py:303-308): the feature gradients and the head's weight gradients from one
+ * kernel that reads each feature once and writes no per-pixel coefficient tensor.  Serves one case and refuses every other
+ * (CDNET_E_ARG): f1, f2, f3 are plain stored fp32 NHWC tensors with 64 channels (f16 = 2, no scale / shift / relu / res), f3 the output
+ * of a residual unit with the fused epilogue that the head alone reads.
+ *   df1, df2 f32 [N][H][W][64]: the feature gradients
+ *   dz3 f32 [N][H][W][64] = (f3 > 0) ? dF3 : 0: the gradient behind the unit's ReLU (dF3 itself is not stored); the unit's bn2 takes it
+ *       as a relu = 0 source without residual (cdnet_bn_backward: its sums pass then reads two tensors and writes none)
+ *   dhead_weights as above.  workspace: cdnet_dam_head_backward_fused_workspace_floats().
+ * Every sum is taken in the order of cdnet_dam_head_backward (cdnet_dam_head_backward_fused_blocks() = its 1024 workgroups): df1, df2,
+ * dz3 = [f3 > 0] df3 and dhead_weights are bit-identical to its results. */
+int cdnet_dam_head_backward_fused_blocks(void);
+int cdnet_dam_head_backward_fused_scratch_bytes(void);   /* scratch bytes per lane of the kernel as built (-1: query failed); expected 0 */
+size_t cdnet_dam_head_backward_fused_workspace_floats(void);
+int cdnet_dam_head_backward_fused(const cdnet_head_feat *f1, const cdnet_head_feat *f2, const cdnet_head_feat *f3,
+                                  const float *head_weights, const float *dmask, const float *dpoint, const float *ddir, int N, int H,
+                                  int W, float *df1, float *df2, float *dz3, float *workspace, size_t workspace_floats,
+                                  float *dhead_weights, void *stream);
 
 /* The five-term CDNet loss (train_util_dam.py:167-276; loss.py:131-260) and its gradient w.r.t. the logits.
  * label u8 {0,1,2}, dirlab u8 0..8, point target f16, weight map u8 (divided by 20 on the fly, :102).
