@@ -1,769 +1,19 @@
-// Training-only streaming kernels (HBM-bound): BatchNorm/ReLU/max-pool backward, the DAM head backward, the five-term
-// CDNet loss with its gradient, and the fused Adam step.  Everything reduces through per-block partials that are
+// Training-only streaming kernels (HBM-bound): the DAM head backward, the five-term CDNet loss with its gradient, and the
+// fused Adam step (BatchNorm/ReLU/max-pool backward: bn_bwd.hip).  Everything reduces through per-block partials that are
 // summed in a fixed order, so a training step is bit-reproducible.
 //
 // Replaces, in the reference's train_util_dam.py:
 //   loss terms :167-276 with loss.py:131-260 (dice / weighted cyclic dice), nn.NLLLoss(reduction='none') x weight map,
 //   nn.MSELoss; loss.backward() :307 (non-convolution parts); optimizer.step() :308 with utils.py:915-918 (Adam).
-#include "common.h"
-#include "xform.h"
+#include "train_util.h"
 
 using namespace cdnet;
 
 namespace {
 
-__device__ __forceinline__ float bf2f(unsigned short u) { return __uint_as_float((unsigned)u << 16); }
-__device__ __forceinline__ unsigned short f2bf(float f) {
-    __bf16 b = (__bf16)f;
-    return __builtin_bit_cast(unsigned short, b);
-}
-__device__ __forceinline__ float h2f(unsigned short u) { return (float)__builtin_bit_cast(_Float16, u); }
-__device__ __forceinline__ float ld16(unsigned short u, bool f16) { return f16 ? h2f(u) : bf2f(u); }
-
-union V16 {
-    uint4 u;
-    unsigned short h[8];
-};
-
 inline int lin_grid(size_t total, int cap = 2048) {
     size_t g = (total + 255) / 256;
     return (int)(g > (size_t)cap ? cap : (g < 1 ? 1 : g));
-}
-
-// out[k] = sum_b partial[b][k]: one wave per output, lanes stride over b, fixed butterfly -> deterministic
-// first pixel (or pool window) of a thread in the "VPP threads per pixel, 256 / VPP pixels per block" layouts below; when VPP does
-// not divide 256 (HRNet's 48 / 80 / 144 channels) the left-over threads of the block sit the loop out
-__device__ __forceinline__ unsigned first_pixel(unsigned ppb, int VPP) {
-    return (int)threadIdx.x < (int)ppb * VPP ? blockIdx.x * ppb + threadIdx.x / VPP : 0xffffffffu;
-}
-
-__global__ __launch_bounds__(256) void reduce_partials_kernel(const float *__restrict__ partial, int nb, int K, float *__restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    const int k = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (k >= K) return;
-    float s = 0.f;
-    for (int b = lane; b < nb; b += 64) s += partial[(size_t)b * K + k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) out[k] = s;
-}
-
-// ======================================================================================================
-// BatchNorm + ReLU (+ residual) (+ consumers' max-pool / F.pad) backward
-// ======================================================================================================
-struct GradIn {
-    const unsigned short *g;     // bf16 NHWC [N][Hg][Wg][C]: gradient w.r.t. this tensor as seen by one consumer
-    int Hg, Wg;
-    int oy, ox;                  // consumer read (y - oy, x - ox) of this tensor  => gradient sits at (y + oy, x + ox)
-    int pooled;                  // consumer read maxpool2x2 of this tensor (1 floor / 2 ceil): route to the argmax
-    int coff, cstride;           // channel slice of a wider gradient tensor
-};
-
-struct BnBwdArgs {
-    const unsigned short *raw;   // stored forward output [N][H][W][C]
-    const unsigned short *res;   // optional residual added before the ReLU
-    int f16;                     // storage format of raw/res
-    const float *scale, *shift;  // forward affine (NULL: identity)
-    int relu;
-    const float *mean, *invstd;  // saved batch statistics
-    GradIn gin[3];
-    int ngin;
-    int N, H, W, C;
-    float *partial;              // reduce: [nblocks][2][C]
-    const float *k1, *k2, *k3;   // apply: draw = k1*(dz - k2 - xhat*k3)
-    unsigned short *draw;        // bf16 [N][H][W][C]
-    unsigned short *dz_out;      // optional bf16 copy of dz (gradient of the residual branch)
-    int rev;                     // apply pass walks the tensor back to front (see cdnet_bn_backward)
-};
-
-__device__ __forceinline__ void ldf8(const void *base, size_t e, float *v) {
-    const float4 *p = reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(base) + e);
-    const float4 a = p[0], b = p[1];
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-__device__ __forceinline__ void stf8(void *base, size_t e, const float *v) {
-    float4 *p = reinterpret_cast<float4 *>(reinterpret_cast<float *>(base) + e);
-    p[0] = make_float4(v[0], v[1], v[2], v[3]);
-    p[1] = make_float4(v[4], v[5], v[6], v[7]);
-}
-
-// fp32 tensors (f16 == 2): the activated value in plain fp32 arithmetic; relu == 2: `res` is the stored post-ReLU output of the
-// unit (fused residual epilogue) and the mask is read from it
-__device__ __forceinline__ void act8_f32(const BnBwdArgs &A, size_t e, const float *sc, const float *sh, float *a, float *rawf) {
-    float x[8], r[8];
-    ldf8(A.raw, e, x);
-    if (A.res) ldf8(A.res, e, r);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        if (rawf) rawf[j] = x[j];
-        float v = A.scale ? fmaf(x[j], sc[j], sh[j]) : x[j];
-        if (A.relu == 2) v = r[j];
-        else {
-            if (A.res) v += r[j];
-            if (A.relu) v = fmaxf(v, 0.f);
-        }
-        a[j] = v;
-    }
-}
-
-// activated value (rounded to bf16 like the forward staging does) of 8 channels at one pixel
-template <bool F32 = false>
-__device__ __forceinline__ void act8(const BnBwdArgs &A, size_t e, const float *sc, const float *sh, float *a, float *rawf) {
-    if (F32) { act8_f32(A, e, sc, sh, a, rawf); return; }
-    V16 r, rr;
-    r.u = *reinterpret_cast<const uint4 *>(A.raw + e);
-    rr.u = make_uint4(0, 0, 0, 0);
-    if (A.res) rr.u = *reinterpret_cast<const uint4 *>(A.res + e);
-    const bool f16 = A.f16 != 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        float x = ld16(r.h[j], f16);
-        if (rawf) rawf[j] = x;
-        float v = A.scale ? fmaf(x, sc[j], sh[j]) : x;
-        if (A.res) v += ld16(rr.h[j], f16);
-        if (A.relu) v = fmaxf(v, 0.f);
-        a[j] = bf2f(f2bf(v));
-    }
-}
-
-// dz for 8 channels of pixel (n,y,x); also returns xhat
-template <bool WANT_XHAT, bool F32 = false>
-__device__ __forceinline__ void dz8(const BnBwdArgs &A, int n, int y, int x, int c0, const float *sc, const float *sh,
-                                    const float *mu, const float *is, float *dz, float *xhat) {
-    const size_t e = (((size_t)n * A.H + y) * A.W + x) * A.C + c0;
-    float a[8], rawf[8];
-    act8<F32>(A, e, sc, sh, a, rawf);
-    float g[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) g[j] = 0.f;
-    for (int k = 0; k < A.ngin; ++k) {
-        const GradIn &gi = A.gin[k];
-        if (!gi.pooled) {
-            const int yy = y + gi.oy, xx = x + gi.ox;
-            if (yy >= 0 && yy < gi.Hg && xx >= 0 && xx < gi.Wg) {
-                const size_t ge = (((size_t)n * gi.Hg + yy) * gi.Wg + xx) * gi.cstride + gi.coff + c0;
-                if (F32) {
-                    float t[8];
-                    ldf8(gi.g, ge, t);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) g[j] += t[j];
-                } else {
-                    V16 v;
-                    v.u = *reinterpret_cast<const uint4 *>(gi.g + ge);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) g[j] += bf2f(v.h[j]);
-                }
-            }
-        } else {
-            const int py = y >> 1, px = x >> 1;
-            if (py < gi.Hg && px < gi.Wg) {
-                // is (y,x) the first maximum of its 2x2 window?  (nn.MaxPool2d backward)
-                bool sel[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) sel[j] = true;
-                const int q0 = (y & 1) * 2 + (x & 1);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    if (q == q0) continue;
-                    const int yy = (y & ~1) + (q >> 1), xx = (x & ~1) + (q & 1);
-                    if (yy >= A.H || xx >= A.W) continue;
-                    float b[8];
-                    act8<F32>(A, (((size_t)n * A.H + yy) * A.W + xx) * A.C + c0, sc, sh, b, nullptr);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) sel[j] = sel[j] && (q < q0 ? a[j] > b[j] : a[j] >= b[j]);
-                }
-                const size_t ge = (((size_t)n * gi.Hg + py) * gi.Wg + px) * gi.cstride + gi.coff + c0;
-                if (F32) {
-                    float t[8];
-                    ldf8(gi.g, ge, t);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) g[j] += sel[j] ? t[j] : 0.f;
-                } else {
-                    V16 v;
-                    v.u = *reinterpret_cast<const uint4 *>(gi.g + ge);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) g[j] += sel[j] ? bf2f(v.h[j]) : 0.f;
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        dz[j] = (A.relu && !(a[j] > 0.f)) ? 0.f : g[j];
-        if (WANT_XHAT) xhat[j] = A.mean ? (rawf[j] - mu[j]) * is[j] : 0.f;
-    }
-}
-
-__device__ __forceinline__ void load8(const float *p, int c0, float *o, float dflt) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = p ? p[c0 + j] : dflt;
-}
-
-// Both passes are pure streaming (HBM bound): every thread keeps BN_U independent pixels in flight per iteration.
-constexpr int BN_U = 4;
-constexpr int BN_MAX_BLOCKS = 2048;      // workspace rows
-// blocks actually launched by the streaming passes: two 256-thread workgroups per CU keep 64-98 KB of loads in flight per CU, and the
-// finalize pass (one workgroup per channel walking the partial rows with a 2 * C stride) has a quarter of the rows to sum - measured
-// (bench.py, 16 tiles): 2048 blocks 1 641 tiles/s, 1024 1 645-1 655, 768 1 652-1 655, 512 1 654-1 663, 256 1 605-1 609
-static int bn_blocks_cap() {
-    return 512 > BN_MAX_BLOCKS ? BN_MAX_BLOCKS : 512;
-}
-
-template <bool F32 = false>
-__device__ __forceinline__ void dz8_at(const BnBwdArgs &A, unsigned p, unsigned HW, int c0, const float *sc, const float *sh, const float *mu,
-                                       const float *is, float *dz, float *xh) {
-    const unsigned n = p / HW, r = p - n * HW;
-    const unsigned y = r / (unsigned)A.W, x = r - y * (unsigned)A.W;
-    dz8<true, F32>(A, (int)n, (int)y, (int)x, c0, sc, sh, mu, is, dz, xh);
-}
-
-// The storage format of the raw tensor (fp16 / bf16) and the ReLU mode (0 none, 1 mask from the recomputed activation, 2 mask from the
-// stored output in `res`) are wave-uniform run-time fields: the pixel loop is instantiated per combination and chosen once at the top
-// (tested per element they cost a scalar branch + an exec-mask save around every dz: ~25 instructions per element, the reduce pass ran at
-// 3.9 TB/s beside the apply pass's 5.1).
-template <typename Body>
-__device__ __forceinline__ void bn_bwd_dispatch(bool f16, int relu, Body &&body) {
-    using T_ = std::true_type;
-    using F_ = std::false_type;
-    if (f16) {
-        if (relu == 0) body(T_{}, std::integral_constant<int, 0>{});
-        else if (relu == 1) body(T_{}, std::integral_constant<int, 1>{});
-        else body(T_{}, std::integral_constant<int, 2>{});
-    } else {
-        if (relu == 0) body(F_{}, std::integral_constant<int, 0>{});
-        else if (relu == 1) body(F_{}, std::integral_constant<int, 1>{});
-        else body(F_{}, std::integral_constant<int, 2>{});
-    }
-}
-
-// Window kernels: the layer's consumers are one 2x2 max-pool plus NF same-size un-shifted tensors (the skip connection).
-// One pooling window per thread: the four activations are read once, the pooled gradient goes to the first maximum
-// (nn.MaxPool2d backward).  All loads are unconditional (clamped coordinates) and issued before any arithmetic.
-template <int NF, bool APPLY>
-__global__ __launch_bounds__(256) void bn_bwd_window_kernel(BnBwdArgs A, int kp) {
-    __shared__ float s_red[APPLY ? 1 : 256][17];
-    const int VPP = A.C / 8;
-    const int tid = threadIdx.x;
-    const int slot = tid % VPP, c0 = slot * 8;
-    float sc[8], sh[8], mu[8], is[8], k1[8], k2[8], k3[8], s1[8], s2[8];
-    load8(A.scale, c0, sc, 1.f); load8(A.shift, c0, sh, 0.f); load8(A.mean, c0, mu, 0.f); load8(A.invstd, c0, is, 1.f);
-    if (APPLY) { load8(A.k1, c0, k1, 1.f); load8(A.k2, c0, k2, 0.f); load8(A.k3, c0, k3, 0.f); }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
-    const unsigned H = A.H, W = A.W, Hp = (H + 1) / 2, Wp = (W + 1) / 2, nwin = (unsigned)A.N * Hp * Wp;
-    const unsigned ppb = 256 / VPP;
-    const GradIn gp = A.gin[kp];
-    int kf[2] = {0, 0};
-    {
-        int m = 0;
-        for (int k = 0; k < A.ngin && m < NF; ++k)
-            if (k != kp) kf[m++] = k;
-    }
-    bn_bwd_dispatch(A.f16 != 0, A.relu != 0 ? 1 : 0, [&](auto f16_c, auto relu_c) {
-    constexpr bool f16 = decltype(f16_c)::value, relu = decltype(relu_c)::value != 0;
-    for (unsigned w0 = first_pixel(ppb, VPP); w0 < nwin; w0 += gridDim.x * ppb) {
-        const unsigned w = (APPLY && A.rev) ? nwin - 1 - w0 : w0;
-        const unsigned n = w / (Hp * Wp), r = w - n * Hp * Wp;
-        const unsigned py = r / Wp, px = r - py * Wp;
-        V16 raw[4], g[4][NF > 0 ? NF : 1], gv;
-        unsigned pix[4];
-        bool ok[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            unsigned yy = 2 * py + (q >> 1), xx = 2 * px + (q & 1);
-            ok[q] = yy < H && xx < W;
-            yy = yy < H ? yy : H - 1;
-            xx = xx < W ? xx : W - 1;
-            pix[q] = (n * H + yy) * W + xx;
-            raw[q].u = *reinterpret_cast<const uint4 *>(A.raw + (size_t)pix[q] * A.C + c0);
-#pragma unroll
-            for (int m = 0; m < NF; ++m)
-                g[q][m].u = *reinterpret_cast<const uint4 *>(A.gin[kf[m]].g + (size_t)pix[q] * A.gin[kf[m]].cstride + A.gin[kf[m]].coff + c0);
-        }
-        const bool pok = py < (unsigned)gp.Hg && px < (unsigned)gp.Wg;
-        {
-            const unsigned cy = pok ? py : 0, cx = pok ? px : 0;
-            gv.u = *reinterpret_cast<const uint4 *>(gp.g + (((size_t)n * gp.Hg + cy) * gp.Wg + cx) * gp.cstride + gp.coff + c0);
-        }
-        V16 o[4];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float x[4], a[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                x[q] = ld16(raw[q].h[j], f16);
-                float v = fmaf(x[q], sc[j], sh[j]);
-                if (relu) v = fmaxf(v, 0.f);
-                a[q] = bf2f(f2bf(v));
-            }
-            int bi = 0;
-            float best = a[0];
-#pragma unroll
-            for (int q = 1; q < 4; ++q)
-                if (ok[q] && a[q] > best) { best = a[q]; bi = q; }
-            const float gpool = pok ? bf2f(gv.h[j]) : 0.f;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float gs = (bi == q) ? gpool : 0.f;
-#pragma unroll
-                for (int m = 0; m < NF; ++m) gs += bf2f(g[q][m].h[j]);
-                const float dz = (!ok[q] || (relu && !(a[q] > 0.f))) ? 0.f : gs;
-                const float xh = (x[q] - mu[j]) * is[j];
-                if (APPLY) o[q].h[j] = f2bf(k1[j] * (dz - k2[j] - xh * k3[j]));
-                else { s1[j] += dz; s2[j] = fmaf(dz, xh, s2[j]); }
-            }
-        }
-        if (APPLY) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (ok[q]) *reinterpret_cast<uint4 *>(A.draw + (size_t)pix[q] * A.C + c0) = o[q].u;
-        }
-    }
-    });
-    if (!APPLY) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { s_red[tid][j] = s1[j]; s_red[tid][8 + j] = s2[j]; }
-        __syncthreads();
-        for (int q = tid; q < 16 * VPP; q += 256) {
-            const int sl = q % VPP, j = q / VPP;
-            float t = 0.f;
-            for (int k = sl; k < 256; k += VPP) t += s_red[k][j];
-            float *op = A.partial + (size_t)blockIdx.x * 2 * A.C;
-            op[(j >> 3) * A.C + sl * 8 + (j & 7)] = t;
-        }
-    }
-}
-
-// Flat kernels: every gradient source is a same-size un-shifted tensor, so dz needs only the pixel index.  Loads of BN_U
-// pixels are issued back to back (clamped index, no branch), then each pixel is folded into the sums / written out.
-template <int NG, bool RES>
-__global__ __launch_bounds__(256) void bn_bwd_reduce_flat_kernel(BnBwdArgs A) {
-    __shared__ float s_red[256][17];
-    const int VPP = A.C / 8;
-    const int tid = threadIdx.x;
-    const int slot = tid % VPP, c0 = slot * 8;
-    float sc[8], sh[8], mu[8], is[8];
-    load8(A.scale, c0, sc, 1.f); load8(A.shift, c0, sh, 0.f); load8(A.mean, c0, mu, 0.f); load8(A.invstd, c0, is, 1.f);
-    float s1[8], s2[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
-    const unsigned npix = (unsigned)(A.N * A.H * A.W);
-    const unsigned ppb = 256 / VPP, step = gridDim.x * ppb;
-    bn_bwd_dispatch(A.f16 != 0, A.relu, [&](auto f16_c, auto relu_c) {
-        constexpr bool F16 = decltype(f16_c)::value;
-        constexpr int RELU = decltype(relu_c)::value;
-        for (unsigned p0 = first_pixel(ppb, VPP); p0 < npix; p0 += step * BN_U) {
-            V16 raw[BN_U], res[BN_U], g[BN_U][NG];
-#pragma unroll
-            for (int u = 0; u < BN_U; ++u) {
-                unsigned p = p0 + u * step;
-                p = p < npix ? p : npix - 1;
-                raw[u].u = *reinterpret_cast<const uint4 *>(A.raw + (size_t)p * A.C + c0);
-                if (RES) res[u].u = *reinterpret_cast<const uint4 *>(A.res + (size_t)p * A.C + c0);
-#pragma unroll
-                for (int k = 0; k < NG; ++k)
-                    g[u][k].u = *reinterpret_cast<const uint4 *>(A.gin[k].g + (size_t)p * A.gin[k].cstride + A.gin[k].coff + c0);
-            }
-#pragma unroll
-            for (int u = 0; u < BN_U; ++u) {
-                const bool valid = p0 + u * step < npix;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float x = ld16(raw[u].h[j], F16);
-                    float v = fmaf(x, sc[j], sh[j]);
-                    if (RES) v = RELU == 2 ? bf2f(res[u].h[j]) : v + ld16(res[u].h[j], F16);     // RELU 2: res IS the stored output
-                    float gs = bf2f(g[u][0].h[j]);
-#pragma unroll
-                    for (int k = 1; k < NG; ++k) gs += bf2f(g[u][k].h[j]);
-                    // the forward rounds the activation to bf16 before the ReLU; rounding keeps the sign
-                    const bool keep = valid & (RELU == 0 || bf2f(f2bf(v)) > 0.f);
-                    const float dz = keep ? gs : 0.f;
-                    s1[j] += dz;
-                    s2[j] = fmaf(dz, (x - mu[j]) * is[j], s2[j]);
-                    if (RES) res[u].h[j] = f2bf(dz);                             // (the register is free: dz for the store below)
-                }
-                // a residual unit's bn2: dz is the 1x1 branch's gradient and is stored anyway - by this pass, so that the second pass reads
-                // one tensor instead of the NG gradient sources and the mask again (cdnet_bn_backward; it then sees dz rounded to bf16)
-                if (RES && A.dz_out && valid) *reinterpret_cast<uint4 *>(A.dz_out + (size_t)(p0 + u * step) * A.C + c0) = res[u].u;
-            }
-        }
-    });
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { s_red[tid][j] = s1[j]; s_red[tid][8 + j] = s2[j]; }
-    __syncthreads();
-    for (int q = tid; q < 16 * VPP; q += 256) {
-        const int sl = q % VPP, j = q / VPP;
-        float t = 0.f;
-        for (int k = sl; k < 256; k += VPP) t += s_red[k][j];
-        float *o = A.partial + (size_t)blockIdx.x * 2 * A.C;
-        o[(j >> 3) * A.C + sl * 8 + (j & 7)] = t;
-    }
-}
-
-template <int NG, bool RES>
-__global__ __launch_bounds__(256) void bn_bwd_apply_flat_kernel(BnBwdArgs A) {
-    const int VPP = A.C / 8;
-    const int tid = threadIdx.x;
-    const int slot = tid % VPP, c0 = slot * 8;
-    float sc[8], sh[8], mu[8], is[8], k1[8], k2[8], k3[8];
-    load8(A.scale, c0, sc, 1.f); load8(A.shift, c0, sh, 0.f); load8(A.mean, c0, mu, 0.f); load8(A.invstd, c0, is, 1.f);
-    load8(A.k1, c0, k1, 1.f); load8(A.k2, c0, k2, 0.f); load8(A.k3, c0, k3, 0.f);
-    const unsigned npix = (unsigned)(A.N * A.H * A.W);
-    const unsigned ppb = 256 / VPP, step = gridDim.x * ppb;
-    const bool rev = A.rev != 0;
-    bn_bwd_dispatch(A.f16 != 0, A.relu, [&](auto f16_c, auto relu_c) {
-        constexpr bool F16 = decltype(f16_c)::value;
-        constexpr int RELU = decltype(relu_c)::value;
-        for (unsigned p0 = first_pixel(ppb, VPP); p0 < npix; p0 += step * BN_U) {
-            V16 raw[BN_U], res[BN_U], g[BN_U][NG];
-#pragma unroll
-            for (int u = 0; u < BN_U; ++u) {
-                unsigned p = p0 + u * step;
-                p = p < npix ? p : npix - 1;
-                p = rev ? npix - 1 - p : p;
-                raw[u].u = *reinterpret_cast<const uint4 *>(A.raw + (size_t)p * A.C + c0);
-                if (RES) res[u].u = *reinterpret_cast<const uint4 *>(A.res + (size_t)p * A.C + c0);
-#pragma unroll
-                for (int k = 0; k < NG; ++k)
-                    g[u][k].u = *reinterpret_cast<const uint4 *>(A.gin[k].g + (size_t)p * A.gin[k].cstride + A.gin[k].coff + c0);
-            }
-#pragma unroll
-            for (int u = 0; u < BN_U; ++u) {
-                const unsigned p = p0 + u * step;
-                V16 o, z;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float x = ld16(raw[u].h[j], F16);
-                    float v = fmaf(x, sc[j], sh[j]);
-                    if (RES) v = RELU == 2 ? bf2f(res[u].h[j]) : v + ld16(res[u].h[j], F16);
-                    float gs = bf2f(g[u][0].h[j]);
-#pragma unroll
-                    for (int k = 1; k < NG; ++k) gs += bf2f(g[u][k].h[j]);
-                    const bool keep = RELU == 0 || bf2f(f2bf(v)) > 0.f;
-                    const float dz = keep ? gs : 0.f;
-                    o.h[j] = f2bf(k1[j] * (dz - k2[j] - (x - mu[j]) * is[j] * k3[j]));
-                    z.h[j] = f2bf(dz);
-                }
-                if (p < npix) {
-                    const unsigned pw = rev ? npix - 1 - p : p;
-                    *reinterpret_cast<uint4 *>(A.draw + (size_t)pw * A.C + c0) = o.u;
-                    if (RES) *reinterpret_cast<uint4 *>(A.dz_out + (size_t)pw * A.C + c0) = z.u;
-                }
-            }
-        }
-    });
-}
-
-// fp32 variants of the flat kernels: 4 channels per thread (one float4 per tensor and pixel), BN_U pixels in flight, plain
-// fp32 arithmetic (no 16-bit rounding of the activation); relu == 2 reads the mask from the stored output in `res`.
-typedef float bn_f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void load4(const float *p, int c0, float *o, float dflt) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = p ? p[c0 + j] : dflt;
-}
-
-template <int NG, bool RES, bool APPLY>
-__global__ __launch_bounds__(256) void bn_bwd_flat32_kernel(BnBwdArgs A) {
-    __shared__ float s_red[APPLY ? 1 : 256][9];
-    const int VPP = A.C / 4;
-    const int tid = threadIdx.x;
-    const int slot = tid % VPP, c0 = slot * 4;
-    float sc[4], sh[4], mu[4], is[4], k1[4], k2[4], k3[4], s1[4], s2[4];
-    load4(A.scale, c0, sc, 1.f); load4(A.shift, c0, sh, 0.f); load4(A.mean, c0, mu, 0.f); load4(A.invstd, c0, is, 1.f);
-    if (APPLY) { load4(A.k1, c0, k1, 1.f); load4(A.k2, c0, k2, 0.f); load4(A.k3, c0, k3, 0.f); }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
-    const unsigned npix = (unsigned)(A.N * A.H * A.W);
-    const unsigned ppb = 256 / VPP, step = gridDim.x * ppb;
-    const bool relu = A.relu != 0, outmask = A.relu == 2;
-    const float *raw = reinterpret_cast<const float *>(A.raw), *resp = reinterpret_cast<const float *>(A.res);
-    float *draw = reinterpret_cast<float *>(A.draw), *dzo = reinterpret_cast<float *>(A.dz_out);
-    for (unsigned p0 = first_pixel(ppb, VPP); p0 < npix; p0 += step * BN_U) {
-        bn_f32x4 x[BN_U], r[BN_U], g[BN_U][NG];
-#pragma unroll
-        for (int u = 0; u < BN_U; ++u) {
-            unsigned p = p0 + u * step;
-            p = p < npix ? p : npix - 1;
-            if (APPLY && A.rev) p = npix - 1 - p;
-            x[u] = *reinterpret_cast<const bn_f32x4 *>(raw + (size_t)p * A.C + c0);
-            if (RES) r[u] = *reinterpret_cast<const bn_f32x4 *>(resp + (size_t)p * A.C + c0);
-#pragma unroll
-            for (int k = 0; k < NG; ++k)
-                g[u][k] = *reinterpret_cast<const bn_f32x4 *>(reinterpret_cast<const float *>(A.gin[k].g) + (size_t)p * A.gin[k].cstride + A.gin[k].coff + c0);
-        }
-#pragma unroll
-        for (int u = 0; u < BN_U; ++u) {
-            const unsigned p = p0 + u * step;
-            const bool valid = p < npix;
-            bn_f32x4 o, z;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float v = fmaf(x[u][j], sc[j], sh[j]);
-                if (RES) v = outmask ? r[u][j] : v + r[u][j];
-                float gs = g[u][0][j];
-#pragma unroll
-                for (int k = 1; k < NG; ++k) gs += g[u][k][j];
-                const float dz = (!valid || (relu && !(v > 0.f))) ? 0.f : gs;
-                const float xh = (x[u][j] - mu[j]) * is[j];
-                if (APPLY) { o[j] = k1[j] * (dz - k2[j] - xh * k3[j]); z[j] = dz; }
-                else { s1[j] += dz; s2[j] = fmaf(dz, xh, s2[j]); z[j] = dz; }
-            }
-            if (APPLY && valid) {
-                const unsigned pw = A.rev ? npix - 1 - p : p;
-                *reinterpret_cast<bn_f32x4 *>(draw + (size_t)pw * A.C + c0) = o;
-                if (RES) *reinterpret_cast<bn_f32x4 *>(dzo + (size_t)pw * A.C + c0) = z;
-            }
-            // the sums pass of a residual unit's bn2 already leaves dz (the 1x1 branch's gradient): the second pass then reads one
-            // tensor instead of the NG gradient sources and the mask again (cdnet_bn_backward)
-            if (!APPLY && RES && dzo && valid) *reinterpret_cast<bn_f32x4 *>(dzo + (size_t)p * A.C + c0) = z;
-        }
-    }
-    if (!APPLY) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { s_red[tid][j] = s1[j]; s_red[tid][4 + j] = s2[j]; }
-        __syncthreads();
-        for (int q = tid; q < 8 * VPP; q += 256) {
-            const int sl = q % VPP, j = q / VPP;
-            float t = 0.f;
-            for (int k = sl; k < 256; k += VPP) t += s_red[k][j];
-            float *op = A.partial + (size_t)blockIdx.x * 2 * A.C;
-            op[(j >> 2) * A.C + sl * 4 + (j & 3)] = t;
-        }
-    }
-}
-
-template <bool APPLY>
-static void launch_flat32(const BnBwdArgs &A, int nb, hipStream_t st) {
-    switch (A.ngin * 2 + (A.res ? 1 : 0)) {
-        case 2: bn_bwd_flat32_kernel<1, false, APPLY><<<nb, 256, 0, st>>>(A); break;
-        case 3: bn_bwd_flat32_kernel<1, true, APPLY><<<nb, 256, 0, st>>>(A); break;
-        case 4: bn_bwd_flat32_kernel<2, false, APPLY><<<nb, 256, 0, st>>>(A); break;
-        case 5: bn_bwd_flat32_kernel<2, true, APPLY><<<nb, 256, 0, st>>>(A); break;
-        case 6: bn_bwd_flat32_kernel<3, false, APPLY><<<nb, 256, 0, st>>>(A); break;
-        default: bn_bwd_flat32_kernel<3, true, APPLY><<<nb, 256, 0, st>>>(A); break;
-    }
-}
-
-// fp32 variant of the window kernels (one 2x2 max-pool consumer + NF same-size un-shifted ones: the encoder's conv1_2 ... conv5_3):
-// one pooling window x 4 channels per thread, the four raw vectors, their flat gradients and the pooled gradient requested back to back,
-// plain fp32 arithmetic, the pooled gradient to the first maximum of relu(bn(raw)) (nn.MaxPool2d backward) - bit-identical to the
-// generic per-pixel path (bn_bwd_reduce_kernel / bn_bwd_apply_kernel<true>), which reads a window's raw vectors once per pixel.
-template <int NF, bool APPLY>
-__global__ __launch_bounds__(256) void bn_bwd_window32_kernel(BnBwdArgs A, int kp) {
-    __shared__ float s_red[APPLY ? 1 : 256][9];
-    const int VPP = A.C / 4;
-    const int tid = threadIdx.x;
-    const int slot = tid % VPP, c0 = slot * 4;
-    float sc[4], sh[4], mu[4], is[4], k1[4], k2[4], k3[4], s1[4], s2[4];
-    load4(A.scale, c0, sc, 1.f); load4(A.shift, c0, sh, 0.f); load4(A.mean, c0, mu, 0.f); load4(A.invstd, c0, is, 1.f);
-    if (APPLY) { load4(A.k1, c0, k1, 1.f); load4(A.k2, c0, k2, 0.f); load4(A.k3, c0, k3, 0.f); }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
-    const unsigned H = A.H, W = A.W, Hp = (H + 1) / 2, Wp = (W + 1) / 2, nwin = (unsigned)A.N * Hp * Wp;
-    const unsigned ppb = 256 / VPP;
-    const bool relu = A.relu != 0;
-    const GradIn gp = A.gin[kp];
-    const float *gpool_p = reinterpret_cast<const float *>(gp.g);
-    const float *raw = reinterpret_cast<const float *>(A.raw);
-    float *draw = reinterpret_cast<float *>(A.draw);
-    const float *gf[NF > 0 ? NF : 1];
-    int gcs[NF > 0 ? NF : 1], gco[NF > 0 ? NF : 1];
-    {
-        int m = 0;
-        for (int k = 0; k < A.ngin && m < NF; ++k)
-            if (k != kp) { gf[m] = reinterpret_cast<const float *>(A.gin[k].g); gcs[m] = A.gin[k].cstride; gco[m] = A.gin[k].coff; ++m; }
-    }
-    for (unsigned w0 = first_pixel(ppb, VPP); w0 < nwin; w0 += gridDim.x * ppb) {
-        const unsigned w = (APPLY && A.rev) ? nwin - 1 - w0 : w0;
-        const unsigned n = w / (Hp * Wp), r = w - n * Hp * Wp;
-        const unsigned py = r / Wp, px = r - py * Wp;
-        bn_f32x4 x[4], g[4][NF > 0 ? NF : 1], gv;
-        unsigned pix[4];
-        bool ok[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            unsigned yy = 2 * py + (q >> 1), xx = 2 * px + (q & 1);
-            ok[q] = yy < H && xx < W;
-            yy = yy < H ? yy : H - 1;
-            xx = xx < W ? xx : W - 1;
-            pix[q] = (n * H + yy) * W + xx;
-            x[q] = *reinterpret_cast<const bn_f32x4 *>(raw + (size_t)pix[q] * A.C + c0);
-#pragma unroll
-            for (int m = 0; m < NF; ++m)
-                g[q][m] = *reinterpret_cast<const bn_f32x4 *>(gf[m] + (size_t)pix[q] * gcs[m] + gco[m] + c0);
-        }
-        const bool pok = py < (unsigned)gp.Hg && px < (unsigned)gp.Wg;
-        {
-            const unsigned cy = pok ? py : 0, cx = pok ? px : 0;
-            gv = *reinterpret_cast<const bn_f32x4 *>(gpool_p + (((size_t)n * gp.Hg + cy) * gp.Wg + cx) * gp.cstride + gp.coff + c0);
-        }
-        bn_f32x4 o[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float a[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float v = fmaf(x[q][j], sc[j], sh[j]);
-                a[q] = relu ? fmaxf(v, 0.f) : v;
-            }
-            int bi = 0;
-            float best = a[0];
-#pragma unroll
-            for (int q = 1; q < 4; ++q)
-                if (ok[q] && a[q] > best) { best = a[q]; bi = q; }
-            const float gpool = pok ? gv[j] : 0.f;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                // the generic path's order: 0 + the sources in argument order (kp = the pooled one's position)
-                const float pt = (bi == q) ? gpool : 0.f;
-                float gsum;
-                if (NF == 0) gsum = 0.f + pt;
-                else if (NF == 1) gsum = (0.f + (kp == 0 ? pt : g[q][0][j])) + (kp == 0 ? g[q][0][j] : pt);
-                else gsum = ((0.f + (kp == 0 ? pt : g[q][0][j])) + (kp == 0 ? g[q][0][j] : (kp == 1 ? pt : g[q][NF - 1][j]))) +
-                            (kp == 2 ? pt : g[q][NF - 1][j]);
-                const float dz = (!ok[q] || (relu && !(a[q] > 0.f))) ? 0.f : gsum;
-                const float xh = (x[q][j] - mu[j]) * is[j];
-                if (APPLY) o[q][j] = k1[j] * (dz - k2[j] - xh * k3[j]);
-                else { s1[j] += dz; s2[j] = fmaf(dz, xh, s2[j]); }
-            }
-        }
-        if (APPLY) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (ok[q]) *reinterpret_cast<bn_f32x4 *>(draw + (size_t)pix[q] * A.C + c0) = o[q];
-        }
-    }
-    if (!APPLY) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { s_red[tid][j] = s1[j]; s_red[tid][4 + j] = s2[j]; }
-        __syncthreads();
-        for (int q = tid; q < 8 * VPP; q += 256) {
-            const int sl = q % VPP, j = q / VPP;
-            float t = 0.f;
-            for (int k = sl; k < 256; k += VPP) t += s_red[k][j];
-            float *op = A.partial + (size_t)blockIdx.x * 2 * A.C;
-            op[(j >> 2) * A.C + sl * 4 + (j & 3)] = t;
-        }
-    }
-}
-
-template <bool APPLY>
-static void launch_window32(const BnBwdArgs &A, int nflat, int kp, int nb, hipStream_t st) {
-    if (nflat == 0) bn_bwd_window32_kernel<0, APPLY><<<nb, 256, 0, st>>>(A, kp);
-    else if (nflat == 1) bn_bwd_window32_kernel<1, APPLY><<<nb, 256, 0, st>>>(A, kp);
-    else bn_bwd_window32_kernel<2, APPLY><<<nb, 256, 0, st>>>(A, kp);
-}
-
-template <bool F32>
-__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(BnBwdArgs A) {
-    __shared__ float s_red[256][17];
-    const int VPP = A.C / 8;
-    const int tid = threadIdx.x;
-    const int slot = tid % VPP, c0 = slot * 8;
-    float sc[8], sh[8], mu[8], is[8];
-    load8(A.scale, c0, sc, 1.f); load8(A.shift, c0, sh, 0.f); load8(A.mean, c0, mu, 0.f); load8(A.invstd, c0, is, 1.f);
-    float s1[8], s2[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
-    const unsigned HW = (unsigned)(A.H * A.W), npix = (unsigned)A.N * HW;
-    const unsigned ppb = 256 / VPP;                                 // pixels per block per sub-iteration
-    const unsigned step = gridDim.x * ppb;
-    for (unsigned p0 = first_pixel(ppb, VPP); p0 < npix; p0 += step * BN_U) {
-        float dz[BN_U][8], xh[BN_U][8];
-#pragma unroll
-        for (int u = 0; u < BN_U; ++u) {
-            const unsigned p = p0 + u * step;
-            if (p < npix) dz8_at<F32>(A, p, HW, c0, sc, sh, mu, is, dz[u], xh[u]);
-            else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) { dz[u][j] = 0.f; xh[u][j] = 0.f; }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < BN_U; ++u)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { s1[j] += dz[u][j]; s2[j] = fmaf(dz[u][j], xh[u][j], s2[j]); }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { s_red[tid][j] = s1[j]; s_red[tid][8 + j] = s2[j]; }
-    __syncthreads();
-    // threads with the same slot: tid, tid+VPP, ...  -> fixed-order sum; 16 values x VPP slots spread over the block
-    for (int q = tid; q < 16 * VPP; q += 256) {
-        const int sl = q % VPP, j = q / VPP;
-        float t = 0.f;
-        for (int k = sl; k < 256; k += VPP) t += s_red[k][j];
-        float *o = A.partial + (size_t)blockIdx.x * 2 * A.C;
-        o[(j >> 3) * A.C + sl * 8 + (j & 7)] = t;
-    }
-}
-
-// sums [nb][2][C] -> dgamma, dbeta and the apply coefficients; one workgroup per channel, fixed LDS tree (deterministic)
-__global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float *__restrict__ partial, int nb, int C, float M, const float *gamma,
-                                                              const float *invstd, float *dgamma, float *dbeta, float *k1, float *k2,
-                                                              float *k3) {
-    __shared__ double s_a[256], s_b[256];
-    const int c = blockIdx.x;
-    const int lane = threadIdx.x;
-    double s1 = 0.0, s2 = 0.0;
-    for (int b = lane; b < nb; b += 256) { s1 += (double)partial[((size_t)b * 2) * C + c]; s2 += (double)partial[((size_t)b * 2 + 1) * C + c]; }
-    s_a[lane] = s1; s_b[lane] = s2;
-    __syncthreads();
-#pragma unroll
-    for (int o = 128; o > 0; o >>= 1) {
-        if (lane < o) { s_a[lane] += s_a[lane + o]; s_b[lane] += s_b[lane + o]; }
-        __syncthreads();
-    }
-    s1 = s_a[0]; s2 = s_b[0];
-    if (lane == 0) {
-        if (dbeta) dbeta[c] = (float)s1;
-        if (dgamma) dgamma[c] = (float)s2;
-        k1[c] = gamma[c] * invstd[c];
-        k2[c] = (float)(s1 / M);
-        k3[c] = (float)(s2 / M);
-    }
-}
-
-template <bool F32>
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(BnBwdArgs A) {
-    const int VPP = A.C / 8;
-    const int tid = threadIdx.x;
-    const int slot = tid % VPP, c0 = slot * 8;
-    float sc[8], sh[8], mu[8], is[8], k1[8], k2[8], k3[8];
-    load8(A.scale, c0, sc, 1.f); load8(A.shift, c0, sh, 0.f); load8(A.mean, c0, mu, 0.f); load8(A.invstd, c0, is, 1.f);
-    load8(A.k1, c0, k1, 1.f); load8(A.k2, c0, k2, 0.f); load8(A.k3, c0, k3, 0.f);
-    const unsigned HW = (unsigned)(A.H * A.W), npix = (unsigned)A.N * HW;
-    const unsigned ppb = 256 / VPP;
-    const unsigned step = gridDim.x * ppb;
-    for (unsigned p0 = first_pixel(ppb, VPP); p0 < npix; p0 += step * BN_U) {
-        float dz[BN_U][8], xh[BN_U][8];
-#pragma unroll
-        for (int u = 0; u < BN_U; ++u) {
-            const unsigned p = p0 + u * step;
-            if (p < npix) dz8_at<F32>(A, p, HW, c0, sc, sh, mu, is, dz[u], xh[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < BN_U; ++u) {
-            const unsigned p = p0 + u * step;
-            if (p >= npix) continue;
-            if (F32) {
-                float o32[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) o32[j] = k1[j] * (dz[u][j] - k2[j] - xh[u][j] * k3[j]);
-                if (A.draw) stf8(A.draw, (size_t)p * A.C + c0, o32);
-                if (A.dz_out) stf8(A.dz_out, (size_t)p * A.C + c0, dz[u]);
-                continue;
-            }
-            V16 o, z;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                o.h[j] = f2bf(k1[j] * (dz[u][j] - k2[j] - xh[u][j] * k3[j]));
-                z.h[j] = f2bf(dz[u][j]);
-            }
-            if (A.draw) *reinterpret_cast<uint4 *>(A.draw + (size_t)p * A.C + c0) = o.u;
-            if (A.dz_out) *reinterpret_cast<uint4 *>(A.dz_out + (size_t)p * A.C + c0) = z.u;
-        }
-    }
 }
 
 // ======================================================================================================
@@ -1973,216 +1223,6 @@ __global__ __launch_bounds__(256) void bias_grad_kernel(const unsigned short *__
 // ------------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------------
-static int fill_bn_args(const cdnet_bn_bwd_args *a, BnBwdArgs &A, const char *who) {
-    CDNET_REQUIRE(a && a->raw, "%s: null pointer", who);
-    CDNET_REQUIRE(a->C % 8 == 0 && a->C >= 8 && a->C <= 2048 , "%s: C=%d unsupported", who, a->C);
-    CDNET_REQUIRE(a->ngin >= 1 && a->ngin <= 3, "%s: ngin=%d", who, a->ngin);
-    A.raw = a->raw; A.res = a->res; A.f16 = a->f16; A.scale = a->scale; A.shift = a->shift; A.relu = a->relu;
-    A.mean = a->mean; A.invstd = a->invstd;
-    for (int k = 0; k < 3; ++k) {
-        A.gin[k].g = a->gin[k].g; A.gin[k].Hg = a->gin[k].Hg; A.gin[k].Wg = a->gin[k].Wg;
-        A.gin[k].oy = a->gin[k].oy; A.gin[k].ox = a->gin[k].ox; A.gin[k].pooled = a->gin[k].pooled;
-        A.gin[k].coff = a->gin[k].coff; A.gin[k].cstride = a->gin[k].cstride ? a->gin[k].cstride : a->C;
-        if (k < a->ngin) CDNET_REQUIRE(a->gin[k].g, "%s: null gradient input %d", who, k);
-    }
-    A.ngin = a->ngin; A.N = a->N; A.H = a->H; A.W = a->W; A.C = a->C;
-    A.partial = nullptr; A.k1 = A.k2 = A.k3 = nullptr; A.draw = nullptr; A.dz_out = nullptr;
-    return CDNET_OK;
-}
-
-extern "C" int cdnet_bn_backward(const cdnet_bn_bwd_args *a, const float *gamma, float *dgamma, float *dbeta, float *workspace,
-                                 size_t workspace_floats, uint16_t *draw, uint16_t *dz_out, void *stream) {
-    BnBwdArgs A;
-    int rc = fill_bn_args(a, A, "cdnet_bn_backward");
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t npix = (size_t)A.N * A.H * A.W;
-    CDNET_REQUIRE(npix * (size_t)A.C < ((size_t)1 << 32) && npix < ((size_t)1 << 31), "cdnet_bn_backward: tensor too large for 32-bit pixel indexing");
-    const int ppb = 256 / (A.C / 8);
-    int nb = (int)((npix + (size_t)ppb * BN_U - 1) / ((size_t)ppb * BN_U));
-    if (nb > bn_blocks_cap()) nb = bn_blocks_cap();
-    if (nb < 1) nb = 1;
-    bool simple = true, window = false;               // every gradient source a same-size, un-shifted tensor?
-    int npool = 0, kp = 0, nflat = 0;
-    for (int k = 0; k < A.ngin; ++k) {
-        const GradIn &g = A.gin[k];
-        const bool same = !g.pooled && g.oy == 0 && g.ox == 0 && g.Hg == A.H && g.Wg == A.W;
-        simple = simple && same;
-        if (g.pooled) { ++npool; kp = k; }
-        else if (same) ++nflat;
-    }
-    // window path: exactly one pooled consumer, every other one flat, a BatchNorm + ReLU layer without residual branch
-    window = npool == 1 && nflat == A.ngin - 1 && nflat <= 2 && A.mean && A.scale && !A.res && draw && !dz_out;
-    if (window) {
-        const size_t nwin = (size_t)A.N * ((A.H + 1) / 2) * ((A.W + 1) / 2);
-        nb = (int)((nwin + ppb - 1) / ppb);
-        if (nb > bn_blocks_cap()) nb = bn_blocks_cap();
-    }
-    A.draw = draw; A.dz_out = dz_out;
-    static const bool dz_reuse = !(getenv("CDNET_BN_DZ_REUSE") && atoi(getenv("CDNET_BN_DZ_REUSE")) == 0);
-    if (!dz_reuse) A.dz_out = nullptr;                // (the sums pass stores dz only when the second pass is going to read it)
-    // The apply pass re-reads what the reduce pass just streamed (raw + gradients, up to 2 x 134 MB against 256 MB of
-    // Infinity Cache): walking it back to front meets the most recently cached lines first instead of chasing the LRU tail.
-    A.rev = 1;
-    bool flat = !window && simple && A.mean && A.scale && draw && ((A.res != nullptr) == (dz_out != nullptr));
-    CDNET_REQUIRE(A.relu != 2 || (flat && A.res), "cdnet_bn_backward: relu = 2 (mask from the stored output) needs same-size gradient sources and res");
-    const bool f32 = A.f16 == 2;                      // fp32 tensors: flat32 kernels (same-size sources) or the generic ones (pool / pad routing)
-    const bool flat32 = f32 && flat && A.C <= 1024;
-    const bool window32 = f32 && window && A.C % 4 == 0 && A.C <= 1024 && A.shift && A.invstd;
-    if (window32) {
-        const int ppb4 = 256 / (A.C / 4);
-        const size_t nwin = (size_t)A.N * ((A.H + 1) / 2) * ((A.W + 1) / 2);
-        nb = (int)((nwin + ppb4 - 1) / ppb4);
-        if (nb > bn_blocks_cap()) nb = bn_blocks_cap();
-    }
-    if (f32) { window = false; flat = false; }
-    if (flat32) {
-        const int ppb4 = 256 / (A.C / 4);
-        nb = (int)((npix + (size_t)ppb4 * BN_U - 1) / ((size_t)ppb4 * BN_U));
-        if (nb > bn_blocks_cap()) nb = bn_blocks_cap();
-        if (nb < 1) nb = 1;
-    }
-    if (A.mean) {
-        CDNET_REQUIRE(gamma && A.invstd && workspace, "cdnet_bn_backward: BatchNorm layer needs gamma/invstd/workspace");
-        const size_t need = (size_t)nb * 2 * A.C + 3 * (size_t)A.C;
-        if (workspace_floats < need) { set_error("cdnet_bn_backward: workspace %zu < %zu floats", workspace_floats, need); return CDNET_E_WORKSPACE; }
-        A.partial = workspace;
-        float *k = workspace + (size_t)nb * 2 * A.C;
-        if (window) {
-            if (nflat == 0) bn_bwd_window_kernel<0, false><<<nb, 256, 0, st>>>(A, kp);
-            else if (nflat == 1) bn_bwd_window_kernel<1, false><<<nb, 256, 0, st>>>(A, kp);
-            else bn_bwd_window_kernel<2, false><<<nb, 256, 0, st>>>(A, kp);
-        } else if (flat) {
-            switch (A.ngin * 2 + (A.res ? 1 : 0)) {
-                case 2: bn_bwd_reduce_flat_kernel<1, false><<<nb, 256, 0, st>>>(A); break;
-                case 3: bn_bwd_reduce_flat_kernel<1, true><<<nb, 256, 0, st>>>(A); break;
-                case 4: bn_bwd_reduce_flat_kernel<2, false><<<nb, 256, 0, st>>>(A); break;
-                case 5: bn_bwd_reduce_flat_kernel<2, true><<<nb, 256, 0, st>>>(A); break;
-                case 6: bn_bwd_reduce_flat_kernel<3, false><<<nb, 256, 0, st>>>(A); break;
-                default: bn_bwd_reduce_flat_kernel<3, true><<<nb, 256, 0, st>>>(A); break;
-            }
-        } else if (window32) launch_window32<false>(A, nflat, kp, nb, st);
-        else if (flat32) launch_flat32<false>(A, nb, st);
-        else if (f32) bn_bwd_reduce_kernel<true><<<nb, 256, 0, st>>>(A);
-        else bn_bwd_reduce_kernel<false><<<nb, 256, 0, st>>>(A);
-        bn_bwd_finalize_kernel<<<A.C, 256, 0, st>>>(A.partial, nb, A.C, (float)npix, gamma, A.invstd, dgamma, dbeta, k,
-                                                              k + A.C, k + 2 * A.C);
-        A.k1 = k; A.k2 = k + A.C; A.k3 = k + 2 * A.C;
-    }
-    A.dz_out = dz_out;
-    if (window) {
-        if (nflat == 0) bn_bwd_window_kernel<0, true><<<nb, 256, 0, st>>>(A, kp);
-        else if (nflat == 1) bn_bwd_window_kernel<1, true><<<nb, 256, 0, st>>>(A, kp);
-        else bn_bwd_window_kernel<2, true><<<nb, 256, 0, st>>>(A, kp);
-    } else if (flat && dz_reuse && A.mean && A.res && dz_out) {
-        BnBwdArgs B = A;
-        B.ngin = 1;
-        B.gin[0].g = dz_out; B.gin[0].Hg = A.H; B.gin[0].Wg = A.W; B.gin[0].oy = 0; B.gin[0].ox = 0; B.gin[0].pooled = 0;
-        B.gin[0].coff = 0; B.gin[0].cstride = A.C;
-        B.res = nullptr; B.relu = 0; B.dz_out = nullptr;
-        bn_bwd_apply_flat_kernel<1, false><<<nb, 256, 0, st>>>(B);
-    } else if (flat) {
-        switch (A.ngin * 2 + (A.res ? 1 : 0)) {
-            case 2: bn_bwd_apply_flat_kernel<1, false><<<nb, 256, 0, st>>>(A); break;
-            case 3: bn_bwd_apply_flat_kernel<1, true><<<nb, 256, 0, st>>>(A); break;
-            case 4: bn_bwd_apply_flat_kernel<2, false><<<nb, 256, 0, st>>>(A); break;
-            case 5: bn_bwd_apply_flat_kernel<2, true><<<nb, 256, 0, st>>>(A); break;
-            case 6: bn_bwd_apply_flat_kernel<3, false><<<nb, 256, 0, st>>>(A); break;
-            default: bn_bwd_apply_flat_kernel<3, true><<<nb, 256, 0, st>>>(A); break;
-        }
-    } else if (window32) launch_window32<true>(A, nflat, kp, nb, st);
-    else if (flat32 && A.mean && A.res && dz_out && dz_reuse) {
-        // (the sums pass stored dz: one plain source, no mask, no second dz store - bit-identical, 9 instead of 12 tensor passes)
-        BnBwdArgs B = A;
-        B.ngin = 1;
-        B.gin[0].g = dz_out; B.gin[0].Hg = A.H; B.gin[0].Wg = A.W; B.gin[0].oy = 0; B.gin[0].ox = 0; B.gin[0].pooled = 0;
-        B.gin[0].coff = 0; B.gin[0].cstride = A.C;
-        B.res = nullptr; B.relu = 0; B.dz_out = nullptr;
-        launch_flat32<true>(B, nb, st);
-    } else if (flat32) launch_flat32<true>(A, nb, st);
-    else if (f32) bn_bwd_apply_kernel<true><<<nb, 256, 0, st>>>(A);
-    else bn_bwd_apply_kernel<false><<<nb, 256, 0, st>>>(A);
-    return check_launch("cdnet_bn_backward");
-}
-
-// The two passes of cdnet_bn_backward as separate calls, for the plain case (one same-size gradient source, BatchNorm + ReLU, no
-// residual, 16-bit tensors): `stats` = reduce + finalize and the [7][C] table scale | shift | mean | invstd | k1 | k2 | k3 that both
-// the apply pass and a fused consumer (cdnet_conv_src.relu = 3) read; `apply` = the second pass alone.  The trainer runs `stats`
-// on the main chain, backward-data with the fused source right behind it, and `apply` + the weight gradient on the side stream.
-// masked: the source may also be a gradient that already went through the ReLU (relu = 0: dz as a residual unit's sums pass stores it)
-static bool bn_plain_case(const BnBwdArgs &A, bool masked = false) {
-    const GradIn &g = A.gin[0];
-    return A.ngin == 1 && !g.pooled && g.oy == 0 && g.ox == 0 && g.Hg == A.H && g.Wg == A.W && A.mean && A.scale && A.shift && A.invstd && !A.res &&
-           (A.relu == 1 || (masked && A.relu == 0)) && (g.cstride == 0 || g.cstride == A.C) && g.coff == 0;
-}
-
-__global__ void bn_ktab_copy_kernel(const float *scale, const float *shift, const float *mean, const float *invstd, int C, float *ktab) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < C) { ktab[c] = scale[c]; ktab[C + c] = shift[c]; ktab[2 * C + c] = mean[c]; ktab[3 * C + c] = invstd[c]; }
-}
-
-extern "C" int cdnet_bn_backward_stats(const cdnet_bn_bwd_args *a, const float *gamma, float *dgamma, float *dbeta, float *workspace,
-                                       size_t workspace_floats, float *ktab, void *stream) {
-    BnBwdArgs A;
-    int rc = fill_bn_args(a, A, "cdnet_bn_backward_stats");
-    if (rc) return rc;
-    CDNET_REQUIRE(bn_plain_case(A) && A.f16 != 2 && gamma && workspace && ktab, "cdnet_bn_backward_stats: plain 16-bit case only (one same-size gradient, BatchNorm + ReLU, no residual)");
-    hipStream_t st = (hipStream_t)stream;
-    const size_t npix = (size_t)A.N * A.H * A.W;
-    CDNET_REQUIRE(npix * (size_t)A.C < ((size_t)1 << 32) && npix < ((size_t)1 << 31), "cdnet_bn_backward_stats: tensor too large for 32-bit pixel indexing");
-    const int ppb = 256 / (A.C / 8);
-    int nb = (int)((npix + (size_t)ppb * BN_U - 1) / ((size_t)ppb * BN_U));
-    if (nb > bn_blocks_cap()) nb = bn_blocks_cap();
-    if (nb < 1) nb = 1;
-    const size_t need = (size_t)nb * 2 * A.C;
-    if (workspace_floats < need) { set_error("cdnet_bn_backward_stats: workspace %zu < %zu floats", workspace_floats, need); return CDNET_E_WORKSPACE; }
-    A.partial = workspace;
-    A.draw = nullptr; A.dz_out = nullptr; A.rev = 0;
-    bn_ktab_copy_kernel<<<cdiv(A.C, 256), 256, 0, st>>>(A.scale, A.shift, A.mean, A.invstd, A.C, ktab);
-    bn_bwd_reduce_flat_kernel<1, false><<<nb, 256, 0, st>>>(A);
-    bn_bwd_finalize_kernel<<<A.C, 256, 0, st>>>(A.partial, nb, A.C, (float)npix, gamma, A.invstd, dgamma, dbeta, ktab + 4 * A.C, ktab + 5 * A.C,
-                                                 ktab + 6 * A.C);
-    return check_launch("cdnet_bn_backward_stats");
-}
-
-/* finalize pass alone over partial rows f32 [nb][2][C] that somebody else produced (the backward-data kernel with
- * cdnet_conv_args.ws = 2): dgamma, dbeta and rows 4..6 (k1 | k2 | k3) of ktab - all cdnet_bn_backward_apply reads; rows 0..3 are left
- * alone (their only reader, round 2's fused convolution source, is gone: nine copy launches per training step less) */
-extern "C" int cdnet_bn_backward_finalize(const cdnet_bn_bwd_args *a, const float *gamma, float *dgamma, float *dbeta, const float *partial,
-                                          int nb, float *ktab, void *stream) {
-    BnBwdArgs A;
-    int rc = fill_bn_args(a, A, "cdnet_bn_backward_finalize");
-    if (rc) return rc;
-    CDNET_REQUIRE(bn_plain_case(A) && gamma && partial && ktab && nb >= 1, "cdnet_bn_backward_finalize: plain case only");
-    hipStream_t st = (hipStream_t)stream;
-    const size_t npix = (size_t)A.N * A.H * A.W;
-    bn_bwd_finalize_kernel<<<A.C, 256, 0, st>>>(partial, nb, A.C, (float)npix, gamma, A.invstd, dgamma, dbeta, ktab + 4 * A.C, ktab + 5 * A.C,
-                                                 ktab + 6 * A.C);
-    return check_launch("cdnet_bn_backward_finalize");
-}
-
-extern "C" int cdnet_bn_backward_apply(const cdnet_bn_bwd_args *a, const float *ktab, uint16_t *draw, void *stream) {
-    BnBwdArgs A;
-    int rc = fill_bn_args(a, A, "cdnet_bn_backward_apply");
-    if (rc) return rc;
-    CDNET_REQUIRE(bn_plain_case(A, true) && ktab && draw, "cdnet_bn_backward_apply: plain case only");
-    const size_t npix = (size_t)A.N * A.H * A.W;
-    const bool f32 = A.f16 == 2;                                 // fp32 tensors (gradient, raw output, dRaw): the flat32 kernel
-    CDNET_REQUIRE(!f32 || A.C <= 1024, "cdnet_bn_backward_apply(f32): C=%d > 1024", A.C);
-    const int ppb = 256 / (A.C / (f32 ? 4 : 8));
-    int nb = (int)((npix + (size_t)ppb * BN_U - 1) / ((size_t)ppb * BN_U));
-    if (nb > bn_blocks_cap()) nb = bn_blocks_cap();
-    if (nb < 1) nb = 1;
-    A.rev = 1;
-    A.draw = draw; A.dz_out = nullptr;
-    A.k1 = const_cast<float *>(ktab) + 4 * A.C; A.k2 = const_cast<float *>(ktab) + 5 * A.C; A.k3 = const_cast<float *>(ktab) + 6 * A.C;
-    if (f32) launch_flat32<true>(A, nb, (hipStream_t)stream);
-    else bn_bwd_apply_flat_kernel<1, false><<<nb, 256, 0, (hipStream_t)stream>>>(A);
-    return check_launch("cdnet_bn_backward_apply");
-}
-
-extern "C" size_t cdnet_bn_backward_workspace_floats(int C) { return (size_t)BN_MAX_BLOCKS * 2 * C + 3 * (size_t)C; }
-
 static HeadFeat mk_hf(const cdnet_head_feat &f) {
     HeadFeat h;
     h.raw = f.raw; h.res = f.res; h.scale = f.scale; h.shift = f.shift; h.relu = f.relu; h.f16 = f.f16;

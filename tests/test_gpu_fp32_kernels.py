@@ -1,8 +1,14 @@
 """fp32-precision training kernels (fp32 tensors, split-bf16 x3 MFMA products) against plain PyTorch fp32 / fp64 (CPU autograd)
 references of the same ops.  Tolerances: MFMA kernels 5e-5 relative (2^-16 per product), streaming kernels 1e-5."""
 import ctypes as C
+import os
+import sys
+
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _bn_cases import bn_case  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -152,81 +158,10 @@ def test_backward_data_fp32():
         assert _rel(_nchw(out), x.grad) < 5e-5, (k, _rel(_nchw(out), x.grad))
 
 
-def _bn_case(pooled, with_res, two_grads, seed, outmask=False, skip=0, size=(12, 20), pool_first=True):
-    import torch
-    import torch.nn.functional as F
-    from cdnet_amd import _lib, trainer
-    g = torch.Generator().manual_seed(seed)
-    N, Cc, (H, W) = 2, 32, size
-    raw = torch.randn((N, Cc, H, W), generator=g).requires_grad_(True)
-    res = torch.randn((N, Cc, H, W), generator=g).requires_grad_(True) if with_res else None
-    gamma = (torch.rand((Cc,), generator=g) + 0.5).requires_grad_(True)
-    gamma.data[::4] *= -1
-    beta = (torch.randn((Cc,), generator=g) * 0.2).requires_grad_(True)
-    mean = raw.detach().mean((0, 2, 3))
-    var = raw.detach().var((0, 2, 3), unbiased=False)
-    y = F.batch_norm(raw, None, None, gamma, beta, training=True, eps=1e-5)
-    if with_res:
-        y = y + res
-    a = F.relu(y)
-    total = 0
-    gins = []
-    if pooled:
-        p = F.max_pool2d(a, 2)
-        gp = torch.randn(p.shape, generator=g)
-        total = total + (p * gp).sum()
-        gins.append(trainer._G(_nhwc(gp), p.shape[2], p.shape[3], pooled=1))
-    for _ in range(skip):
-        # a same-size consumer that reads the activation as a channel slice of a wider tensor (the decoder's torch.cat with the skip)
-        gwide = torch.randn((N, Cc + 16, H, W), generator=g)
-        total = total + (a * gwide[:, 16:16 + Cc]).sum()
-        gins.append(trainer._G(_nhwc(gwide), H, W, coff=16, cstride=Cc + 16))
-    if not pool_first:
-        gins = gins[1:] + gins[:1]
-    if (two_grads or not pooled) and not skip:
-        if outmask:
-            gfull = torch.randn((N, Cc, H, W), generator=g)
-            total = total + (a * gfull).sum()
-            gins.append(trainer._G(_nhwc(gfull), H, W))
-        else:
-            ap = F.pad(a, (2, 1, 1, 0))
-            gfull = torch.randn((N, Cc + 16, H + 1, W + 3), generator=g)
-            total = total + (ap * gfull[:, 8:8 + Cc]).sum()
-            gins.append(trainer._G(_nhwc(gfull), H + 1, W + 3, oy=1, ox=2, coff=8, cstride=Cc + 16))
-    total.backward()
-    invstd = 1.0 / torch.sqrt(var + 1e-5)
-    scale = (gamma.detach() * invstd)
-    shift = beta.detach() - mean * scale
-    A = trainer.BnBwdArgs()
-    raw_d = _nhwc(raw.detach())
-    # relu = 2: `res` is the stored post-ReLU output of the unit (the fused residual epilogue), the mask is read from it
-    res_d = (_nhwc(a.detach()) if outmask else _nhwc(res.detach())) if with_res else None
-    A.raw, A.res = raw_d.data_ptr(), (res_d.data_ptr() if with_res else None)
-    dev = lambda t: t.detach().float().cuda().contiguous()
-    sc, sh, mu, iv, gm = dev(scale), dev(shift), dev(mean), dev(invstd), dev(gamma)
-    A.scale, A.shift, A.mean, A.invstd = sc.data_ptr(), sh.data_ptr(), mu.data_ptr(), iv.data_ptr()
-    A.ngin = len(gins)
-    for k, gi in enumerate(gins):
-        A.gin[k].g = gi.t.data_ptr()
-        A.gin[k].Hg, A.gin[k].Wg, A.gin[k].oy, A.gin[k].ox = gi.Hg, gi.Wg, gi.oy, gi.ox
-        A.gin[k].pooled, A.gin[k].coff, A.gin[k].cstride = gi.pooled, gi.coff, gi.cstride or Cc
-    A.f16, A.relu, A.N, A.H, A.W, A.C = 2, (2 if outmask else 1), N, H, W, Cc
-    ws = torch.empty((_lib.load().cdnet_bn_backward_workspace_floats(Cc),), dtype=torch.float32, device='cuda')
-    dgamma, dbeta = torch.zeros(Cc, device='cuda'), torch.zeros(Cc, device='cuda')
-    draw = torch.empty((N, H, W, Cc), dtype=torch.float32, device='cuda')
-    dz = torch.empty((N, H, W, Cc), dtype=torch.float32, device='cuda')
-    _lib.call('cdnet_bn_backward', C.byref(A), _lib.ptr(gm), _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(ws), ws.numel(),
-              _lib.ptr(draw), _lib.ptr(dz) if with_res else None, _lib.stream_ptr())
-    assert _rel(_nchw(draw), raw.grad) < 1e-5, ('draw', _rel(_nchw(draw), raw.grad))
-    assert _rel(dgamma.cpu(), gamma.grad) < 1e-5 and _rel(dbeta.cpu(), beta.grad) < 1e-5
-    if with_res:
-        assert _rel(_nchw(dz), res.grad) < 1e-5
-
-
 @pytest.mark.parametrize('cfg', [(False, False, False), (True, False, False), (True, False, True), (False, True, False),
                                  (True, True, True)])
 def test_bn_backward_fp32(cfg):
-    _bn_case(*cfg, seed=11)
+    bn_case('f32', *cfg, seed=11)
 
 
 @pytest.mark.parametrize('cfg', [(1, (12, 20), True), (1, (13, 21), False), (2, (10, 18), False), (0, (9, 7), True)])
@@ -234,11 +169,11 @@ def test_bn_backward_fp32_pool_window(cfg):
     """the encoder's layers in front of a max-pool (one pooled consumer + the decoder's skip slice): bn_bwd_window32_kernel, odd sizes
     (a last window row / column without a pooled gradient), the pooled source first or last in the argument order"""
     skip, size, pool_first = cfg
-    _bn_case(True, False, False, seed=13, skip=skip, size=size, pool_first=pool_first)
+    bn_case('f32', True, False, False, seed=13, skip=skip, size=size, pool_first=pool_first)
 
 
 def test_bn_backward_fp32_mask_from_stored_output():
-    _bn_case(False, True, False, seed=12, outmask=True)
+    bn_case('f32', False, True, False, seed=12, outmask=True)
 
 
 def test_head_forward_backward_fp32():

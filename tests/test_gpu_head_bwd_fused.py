@@ -1,6 +1,6 @@
 """cdnet_dam_head_backward_fused (fp32 training step): the DAM head's backward and its weight gradients in one launch, the third
 feature's gradient leaving behind its residual unit's ReLU for that unit's BatchNorm backward - against fp64 autograd (streaming-kernel
-tolerance 1e-5, as test_head_forward_backward_fp32 and _bn_case of test_gpu_fp32_kernels.py), bit for bit against the two-kernel path on
+tolerance 1e-5, as test_head_forward_backward_fp32 and tests/_bn_cases.py), bit for bit against the two-kernel path on
 the same inputs, and through Trainer.backward.
 
 Shapes (N, H, W): (1, 8, 8) one 64-pixel group - every other workgroup must contribute zeros; (3, 7, 9) 189 pixels, a ragged last group

@@ -1,7 +1,13 @@
 """GPU numerics of the training kernels against plain PyTorch fp32 (CPU autograd) references of the same ops."""
 import ctypes as C
+import os
+import sys
+
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _bn_cases import bn_case  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -181,71 +187,10 @@ def test_backward_data_of_transposed_conv_via_space_to_depth():
         assert _rel(_nchw(out), x.grad) < 6e-3, (k, _rel(_nchw(out), x.grad))
 
 
-def _bn_case(pooled, with_res, two_grads, seed):
-    import torch
-    import torch.nn.functional as F
-    from cdnet_amd import _lib, trainer
-    g = torch.Generator().manual_seed(seed)
-    N, Cc, H, W = 2, 32, 12, 20
-    raw = torch.randn((N, Cc, H, W), generator=g).half().float().requires_grad_(True)
-    res = torch.randn((N, Cc, H, W), generator=g).half().float().requires_grad_(True) if with_res else None
-    gamma = (torch.rand((Cc,), generator=g) + 0.5).requires_grad_(True)
-    gamma.data[::4] *= -1
-    beta = (torch.randn((Cc,), generator=g) * 0.2).requires_grad_(True)
-    mean = raw.detach().mean((0, 2, 3))
-    var = raw.detach().var((0, 2, 3), unbiased=False)
-    y = F.batch_norm(raw, None, None, gamma, beta, training=True, eps=1e-5)
-    if with_res:
-        y = y + res
-    a = F.relu(y)
-    a = a + (_bf(a.detach()) - a.detach())      # consumers see the activation rounded to bf16 (as the conv staging does)
-    total = 0
-    gins = []
-    if pooled:
-        p = F.max_pool2d(a, 2)
-        gp = _bf(torch.randn(p.shape, generator=g))
-        total = total + (p * gp).sum()
-        gins.append(trainer._G(_nhwc(gp), p.shape[2], p.shape[3], pooled=1))
-    if two_grads or not pooled:
-        # consumer that read the tensor through F.pad offsets (1, 2) and as a channel slice of a wider gradient
-        ap = F.pad(a, (2, 1, 1, 0))
-        gfull = _bf(torch.randn((N, Cc + 16, H + 1, W + 3), generator=g))
-        total = total + (ap * gfull[:, 8:8 + Cc]).sum()
-        gins.append(trainer._G(_nhwc(gfull), H + 1, W + 3, oy=1, ox=2, coff=8, cstride=Cc + 16))
-    total.backward()
-    invstd = 1.0 / torch.sqrt(var + 1e-5)
-    scale = (gamma.detach() * invstd)
-    shift = beta.detach() - mean * scale
-    A = trainer.BnBwdArgs()
-    raw_d = _nhwc(raw.detach(), torch.float16)
-    res_d = _nhwc(res.detach(), torch.float16) if with_res else None
-    keep = [raw_d, res_d]
-    A.raw, A.res = raw_d.data_ptr(), (res_d.data_ptr() if with_res else None)
-    dev = lambda t: t.detach().float().cuda().contiguous()
-    sc, sh, mu, iv, gm = dev(scale), dev(shift), dev(mean), dev(invstd), dev(gamma)
-    A.scale, A.shift, A.mean, A.invstd = sc.data_ptr(), sh.data_ptr(), mu.data_ptr(), iv.data_ptr()
-    A.ngin = len(gins)
-    for k, gi in enumerate(gins):
-        A.gin[k].g = gi.t.data_ptr()
-        A.gin[k].Hg, A.gin[k].Wg, A.gin[k].oy, A.gin[k].ox = gi.Hg, gi.Wg, gi.oy, gi.ox
-        A.gin[k].pooled, A.gin[k].coff, A.gin[k].cstride = gi.pooled, gi.coff, gi.cstride or Cc
-    A.f16, A.relu, A.N, A.H, A.W, A.C = 1, 1, N, H, W, Cc
-    ws = torch.empty((_lib.load().cdnet_bn_backward_workspace_floats(Cc),), dtype=torch.float32, device='cuda')
-    dgamma, dbeta = torch.zeros(Cc, device='cuda'), torch.zeros(Cc, device='cuda')
-    draw = torch.empty((N, H, W, Cc), dtype=torch.bfloat16, device='cuda')
-    dz = torch.empty((N, H, W, Cc), dtype=torch.bfloat16, device='cuda')
-    _lib.call('cdnet_bn_backward', C.byref(A), _lib.ptr(gm), _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(ws), ws.numel(),
-              _lib.ptr(draw), _lib.ptr(dz) if with_res else None, _lib.stream_ptr())
-    assert _rel(_nchw(draw), raw.grad) < 1e-2, ('draw', _rel(_nchw(draw), raw.grad))
-    assert _rel(dgamma.cpu(), gamma.grad) < 3e-3 and _rel(dbeta.cpu(), beta.grad) < 3e-3
-    if with_res:
-        assert _rel(_nchw(dz), res.grad) < 6e-3
-
-
 @pytest.mark.parametrize('cfg', [(False, False, False), (True, False, False), (True, False, True), (False, True, False),
                                  (True, True, True)])
 def test_bn_relu_pool_pad_backward(cfg):
-    _bn_case(*cfg, seed=11)
+    bn_case('f16', *cfg, seed=11)
 
 
 def test_loss_values_and_gradients(golden):
