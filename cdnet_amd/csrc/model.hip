@@ -778,13 +778,23 @@ __global__ __launch_bounds__(256) void fuse_sum16_kernel(FuseArgs A) {
 
 // transpose of the bilinear up-sampling inside fuse_sum (gather form, deterministic): din[ys][xs] = sum over the output
 // pixels (y, x) whose interpolation reads (ys, xs) of their weight x dout[y][x].  dout may be a channel slice.
+// Any Hs <= H, Ws <= W.  Output row y reads source row ys only if ys - 1 < (y + 0.5) * Hs / H - 0.5 < ys + 1, that is
+// (2 ys - 1) H < (2 y + 1) Hs < (2 ys + 3) H; upsample_window() is that interval in integers, one row wider on each side
+// because the weights below come from the fp32 `fy` of the forward, which may land one row beside the exact one.  Rows
+// of the window that do not read ys drop out through wy == 0.  At integer ratios the window is never wider than
+// [(ys - 1) r, (ys + 2) r), and the visiting order is y then x ascending.
+__device__ __forceinline__ void upsample_window(int ys, int Hs, int H, int &lo, int &hi) {
+    lo = ys == 0 ? 0 : ((2 * ys - 1) * H - Hs) / (2 * Hs);            // (first row that satisfies the left inequality) - 1
+    hi = ((2 * ys + 3) * H + Hs - 1) / (2 * Hs) + 1;                  // (one past the last row of the right one) + 1
+    hi = hi > H ? H : hi;
+}
+
 template <bool F32>
 __global__ __launch_bounds__(256) void upsample_bwd_kernel(const unsigned short *__restrict__ dout, int N, int H, int W, int C, int cstride,
                                                            int coff, int Hs, int Ws, unsigned short *__restrict__ din) {
     const int VPP = C / 8;
     const size_t total = (size_t)N * Hs * Ws * VPP;
     const float sy = (float)Hs / (float)H, sx = (float)Ws / (float)W;
-    const int ry = (H + Hs - 1) / Hs, rx = (W + Ws - 1) / Ws;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int slot = (int)(i % VPP);
         const size_t pix = i / VPP;
@@ -792,8 +802,9 @@ __global__ __launch_bounds__(256) void upsample_bwd_kernel(const unsigned short 
         float acc[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) acc[j] = 0.f;
-        const int ylo = (ys - 1) * ry < 0 ? 0 : (ys - 1) * ry, yhi = (ys + 2) * ry > H ? H : (ys + 2) * ry;
-        const int xlo = (xs - 1) * rx < 0 ? 0 : (xs - 1) * rx, xhi = (xs + 2) * rx > W ? W : (xs + 2) * rx;
+        int ylo, yhi, xlo, xhi;
+        upsample_window(ys, Hs, H, ylo, yhi);
+        upsample_window(xs, Ws, W, xlo, xhi);
         for (int y = ylo; y < yhi; ++y) {
             float fy = ((float)y + 0.5f) * sy - 0.5f;
             fy = fy < 0.f ? 0.f : fy;
@@ -1045,15 +1056,16 @@ static int fuse_sum_impl(const cdnet_fuse_term *terms, int nterm, int N, int H, 
     CDNET_REQUIRE(A.out_cstride % 8 == 0 && out_coff % 8 == 0 && out_coff + C <= A.out_cstride, "cdnet_fuse_sum: output channel slice");
     const size_t total = (size_t)N * H * W * (C / 8);
     const int grid = lin_grid(total);
+    CDNET_REQUIRE(f32 || total < (1ull << 31), "cdnet_fuse_sum: more than 2^31 output vectors (the 16-bit kernels index in 32 bits)");
     if (f32) fuse_sum_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(A);
-    else if (total < (1ull << 31)) {
+    else {
         switch (nterm) {
             case 1: fuse_sum16_kernel<1><<<grid, 256, 0, (hipStream_t)stream>>>(A); break;
             case 2: fuse_sum16_kernel<2><<<grid, 256, 0, (hipStream_t)stream>>>(A); break;
             case 3: fuse_sum16_kernel<3><<<grid, 256, 0, (hipStream_t)stream>>>(A); break;
             default: fuse_sum16_kernel<4><<<grid, 256, 0, (hipStream_t)stream>>>(A); break;
         }
-    } else fuse_sum_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(A);
+    }
     return check_launch("cdnet_fuse_sum");
 }
 
@@ -1072,6 +1084,8 @@ static int upsample_bwd_impl(const void *dout, int N, int H, int W, int C, int d
     CDNET_REQUIRE(dout && din && N > 0 && H >= Hs && W >= Ws && Hs > 0 && Ws > 0 && C % 8 == 0 && C >= 8, "cdnet_upsample_bilinear_backward: bad args");
     const int cs = dout_cstride ? dout_cstride : C;
     CDNET_REQUIRE(cs % 8 == 0 && dout_coff % 8 == 0 && dout_coff + C <= cs, "cdnet_upsample_bilinear_backward: channel slice");
+    CDNET_REQUIRE((2ll * Hs + 1) * H + Hs < (1ll << 31) && (2ll * Ws + 1) * W + Ws < (1ll << 31),
+                  "cdnet_upsample_bilinear_backward: (2 Hs + 1) H does not fit 32 bits");
     const unsigned short *d = reinterpret_cast<const unsigned short *>(dout);
     unsigned short *o = reinterpret_cast<unsigned short *>(din);
     if (f32) upsample_bwd_kernel<true><<<lin_grid((size_t)N * Hs * Ws * (C / 8)), 256, 0, (hipStream_t)stream>>>(d, N, H, W, C, cs, dout_coff, Hs, Ws, o);

@@ -650,7 +650,7 @@ int cdnet_label_encoding_instances(const int32_t *label_inst, int N, int H, int 
  * of the four branches (:528-533).  out[N][H][W] = [relu](sum of 1..4 terms), every term a bf16 NHWC tensor with C
  * channels (optionally with a per-channel affine), either [H][W] or a lower resolution that is up-sampled bilinearly
  * (align_corners = False).  The output may be a
- * channel slice [out_coff, out_coff + C) of pixels out_cstride wide (0 = C).
+ * channel slice [out_coff, out_coff + C) of pixels out_cstride wide (0 = C).  The 16-bit entry refuses N * H * W * C / 8 >= 2^31.
  * ---------------------------------------------------------------------------------------------------- */
 typedef struct cdnet_fuse_term {
     const uint16_t *x;      /* bf16 (or fp16 when f16 = 1) NHWC [N][Hs][Ws][C] */
@@ -664,7 +664,8 @@ int cdnet_fuse_sum(const cdnet_fuse_term *terms, int nterm, int N, int H, int W,
 
 /* backward pieces of the HRNet training step (loss.backward() through seg_hrnet_rev1.py:256-283, 436-443):
  * cdnet_upsample_bilinear_backward: transpose of the bilinear up-sampling done inside cdnet_fuse_sum: dout bf16 NHWC
- *   [N][H][W] (channel slice coff / cstride allowed) -> din bf16 [N][Hs][Ws][C];
+ *   [N][H][W] (channel slice coff / cstride allowed) -> din bf16 [N][Hs][Ws][C], for any Hs <= H, Ws <= W (the ratio need not be an
+ *   integer; (2 Hs + 1) H must fit 32 bits);
  * cdnet_s2d_to_nhwc: gradient computed in the space-to-depth view [N][H2][W2][(a, b, c)] -> [N][2*H2][2*W2][C]
  *   (input gradient of a stride-2 convolution; weight pack mode 7 = backward-data of mode 6). */
 int cdnet_upsample_bilinear_backward(const uint16_t *dout, int N, int H, int W, int C, int dout_cstride, int dout_coff, int Hs, int Ws,

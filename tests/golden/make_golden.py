@@ -25,6 +25,7 @@ Fixtures:
   postproc.npz     test_dam.py:445-450,479-491,529-563 re-assembled (TTA mean, DDM fuse, boost, argmax,
                    fill holes, remove small, label, dilation) [skimage-semantics restated]
   aji.npz          stats_utils.get_fast_aji / get_dice_1 / get_fast_pq on label fixtures
+  aji_many.npz     the same three on one 384 x 384 pair with more than 512 instances
 """
 import os
 import sys
@@ -717,8 +718,30 @@ def gen_aji():
     save('aji', **out)
 
 
+def gen_aji_many():
+    """one 384 x 384 pair with more than 512 instances each (the fixtures of aji.npz have at most 76): the prediction is the truth shifted
+    by (1, 2) pixels with every 7th instance removed and every 11th merged into its predecessor; both maps remapped by the reference"""
+    import stats_utils
+    rs = np.random.RandomState(11)
+    true = synth.ellipse_instances(384, 384, 6000, rs, rmin=2, rmax=6, margin=7)
+    pred = np.roll(np.roll(true, 1, axis=0), 2, axis=1)
+    n = int(true.max())
+    lut = np.arange(n + 1, dtype=np.int32)
+    lut[7::7] = 0
+    for i in range(11, n + 1, 11):
+        lut[i] = lut[i - 1]
+    pred = lut[pred]
+    t = stats_utils.remap_label(true.copy()).astype(np.int32)
+    p = stats_utils.remap_label(pred.copy()).astype(np.int32)
+    print('  aji_many instances true %d pred %d' % (t.max(), p.max()))
+    assert t.max() > 512 and p.max() > 512
+    aji = stats_utils.get_fast_aji(t, p)
+    save('aji_many', true=t, pred=p, aji=np.array(aji, dtype=np.float64), dice=np.float64(stats_utils.get_dice_1(t, p)),
+         pq=np.array(stats_utils.get_fast_pq(t, p)[0], dtype=np.float64))
+
+
 ALL = {'validate': gen_validate, 'validate_obj': gen_validate_obj, 'ablation': gen_ablation, 'ddm': gen_ddm, 'unet': gen_unet, 'dam': gen_dam, 'losses': gen_losses, 'losses_classes': gen_losses_classes, 'train_iter': gen_train_iter, 'unet_train_iter': gen_unet_train_iter, 'hrnet': gen_hrnet, 'hrnet_train': gen_hrnet_train,
-       'cdm': gen_cdm, 'cdm_inst': gen_cdm_inst, 'split': gen_split, 'probmaps': gen_probmaps, 'postproc': gen_postproc, 'aji': gen_aji}
+       'cdm': gen_cdm, 'cdm_inst': gen_cdm_inst, 'split': gen_split, 'probmaps': gen_probmaps, 'postproc': gen_postproc, 'aji': gen_aji, 'aji_many': gen_aji_many}
 
 if __name__ == '__main__':
     which = sys.argv[1:] or list(ALL)
