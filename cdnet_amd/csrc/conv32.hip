@@ -440,6 +440,222 @@ int dispatch_conv32(const ConvArgs &A, hipStream_t st) {
     return CDNET_E_ARG;
 }
 
+// ----------------------------------------------------------------------------------------------------------------------------------
+// 1x1 convolution over one dense source as the plain GEMM it is: [pixels x Cin] . [Cin x Cout], no halo, no tile geometry.  A wave
+// works alone on blocks of 32 consecutive NHWC pixels (block index striding over the grid): lane (l31, half) loads the 8 fp32
+// channels of k-half `half` of every chunk of pixel l31 straight from HBM (two 16-byte vectors per chunk - the A fragment's own
+// channels), transforms and splits them in registers and issues the MFMAs against B fragments read from the workgroup's LDS copy of
+// the split pack (written once, the only barrier).  The next block's loads are requested before this block's MFMAs, the other
+// branch of a residual unit (eres) after them, into the registers the inputs have left.
+// Same arithmetic as conv_f32_kernel per output element - chunks ascending, a_lo b_hi, a_hi b_lo, a_hi b_hi per chunk, commit()'s
+// source transform, store_tile_f32's epilogue - so the outputs agree bit for bit (which pixel sits in which MFMA row enters no
+// output element).  The tail block's missing pixels are outside its buffer descriptors' range: read as zero, not written.
+// ----------------------------------------------------------------------------------------------------------------------------------
+template <int BN, int NCH, bool XF, bool ERES>
+__global__ __launch_bounds__(256, 4) void conv1x1_f32_stream_kernel(ConvArgs A) {
+    constexpr int NPW = BN / 32;
+    constexpr int B_PLANE = CK * BN * 2;                          // bytes of one weight image (hi or lo) of one chunk
+    constexpr int CIN = NCH * CK;
+    __shared__ __attribute__((aligned(16))) unsigned char smem[NCH * 2 * B_PLANE + 2 * CIN * 4];
+    unsigned char *lds_b = smem;                                  // per chunk [hi image][lo image]
+    float *s_xf = reinterpret_cast<float *>(smem + NCH * 2 * B_PLANE);       // [scale][shift] of the source
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int half = lane >> 5, l31 = lane & 31;
+    const int cout_tile = blockIdx.y, cout0 = cout_tile * BN;
+    const ConvSrc &S = A.src[0];
+    {
+        const u32x4 *wsrc = reinterpret_cast<const u32x4 *>(A.w + (size_t)cout_tile * NCH * B_PLANE);       // u16 elements: 2 planes x B_PLANE / 2
+        u32x4 *bdst = reinterpret_cast<u32x4 *>(lds_b);
+        for (int v = tid; v < NCH * 2 * B_PLANE / 16; v += 256) bdst[v] = wsrc[v];
+        for (int c = tid; c < CIN; c += 256) {
+            s_xf[c] = S.scale ? S.scale[c] : 1.f;
+            s_xf[CIN + c] = S.shift ? S.shift[c] : 0.f;
+        }
+    }
+    __syncthreads();
+
+    const size_t P = (size_t)A.N * A.H * A.W;
+    const int nblk = (int)((P + 31) / 32), bstride = (int)gridDim.x * 4;
+    int blk = (int)blockIdx.x * 4 + wave;
+    if (blk >= nblk) return;
+    const bool relu = S.relu != 0, orelu = A.orelu != 0, eres_relu = A.eres_relu != 0;
+    const int cout = A.Cout;
+    const int bbase = half * BN * 16 + l31 * 16;
+
+    // per output channel, as store_tile_f32 forms them
+    float osc[NPW], osh[NPW], esc[NPW], esh[NPW];
+#pragma unroll
+    for (int ni = 0; ni < NPW; ++ni) {
+        const int co = cout0 + ni * 32 + l31, c = co < A.Cout ? co : 0;
+        osc[ni] = A.oscale ? A.oscale[c] : 1.f;
+        osh[ni] = fmaf(A.bias ? A.bias[c] : 0.f, osc[ni], A.oshift ? A.oshift[c] : 0.f);
+        esc[ni] = (ERES && A.eres_scale) ? A.eres_scale[c] : 1.f;
+        esh[ni] = (ERES && A.eres_shift) ? A.eres_shift[c] : 0.f;
+    }
+
+    // Every access goes through a buffer descriptor of its block (base = the block's first pixel, range = its pixels) with a 32-bit byte
+    // offset of the lane: a lane without an output channel (co >= Cout) carries an offset outside every range, and what lies past the
+    // tail block's last pixel reads as zero and is not written.  The row of the block is a scalar offset in full blocks (one address
+    // register per lane and channel block); the range check does not see scalar offsets, so the tail block adds the row to the lane's.
+    const char *xbase = reinterpret_cast<const char *>(S.x);
+    char *obase = reinterpret_cast<char *>(A.out) + (size_t)A.out_coff * 4;
+    const char *ebase = ERES ? reinterpret_cast<const char *>(A.eres) : xbase;
+    const unsigned cs4 = (unsigned)A.out_cstride * 4, ce4 = (unsigned)cout * 4;
+    const unsigned vo_in = l31 * (CIN * 4) + half * 32;
+    unsigned vo_out[NPW], vo_eres[NPW];
+#pragma unroll
+    for (int ni = 0; ni < NPW; ++ni) {
+        const unsigned co = cout0 + ni * 32 + l31;
+        vo_out[ni] = co < (unsigned)cout ? 4 * half * cs4 + co * 4 : 0x7fff0000u;
+        vo_eres[ni] = co < (unsigned)cout ? 4 * half * ce4 + co * 4 : 0x7fff0000u;
+    }
+    auto rsrc = [&](const char *base, size_t bytes) {
+        return __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(base), 0, (int)bytes, 0x00020000);
+    };
+
+    auto request = [&](f32x4 (&v)[NCH][2], int b) {
+        const size_t left = P - (size_t)b * 32;
+        const __amdgpu_buffer_rsrc_t rx = rsrc(xbase + (size_t)b * (32 * CIN * 4), (left < 32 ? left : 32) * (CIN * 4));
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            v[c][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)(vo_in + c * 64), 0, 0));
+            v[c][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)(vo_in + c * 64 + 16), 0, 0));
+        }
+    };
+    auto block = [&](auto tail_c, const f32x4 (&cur)[NCH][2], f32x4 (&nxt)[NCH][2]) {
+        constexpr bool TAIL = decltype(tail_c)::value;
+        asm volatile("" ::: "memory");                           // (the B fragments are read from LDS block by block, not held in 16 NCH NPW registers)
+        if (!TAIL) {
+            request(nxt, blk + bstride < nblk ? blk + bstride : blk);    // (after the last block: the same again, no branch)
+            __builtin_amdgcn_sched_barrier(0);                    // these requests stay in front of the MFMAs
+        }
+        f32x16 acc[NPW];
+#pragma unroll
+        for (int ni = 0; ni < NPW; ++ni)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[ni][r] = 0.f;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            float v[8] = {cur[c][0][0], cur[c][0][1], cur[c][0][2], cur[c][0][3], cur[c][1][0], cur[c][1][1], cur[c][1][2], cur[c][1][3]};
+            if (XF) {                                              // (a ReLU comes with a scale / shift here: the dispatcher sees to it)
+                const float *xf = s_xf + c * CK + half * 8;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    v[j] = fmaf(v[j], xf[j], xf[CIN + j]);
+                    v[j] = relu ? fmaxf(v[j], 0.f) : v[j];
+                }
+            }
+            u32x4 hi, lo;
+            split8(v, hi, lo);
+            const bf16x8 ah = __builtin_bit_cast(bf16x8, hi), al = __builtin_bit_cast(bf16x8, lo);
+#pragma unroll
+            for (int ni = 0; ni < NPW; ++ni) {
+                const bf16x8 bh = *reinterpret_cast<const bf16x8 *>(lds_b + c * 2 * B_PLANE + bbase + ni * 512);
+                const bf16x8 bl = *reinterpret_cast<const bf16x8 *>(lds_b + c * 2 * B_PLANE + B_PLANE + bbase + ni * 512);
+                // small terms first
+                acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[ni], 0, 0, 0);
+                acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[ni], 0, 0, 0);
+                acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[ni], 0, 0, 0);
+            }
+        }
+        // a lane owns one output channel and the pixels (r & 3) + 8 (r >> 2) + 4 half of the block; lanes 0..31 / 32..63 write two 128-byte
+        // pixel segments per instruction
+        const size_t left = P - (size_t)blk * 32, rows = left < 32 ? left : 32;
+        const __amdgpu_buffer_rsrc_t ro = rsrc(obase + (size_t)blk * 32 * cs4, rows * cs4);
+        float ev[NPW][16];
+        if (ERES) {                                                // the other branch of the residual unit
+            const __amdgpu_buffer_rsrc_t re = rsrc(ebase + (size_t)blk * 32 * ce4, rows * ce4);
+#pragma unroll
+            for (int ni = 0; ni < NPW; ++ni)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const unsigned pr = (r & 3) + 8 * (r >> 2);
+                    ev[ni][r] = __builtin_bit_cast(float, TAIL ? __builtin_amdgcn_raw_buffer_load_b32(re, (int)(vo_eres[ni] + pr * ce4), 0, 0)
+                                                               : __builtin_amdgcn_raw_buffer_load_b32(re, (int)vo_eres[ni], (int)(pr * ce4), 0));
+                }
+        }
+#pragma unroll
+        for (int ni = 0; ni < NPW; ++ni)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const unsigned pr = (r & 3) + 8 * (r >> 2);
+                float v = fmaf(acc[ni][r], osc[ni], osh[ni]);
+                v = orelu ? fmaxf(v, 0.f) : v;
+                if (ERES) {
+                    v = fmaf(ev[ni][r], esc[ni], esh[ni]) + v;
+                    v = eres_relu ? fmaxf(v, 0.f) : v;
+                }
+                if (TAIL) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ro, (int)(vo_out[ni] + pr * cs4), 0, 0);
+                else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ro, (int)vo_out[ni], (int)(pr * cs4), 0);
+            }
+    };
+    // two register sets take turns (a copy of one into the other would wait for the block's stores as well)
+    f32x4 xa[NCH][2], xb[NCH][2];
+    const int nfull = (int)(P / 32);
+    if (blk < nfull) {
+        request(xa, blk);
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) asm volatile("" ::"v"(xa[c][0]), "v"(xa[c][1]));       // (arrived: the loop's own waits then never count this request, which would make them wait for a block's stores)
+        for (;;) {
+            block(std::false_type{}, xa, xb);
+            blk += bstride;
+            if (blk >= nfull) break;
+            block(std::false_type{}, xb, xa);
+            blk += bstride;
+            if (blk >= nfull) break;
+        }
+    }
+    if (blk < nblk) {                                             // (the tail block asks again for what the last block may have requested)
+        request(xa, blk);
+        block(std::true_type{}, xa, xb);
+    }
+}
+
+template <int BN, int NCH>
+int launch_conv1x1_stream(const ConvArgs &A, hipStream_t st) {
+    static int n_cu = 0;
+    if (n_cu == 0) {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return check_launch("hipGetDeviceProperties");
+        n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    }
+    // sixteen waves per CU are resident; every wave gets the same number of pixel blocks, give or take one
+    const long long nblk = ((long long)A.N * A.H * A.W + 31) / 32;
+    const int ctiles = cdiv(A.Cout, BN);
+    const long long waves = (long long)n_cu * 16 / ctiles > 4 ? (long long)n_cu * 16 / ctiles : 4;
+    const long long rounds = (nblk + waves - 1) / waves;
+    const long long G = ((nblk + rounds - 1) / rounds + 3) / 4;
+    dim3 grid((unsigned)G, ctiles, 1);
+    const bool xf = A.src[0].scale != nullptr, er = A.eres != nullptr;
+    if (xf && er) conv1x1_f32_stream_kernel<BN, NCH, true, true><<<grid, 256, 0, st>>>(A);
+    else if (xf) conv1x1_f32_stream_kernel<BN, NCH, true, false><<<grid, 256, 0, st>>>(A);
+    else if (er) conv1x1_f32_stream_kernel<BN, NCH, false, true><<<grid, 256, 0, st>>>(A);
+    else conv1x1_f32_stream_kernel<BN, NCH, false, false><<<grid, 256, 0, st>>>(A);
+    return check_launch("conv1x1_f32_stream_kernel");
+}
+
+// -1 = not this kernel's launch (the caller goes on to conv_f32_kernel)
+int try_conv1x1_stream(const ConvArgs &A, hipStream_t st) {
+    if (A.debug & 256) return -1;                                 // tests / A-B: conv_f32_kernel instead
+    if (A.taps != 1 || A.taps1 != 0 || A.npar != 1 || A.ostride != 1 || A.ws || A.stats || A.pool_out || A.nsrc != 1) return -1;
+    const ConvSrc &s = A.src[0];
+    if (s.off_y || s.off_x || s.Hs != A.H || s.Ws != A.W || (s.row_stride && s.row_stride != s.Ws * s.C) || s.pool || s.res) return -1;
+    if (s.relu && !s.scale) return -1;                           // (no instantiation for a ReLU without scale / shift)
+    if (s.C != A.nchunk * CK || (long long)A.N * A.H * A.W > (1LL << 31) - 64 || (long long)A.out_cstride * 4 * 36 >= (1LL << 31)) return -1;
+    auto go = [&](auto bn_c) -> int {
+        constexpr int BN = decltype(bn_c)::value;
+        if (A.nchunk == 1) return launch_conv1x1_stream<BN, 1>(A, st);
+        if (A.nchunk == 2) return launch_conv1x1_stream<BN, 2>(A, st);
+        if (A.nchunk == 4) return launch_conv1x1_stream<BN, 4>(A, st);
+        return -1;
+    };
+    if (A.BN == 64) return go(std::integral_constant<int, 64>{});
+    if (A.BN == 32) return go(std::integral_constant<int, 32>{});
+    return -1;
+}
+
 // fp32 variant of materialize_kernel (conv.hip): the source with its pending transform (scale/shift, residual, ReLU, 2x2
 // max-pool floor / ceil mode, pad offset) written out as a plain fp32 tensor
 __global__ __launch_bounds__(256) void materialize_f32_kernel(const ConvSrc s, int N, int H, int W, float *__restrict__ out) {
@@ -512,6 +728,10 @@ int conv_forward_f32(const ConvArgs &A, hipStream_t st) {
     CDNET_REQUIRE(!A.pool_out, "cdnet_conv_forward(f32): the fused max-pool output rides in conv_ws32_kernel's epilogue only (ask cdnet_conv_ws_eligible)");
     if (A.taps == 9) return dispatch_conv32<9>(A, st);
     if (A.taps == 4) return dispatch_conv32<4>(A, st);
+    {
+        const int rc = try_conv1x1_stream(A, st);                // one dense source, a few chunks: the halo-free streaming kernel
+        if (rc >= 0) return rc;
+    }
     return dispatch_conv32<1>(A, st);
 }
 
