@@ -7,6 +7,7 @@
 // the row runs, union-find with agent-scope atomics for the label propagation.  Results are bit-exact against
 // the CPU oracle (tests/test_gpu_postproc.py).
 #include "common.h"
+#include "cc_forest.h"
 
 using namespace cdnet;
 
@@ -26,10 +27,6 @@ __device__ __forceinline__ int view_offset(int xf, int y, int x, int H, int W) {
 }
 
 struct ViewXf { int v[16]; };
-
-__device__ __forceinline__ int ld_relaxed(const int *p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 __device__ __forceinline__ int wave_min(int v) {
 #pragma unroll
@@ -508,120 +505,6 @@ __global__ __launch_bounds__(256) void mask_views_kernel(const float *__restrict
     }
 }
 
-// ------------------------------------------------------------------------------------------------------
-// Connected components: union-find over pixel indices, roots = smallest (raster-first) index of a component.
-// One wave = 64 consecutive pixels of one row: the row runs come from a ballot, so only run heads talk to
-// the forest.  Block (64,4); grid (ceil(W/64), ceil(H/4), N).  L: int32 per pixel, -1 = not in the mask.
-// ------------------------------------------------------------------------------------------------------
-
-__device__ __forceinline__ int uf_find(const int *L, int a) {
-    int p = ld_relaxed(L + a);
-    while (p != a) { a = p; p = ld_relaxed(L + a); }
-    return a;
-}
-
-__device__ __forceinline__ void uf_union(int *L, int a, int b) {
-    bool done;
-    do {
-        a = uf_find(L, a);
-        b = uf_find(L, b);
-        if (a < b) { int old = atomicMin(L + b, a); done = (old == b); b = old; }
-        else if (b < a) { int old = atomicMin(L + a, b); done = (old == a); a = old; }
-        else done = true;
-    } while (!done);
-}
-
-// index of the first lane of the run of set bits that contains `lane`
-__device__ __forceinline__ int run_start(unsigned long long m, int lane) {
-    unsigned long long zeros_below = ~m & ((1ull << lane) - 1ull);
-    return zeros_below ? 64 - __clzll(zeros_below) : 0;
-}
-// number of set bits in the run starting at `lane` (lane is a run head)
-__device__ __forceinline__ int run_length(unsigned long long m, int lane) {
-    unsigned long long z = ~(m >> lane);          // first zero above
-    return z ? __ffsll((long long)z) - 1 : 64 - lane;
-}
-
-// MODE 0: mask = (src != fgval)  [background of pred_inside, for fill-holes]; MODE 1: mask = (src != 0)
-template <int MODE>
-__device__ __forceinline__ bool in_mask(uint8_t v, int fgval) { return MODE == 0 ? (v != fgval) : (v != 0); }
-
-template <int MODE>
-__global__ __launch_bounds__(256) void cc_init_kernel(const uint8_t *__restrict__ src, int fgval, int H, int W,
-                                                      int *__restrict__ L) {
-    const int n = blockIdx.z;
-    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
-    const size_t base = (size_t)n * H * W;
-    const bool valid = x < W && y < H;
-    const bool fg = valid && in_mask<MODE>(src[base + (size_t)y * W + x], fgval);
-    const unsigned long long b = __ballot(fg);
-    if (valid) L[base + (size_t)y * W + x] = fg ? (y * W + blockIdx.x * 64 + run_start(b, threadIdx.x)) : -1;
-}
-
-// CONN: 4 or 8.  Unions between a row run and the runs of the row above, plus the stitch to the left segment.
-template <int MODE, int CONN>
-__global__ __launch_bounds__(256) void cc_merge_kernel(const uint8_t *__restrict__ src, int fgval, int H, int W,
-                                                       int *L) {
-    const int n = blockIdx.z;
-    const int lane = threadIdx.x;
-    const int x0 = blockIdx.x * 64, x = x0 + lane, y = blockIdx.y * 4 + threadIdx.y;
-    if (y >= H) return;                                   // whole wave exits together (y is wave-uniform)
-    const size_t base = (size_t)n * H * W;
-    const uint8_t *m = src + base;
-    int *Ln = L + base;
-    const bool valid = x < W;
-    const bool fg = valid && in_mask<MODE>(m[(size_t)y * W + x], fgval);
-    const bool up = valid && y > 0 && in_mask<MODE>(m[(size_t)(y - 1) * W + x], fgval);
-    // edge pixels outside this 64-segment
-    bool left_edge = false, upleft_edge = false, upright_edge = false;
-    if (lane == 0 && x0 > 0) {
-        left_edge = in_mask<MODE>(m[(size_t)y * W + x0 - 1], fgval);
-        if (y > 0) upleft_edge = in_mask<MODE>(m[(size_t)(y - 1) * W + x0 - 1], fgval);
-    }
-    if (lane == 63 && x0 + 64 < W && y > 0) upright_edge = in_mask<MODE>(m[(size_t)(y - 1) * W + x0 + 64], fgval);
-    const unsigned long long bf = __ballot(fg), bu = __ballot(up);
-    if (!fg) return;
-    const bool left = lane > 0 ? ((bf >> (lane - 1)) & 1ull) : left_edge;
-    const bool a = lane > 0 ? ((bu >> (lane - 1)) & 1ull) : upleft_edge;      // NW
-    const bool b = (bu >> lane) & 1ull;                                        // N
-    const bool c = lane < 63 ? ((bu >> (lane + 1)) & 1ull) : upright_edge;    // NE
-    const int p = y * W + x;
-    if (lane == 0 && left_edge) uf_union(Ln, p, p - 1);
-    if (CONN == 4) {
-        if (b && !(left && a)) uf_union(Ln, p, p - W);
-    } else {
-        if (b) { if (!left) uf_union(Ln, p, p - W); }
-        else {
-            if (a && !left) uf_union(Ln, p, p - W - 1);
-            if (c) uf_union(Ln, p, p - W + 1);
-        }
-    }
-}
-
-// L[p] <- root(p).  AREA: additionally area[root] += run length (one atomic per row run).
-template <bool AREA>
-__global__ __launch_bounds__(256) void cc_flatten_kernel(int H, int W, int *L, int *area) {
-    const int n = blockIdx.z;
-    const int lane = threadIdx.x;
-    const int x = blockIdx.x * 64 + lane, y = blockIdx.y * 4 + threadIdx.y;
-    const size_t base = (size_t)n * H * W;
-    int *Ln = L + base;
-    const bool valid = x < W && y < H;
-    int r = -1;
-    if (valid) {
-        int l = Ln[(size_t)y * W + x];
-        if (l >= 0) { r = uf_find(Ln, l); }
-    }
-    const unsigned long long bf = __ballot(r >= 0);
-    if (r >= 0) {
-        Ln[(size_t)y * W + x] = r;
-        if (AREA) {
-            bool head = lane == 0 || !((bf >> (lane - 1)) & 1ull);
-            if (head) atomicAdd(area + base + r, run_length(bf, lane));
-        }
-    }
-}
-
 // fill-holes: mark the roots of background components that touch the image border (L[root] = ~root < 0 ... -1 is
 // "not background", so use -2-root).
 __global__ __launch_bounds__(256) void fill_mark_border_kernel(int H, int W, int *L) {
@@ -816,7 +699,6 @@ __global__ __launch_bounds__(256) void dilate_disk_kernel(const int32_t *__restr
     out[(size_t)n * H * W + (size_t)y * W + x] = v;
 }
 
-inline dim3 grid_rows(int N, int H, int W) { return dim3(cdiv(W, 64), cdiv(H, 4), N); }
 inline int grid_lin(int plane) { int g = cdiv(plane, 256); return g > 2048 ? 2048 : (g < 1 ? 1 : g); }
 
 }  // namespace
@@ -835,7 +717,7 @@ int label8_raster(const uint8_t *mask, int N, int H, int W, int *L, int *aux, in
     const dim3 gl(grid_lin(plane), N);
     cc_init_kernel<1><<<gr, br, 0, st>>>(mask, 0, H, W, L);
     cc_merge_kernel<1, 8><<<gr, br, 0, st>>>(mask, 0, H, W, L);
-    cc_flatten_kernel<false><<<gr, br, 0, st>>>(H, W, L, nullptr);
+    cc_flatten_kernel<FLAT_PLAIN><<<gr, br, 0, st>>>(H, W, L, nullptr);
     cc_count_roots_kernel<<<dim3(nchunk, N), 256, 0, st>>>(L, plane, nchunk, chunk);
     cc_scan_chunks_kernel<<<N, 256, 0, st>>>(nchunk, chunk, counts);
     cc_rank_roots_kernel<<<dim3(nchunk, N), 256, 0, st>>>(L, plane, nchunk, chunk, aux);
@@ -996,14 +878,14 @@ extern "C" int cdnet_cc_chain(const uint8_t *pred, int fg_value, int N, int H, i
     // 1. fill holes: 4-connected components of the background; those touching the border stay background
     cc_init_kernel<0><<<gr, br, 0, st>>>(pred, fg_value, H, W, L);
     cc_merge_kernel<0, 4><<<gr, br, 0, st>>>(pred, fg_value, H, W, L);
-    cc_flatten_kernel<false><<<gr, br, 0, st>>>(H, W, L, nullptr);
+    cc_flatten_kernel<FLAT_PLAIN><<<gr, br, 0, st>>>(H, W, L, nullptr);
     fill_mark_border_kernel<<<dim3(cdiv(2 * (H + W), 256), N), 256, 0, st>>>(H, W, L);
     fill_output_kernel<<<gl, 256, 0, st>>>(pred, fg_value, plane, L, A);
     // 2. remove small objects: 4-connected components of A with their areas
     if (hipMemsetAsync(aux, 0, (size_t)N * plane * 4, st) != hipSuccess) return check_launch("memset area");
     cc_init_kernel<1><<<gr, br, 0, st>>>(A, 0, H, W, L);
     cc_merge_kernel<1, 4><<<gr, br, 0, st>>>(A, 0, H, W, L);
-    cc_flatten_kernel<true><<<gr, br, 0, st>>>(H, W, L, aux);
+    cc_flatten_kernel<FLAT_AREA><<<gr, br, 0, st>>>(H, W, L, aux);
     // 3. drop small components, add the diagonal unions (8-connectivity) among the survivors, number in raster order
     cc_diag_merge_kernel<<<gr, br, 0, st>>>(A, H, W, min_area, aux, L, B);
     cc_flatten_kept_kernel<<<gl, 256, 0, st>>>(B, plane, L);
@@ -1219,7 +1101,7 @@ void label4_roots(const uint8_t *mask, int N, int H, int W, int *L, hipStream_t 
     const dim3 gr = grid_rows(N, H, W), br(64, 4);
     cc_init_kernel<1><<<gr, br, 0, st>>>(mask, 0, H, W, L);
     cc_merge_kernel<1, 4><<<gr, br, 0, st>>>(mask, 0, H, W, L);
-    cc_flatten_kernel<false><<<gr, br, 0, st>>>(H, W, L, nullptr);
+    cc_flatten_kernel<FLAT_PLAIN><<<gr, br, 0, st>>>(H, W, L, nullptr);
 }
 
 }  // namespace
@@ -1257,7 +1139,7 @@ extern "C" int cdnet_watershed_process(const uint8_t *pred, int N, int H, int W,
     // 2. marker: fill holes, erode, label (raster numbering), drop small labels
     cc_init_kernel<0><<<gr, br, 0, st>>>(m, 1, H, W, L2);
     cc_merge_kernel<0, 4><<<gr, br, 0, st>>>(m, 1, H, W, L2);
-    cc_flatten_kernel<false><<<gr, br, 0, st>>>(H, W, L2, nullptr);
+    cc_flatten_kernel<FLAT_PLAIN><<<gr, br, 0, st>>>(H, W, L2, nullptr);
     fill_mark_border_kernel<<<dim3(cdiv(2 * (H + W), 256), N), 256, 0, st>>>(H, W, L2);
     fill_output_kernel<<<gl, 256, 0, st>>>(m, 1, plane, L2, m2);
     ws_erode4_kernel<<<gl, 256, 0, st>>>(m2, H, W, m);
@@ -1303,7 +1185,7 @@ extern "C" int cdnet_fill_label_process(const uint8_t *pred, int N, int H, int W
     // fill holes: 4-connected components of the background, those touching the border stay background
     cc_init_kernel<0><<<gr, br, 0, st>>>(m, 1, H, W, L2);
     cc_merge_kernel<0, 4><<<gr, br, 0, st>>>(m, 1, H, W, L2);
-    cc_flatten_kernel<false><<<gr, br, 0, st>>>(H, W, L2, nullptr);
+    cc_flatten_kernel<FLAT_PLAIN><<<gr, br, 0, st>>>(H, W, L2, nullptr);
     fill_mark_border_kernel<<<dim3(cdiv(2 * (H + W), 256), N), 256, 0, st>>>(H, W, L2);
     fill_output_kernel<<<gl, 256, 0, st>>>(m, 1, plane, L2, m2);
     label4_roots(m2, N, H, W, L2, st);

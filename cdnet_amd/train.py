@@ -25,10 +25,10 @@ from .options import Options
 class _SyntheticLoader:
     """`n` batches of the SURVEY 8d recipe in the sample layout of the reference's DataLoader"""
 
-    def __init__(self, n_batches, batch, dev, seed):
+    def __init__(self, n_batches, batch, dev, seed, size=256):
         self.items = []
         for k in range(n_batches):
-            x, lab, dirn, point, weight = synth.synthetic_batch(batch, dev, seed=seed + k)
+            x, lab, dirn, point, weight = synth.synthetic_batch(batch, dev, seed=seed + k, H=size, W=size)
             target0 = (lab.to(torch.int64) * 127 + (lab == 2).to(torch.int64)).unsqueeze(1)      # {0,127,255} as ToTensor emits
             self.items.append((x, weight.unsqueeze(1), target0, point, dirn))
 

@@ -6,7 +6,7 @@ gradient / Adam buffers and runs forward, the fused 5-term loss, backward and th
 `criterion` is accepted and ignored (the NLL / dice / MSE terms live in `cdnet_dam_loss`).  A sample is the reference's
 tuple (input f32 [B,3,H,W], weight_map u8 [B,1,H,W], target0 [B,1,H,W] with values {0,127/128,255} or [B,3,H,W] one-hot
 colours, target_point0 f16 [B,H,W], target_direction0 [B,H,W]) as `get_transforms` emits it (:71-142).
-Returns `results.avg`: [loss, loss_direction_CE, loss_direction_dice, loss_mse, loss_CE, loss_var (= -1, alpha = 0),
+Returns `results.avg`: [loss, loss_direction_CE, loss_direction_dice, loss_mse, loss_CE, loss_var (-1 with alpha = 0),
 pixel_accu, pixel_iou, pixel_recall, pixel_precision, pixel_F1] (:294-299, :339)."""
 import numpy as np
 import torch
@@ -38,9 +38,16 @@ def _label3(target0, boundary=2):
 def _check_branches(opt, model):
     """the option combinations the reference's loops accept for the model at hand (train_util_dam.py:152-166): three outputs ->
     direction = 1 and mseloss = 1 (the defaults); the two-output ablation models (mask + direction) -> direction = 1 and mseloss = 0
-    (with mseloss = 1 the reference would read the direction logits as the point map).  alpha = 0: no variance term."""
+    (with mseloss = 1 the reference would read the direction logits as the point map).  alpha = 0: no variance term; alpha = 1: loss_CE +
+    the instance variance term (:174-180, cdnet_variance_loss).  Every other value raises: the reference ignores it silently (:191-193),
+    except 2, its "variance instead of cross-entropy" (:182-189), which is not built here."""
     two = getattr(model, 'VARIANT', 'rev1') == 'MandD'
-    assert opt.model['direction'] == 1 and opt.train['alpha'] == 0, 'the fused loss implements direction = 1, alpha = 0'
+    alpha = opt.train['alpha']
+    if alpha not in (0, 1):
+        raise ValueError('alpha = %r: 0 (no variance term) or 1 (loss_CE + loss_var) are built%s' % (
+            alpha, '; alpha = 2 (the variance term instead of the cross-entropy) would need the cross-entropy gradient taken out of the '
+                   'fused loss kernel and is out of scope' if alpha == 2 else ''))
+    assert opt.model['direction'] == 1, 'the fused loss implements direction = 1'
     if two:
         assert opt.model['mseloss'] in (0, 1), opt.model['mseloss']       # 0 is the reference's setting; 1 is tolerated (no point term either way)
     else:
@@ -61,16 +68,17 @@ def train(train_loader, model, optimizer, criterion, epoch, opt, logger, get_pro
         losses = trainer.train_step(input.to(dev).float(), label.contiguous(), target_direction0.to(dev).to(torch.uint8).contiguous(),
                                     target_point0.to(dev).to(torch.float16).contiguous(), w)
         r = losses.detach().cpu().numpy().astype(np.float64)
-        r[5] = -1.0                                        # loss_var = torch.ones(1) * -1 when alpha == 0 (:249-251)
+        # slot 5 of the device tensor is the dice term; the reference logs loss_var there: torch.ones(1) * -1 when alpha == 0 (:191-193)
+        r[5] = float(trainer.loss_var.item()) if opt.train['alpha'] == 1 else -1.0
         results.update(r, input.size(0))
         if i % opt.train['log_interval'] == 0 and logger is not None:
             logger.info('\tIteration: [{:d}/{:d}]\tLoss {r[0]:.4f}\tloss_direction_CE {r[1]:.4f}\tloss_direction_dice {r[2]:.4f}'
-                        '\tloss_mse {r[3]:.4f}\tLoss_CE {r[4]:.4f}\tPixel_Accu {r[6]:.4f}\tpixel_IoU {r[7]:.4f}'
+                        '\tloss_mse {r[3]:.4f}\tLoss_CE {r[4]:.4f}\tLoss_var {r[5]:.4f}\tPixel_Accu {r[6]:.4f}\tpixel_IoU {r[7]:.4f}'
                         .format(i, len(train_loader), r=results.avg))
     if getattr(trainer, 'world', 1) > 1:
         results.avg = trainer.reduce_scalars(results.avg)         # global-batch means, as DataParallel's gathered loss gives
     if logger is not None:
-        logger.info('\t=> Train Avg: Loss {r[0]:.4f}\tloss_CE {r[4]:.4f}\tPixel_Accu {r[6]:.4f}\tIoU {r[7]:.4f}'.format(r=results.avg))
+        logger.info('\t=> Train Avg: Loss {r[0]:.4f}\tloss_CE {r[4]:.4f}\tLoss_var {r[5]:.4f}\tPixel_Accu {r[6]:.4f}\tIoU {r[7]:.4f}'.format(r=results.avg))
     return results.avg
 
 

@@ -134,6 +134,8 @@ class Trainer:
         self._bufs = {}
         self._wss = {}
         self.losses = torch.zeros((11,), dtype=torch.float32, device=self.dev)     # 6 loss values + 5 pixel metrics
+        self.alpha = 0.0                                   # 1: + the instance variance term (train_util_dam.py:174-180), cdnet_variance_loss
+        self.loss_var = torch.full((1,), -1.0, dtype=torch.float32, device=self.dev)       # -1 as long as the term is off (:192)
         self.tape = []
         self._cat_cache = {}
         self._wstream, self._events = None, {}
@@ -272,7 +274,19 @@ class Trainer:
                   _lib.ptr(dirlab.contiguous()), _lib.ptr(point_t.contiguous()), _lib.ptr(weight.contiguous()), B, H, W, ND,
                   self.quirk, _lib.ptr(ws), ws.numel(), _lib.ptr(self.losses), _lib.ptr(dmask),
                   _lib.ptr(dpoint), _lib.ptr(ddir), _lib.stream_ptr())
+        if self.alpha:
+            self._variance_term(mask, label, dmask)
         return dmask, dpoint, ddir
+
+    def _variance_term(self, mask, label, dmask):
+        """alpha = 1 (train_util_dam.py:174-180): loss_var of the mask logits into self.loss_var, added to losses[0] and its gradient to dmask"""
+        if self.alpha != 1:
+            raise ValueError('alpha = %r: the variance term is built for alpha = 1 (0 switches it off)' % (self.alpha,))
+        B, K, H, W = mask.shape
+        need = _lib.load().cdnet_variance_loss_workspace_bytes(B, K, H, W)
+        ws = self._ws('variance', (need + 3) // 4)
+        _lib.call('cdnet_variance_loss', _lib.ptr(mask), _lib.ptr(label.contiguous()), 1, B, K, H, W, float(self.alpha), _lib.ptr(ws),
+                  ws.numel() * 4, _lib.ptr(self.loss_var), _lib.ptr(self.losses[0:1]), _lib.ptr(dmask), None, None, _lib.stream_ptr())
 
     # ------------------------------------------------------------------------------------------------
     def backward(self, dmask, dpoint, ddir):
@@ -836,7 +850,7 @@ class Trainer:
         """x f32 [B,3,H,W]; label u8 [B,H,W] in {0,1,2}; dirlab u8 [B,H,W] 0..8; point_t f16 [B,H,W]; weight u8 [B,H,W]
         (the png weight map; /20 on the fly).  Returns the device tensor of 11 values: [total, direction CE, direction dice,
         MSE, CE, dice, pixel accuracy, IoU, recall, precision, F1] (train_util_dam.py:297-299; slot 5 holds the mask dice
-        term where the reference logs its unused variance term)."""
+        term where the reference logs its variance term; that one is `self.loss_var`, part of the total when alpha = 1)."""
         mask, point, direction = self.forward(x)
         dmask, dpoint, ddir = self.loss_and_grads(mask, point, direction, label, dirlab, point_t, weight)
         self.backward(dmask, dpoint, ddir)
@@ -865,6 +879,8 @@ class UNetTrainer(Trainer):
         dmask, _, _ = super().loss_and_grads(logits, point, dirn, label, dirlab, point_t, weight)
         self.unet_losses[1:3] = self.losses[4:6]
         self.unet_losses[0] = self.losses[4] + self.losses[5]
+        if self.alpha:
+            self.unet_losses[0] += self.loss_var[0]        # train_util.py: loss = loss_CE + alpha * loss_var (+ dice)
         return dmask
 
     def backward(self, dlogits):

@@ -174,6 +174,7 @@ def get_optimizer(args, model, world_size=1):
         raise ValueError('Optimizer {} not available'.format(args.train['optimizer']))
     trainer = trainer_class(model)(model, lr=args.train['lr'], weight_decay=args.train['weight_decay'], world_size=world_size,
                                    optimizer=name, momentum=getattr(args, 'momentum', 0.95))
+    trainer.alpha = float(args.train.get('alpha', 0.0))           # 1: + the instance variance term (train_util_dam.py:174-180)
     scheduler = None
     if args.train['scheduler'] in optim.SCHEDULERS:
         scheduler = optim.LRSchedule(args.train['scheduler'], args.train['lr'], step=args.train['step'], lr_decay=args.train['lr_decay'])

@@ -515,6 +515,20 @@ int cdnet_dam_loss_classes(const float *mask, const float *point, const float *d
                            int direction_classes, int quirk_sample0, float *workspace, size_t workspace_floats, float *losses,
                            float *dmask, float *dpoint, float *ddir, void *stream);
 
+/* The instance variance term of the training loss (--alpha 1).  Replaces train_util_dam.py:174-180: F.softmax of the mask logits, the per-sample
+ * skimage.measure.label(target == 1) on the CPU (8-connectivity) and LossVariance (loss.py:9-33), with the gradient autograd takes through both:
+ *   loss_var = (1/B) sum_k [ sum over the instances with n > 1 pixels and the K channels of  sum_i (p_ci - mu_c)^2 / (n - 1) ] / (U_k + 1e-8),
+ *   U_k = number of instances of sample k (single pixels included); a sample without foreground contributes 0.
+ * mask_logits f32 [B][K][H][W], K in {2, 3}; label u8 [B][H][W], an instance pixel is label == fg_value (1).
+ * loss_var f32 [1] is written; total (NULL or f32 [1]): *total += alpha * loss_var; dmask (NULL or f32 [B][K][H][W]): += alpha * d loss_var /
+ * d logits; root_out (NULL or i32 [B][H][W]): the raster-first pixel index (y * W + x) of the pixel's instance, -1 off the mask; counts (NULL
+ * or i32 [B]): U_k.  Bit-identical from call to call (fixed-point integer accumulation, fixed-order sums).  No host synchronisation: graph-capturable.
+ * workspace: cdnet_variance_loss_workspace_bytes(B, K, H, W) bytes, 8-byte aligned (0 for shapes / K the entry does not serve). */
+size_t cdnet_variance_loss_workspace_bytes(int B, int K, int H, int W);
+int cdnet_variance_loss(const float *mask_logits, const uint8_t *label, int fg_value, int B, int K, int H, int W, float alpha,
+                        void *workspace, size_t workspace_bytes, float *loss_var, float *total, float *dmask, int32_t *root_out,
+                        int32_t *counts, void *stream);
+
 /* validate() loss mix of train_util_dam.py:367-636 (default options): per-sample sums of ONE pass over the logits, combined on the
  * host by cdnet_amd.train_util_dam.validate.  sums f32 [B][CDNET_VAL_SUMS]:
  *   0..2 sum p_c [label==c], 3..5 sum p_c, 6..8 sum [label==c], 9 sum -log p_label (unweighted mask CE, :499-505);
