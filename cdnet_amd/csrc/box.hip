@@ -5,6 +5,7 @@
 //                    8-wave workgroup per CU; each workgroup stamps s_memtime (shader cycles) and s_memrealtime (constant 100 MHz) around its
 //                    loop: the in-kernel clock the chip holds under matrix load = d(memtime) / d(memrealtime) x 100 MHz
 #include "common.h"
+#include "launch.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -56,12 +57,6 @@ extern "C" int cdnet_box_mfma(const uint32_t *seed, float *sink, unsigned long l
                               void *stream) {
     CDNET_REQUIRE(seed && sink, "cdnet_box_mfma: null pointer");
     CDNET_REQUIRE(workgroups >= 1 && workgroups <= 4096 && waves_per_wg >= 1 && waves_per_wg <= 8 && iters >= 1, "cdnet_box_mfma: bad sizes");
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(box_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 65536) != hipSuccess)
-            return cdnet::check_launch("hipFuncSetAttribute(box_mfma)");
-        attr = true;
-    }
-    box_mfma_kernel<<<workgroups, waves_per_wg * 64, 65536, (hipStream_t)stream>>>(seed, sink, stamps, iters);
-    return cdnet::check_launch("cdnet_box_mfma");
+    return cdnet::launch_lds<box_mfma_kernel>(workgroups, waves_per_wg * 64, 65536, 65536, (hipStream_t)stream, "hipFuncSetAttribute(box_mfma)", "cdnet_box_mfma",
+                                              seed, sink, stamps, iters);
 }

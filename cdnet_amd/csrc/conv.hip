@@ -18,6 +18,7 @@
 #include <vector>
 #include "common.h"
 #include "conv_args.h"
+#include "launch.h"
 #include "xform.h"
 #include "stage16.h"
 #include <stdlib.h>
@@ -741,18 +742,10 @@ int launch_conv(const ConvArgs &A, hipStream_t st) {
     int ctot = 0;
     for (int i = 0; i < A.nsrc; ++i) ctot += A.src[i].C;
     const int smem = LDS::bytes(ctot);
-    auto kern = conv_fwd_kernel<TH, TW, CK, BN, WM, WN, TAPS>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS::bytes(XF_MAX)) != hipSuccess)
-            return check_launch("hipFuncSetAttribute(conv)");
-        attr_done = true;
-    }
     const int total_tiles = cdiv(A.W, TW) * cdiv(A.H, TH) * A.N * A.npar;
     const int ctiles = cdiv(A.Cout, BN);
     dim3 grid(total_tiles, ctiles, 1);
-    kern<<<grid, 256, smem, st>>>(A);
-    return check_launch("conv_fwd_kernel");
+    return launch_lds<conv_fwd_kernel<TH, TW, CK, BN, WM, WN, TAPS>>(grid, 256, LDS::bytes(XF_MAX), smem, st, "hipFuncSetAttribute(conv)", "conv_fwd_kernel", A);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1371,9 +1364,7 @@ int try_launch_conv_ws(const ConvArgs &A, hipStream_t st, bool dry_run = false) 
     for (int i = 0; i < A.nsrc; ++i) {
         if (A.src[i].pool || A.src[i].relu == 3) return -1;
         ctot += A.src[i].C;
-        // the movers' requests: 31-bit byte offsets from the source's base (bit 31 marks a zero-fill vector)
-        const long long rs_ = A.src[i].row_stride ? A.src[i].row_stride : (long long)A.src[i].Ws * A.src[i].C;
-        if ((long long)A.N * A.npar * A.src[i].Hs * rs_ * 2 >= (1LL << 31)) return -1;
+        if (!in_mover_reach(A.src[i], (long long)A.N * A.npar, 2)) return -1;
     }
 #ifdef CDNET_WS_STAMPS
     const int smem = L::bytes(4, ctot, 2) + 2 * 384 * 8;
@@ -1382,58 +1373,33 @@ int try_launch_conv_ws(const ConvArgs &A, hipStream_t st, bool dry_run = false) 
 #endif
     if (smem > 160 * 1024) return -1;
     const int T = (A.W / 16) * (A.H / 16) * A.N;
-    static int n_cu = 0;
-    if (n_cu == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return check_launch("hipGetDeviceProperties");
-        n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
+    int n_cu = 0;
+    if (const int rc = cu_count(&n_cu)) return rc;
     const int ctiles = cdiv(A.Cout, BN);
     // a persistent workgroup pays ~3 us of start-up (weights + first chunks): worth it from a few tiles' worth of chunks per workgroup on
     const int Gmax = n_cu / ctiles > 0 ? n_cu / ctiles : 1;
     // (few tiles but long channel loops - the 16x16-pixel bottleneck layers - still take it: the workgroups that exist keep the memory
     //  pipeline full, which the one-tile-per-workgroup kernel does not)
     // (12, not 16: the decoder's first block - 768 -> 256 channels on 16 tiles of 16 x 16 pixels, 64 workgroups either way - 120 us on the one-tile kernel)
-    if (!(A.debug & 64) && ((long long)T * A.nchunk < 12LL * Gmax || (T < Gmax && A.nchunk < 16))) return -1;
+    if (!(A.debug & CONV_DBG_PERSIST_SMALL) && ((long long)T * A.nchunk < 12LL * Gmax || (T < Gmax && A.nchunk < 16))) return -1;
     bool all_plain = true, all_fast = true;
     for (int i = 0; i < A.nsrc; ++i) {
         const ConvSrc &s = A.src[i];
         all_plain = all_plain && !s.scale && !s.relu && !s.res && !s.f16;
         all_fast = all_fast && s.scale && s.relu && !s.res && s.f16 == 1;
     }
-    int G = n_cu / ctiles;
-    G = G > T ? T : G;
-    if (G >= 8) G &= ~7;
-    if (G < 1) G = 1;
-    dim3 grid(G, ctiles, 1);
-    auto launch2 = [&](auto xf_c, auto st_c, auto sm_c) -> int {
-        constexpr int XF = decltype(xf_c)::value;
-        constexpr bool STATS = decltype(st_c)::value;
-        constexpr bool STREAM = decltype(sm_c)::value;
-        auto kern = conv_ws_kernel<BN, TAPS, XF, STATS, STREAM>;
-        static bool attr_done = false;
-        if (!attr_done) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                return check_launch("hipFuncSetAttribute(conv_ws)");
-            attr_done = true;
-        }
-        kern<<<grid, 512, smem, st>>>(A);
-        return CDNET_OK;
-    };
-    auto launch = [&](auto xf_c, auto st_c) -> int {
-        return stream ? launch2(xf_c, st_c, std::true_type{}) : launch2(xf_c, st_c, std::false_type{});
-    };
+    // (no test cap: conv_ws_kernel reads debug bits 512 and 1024 as ablations of its own)
+    dim3 grid(persistent_grid(n_cu, ctiles, T, 0, 0), ctiles, 1);
     const int xf = all_plain ? 0 : (all_fast ? 1 : 2);
     if (dry_run) return CDNET_OK;
-    using X0 = std::integral_constant<int, 0>;
-    using X1 = std::integral_constant<int, 1>;
-    using X2 = std::integral_constant<int, 2>;
-    int rc;
-    if (A.stats) rc = xf == 0 ? launch(X0{}, std::true_type{}) : (xf == 1 ? launch(X1{}, std::true_type{}) : launch(X2{}, std::true_type{}));
-    else rc = xf == 0 ? launch(X0{}, std::false_type{}) : (xf == 1 ? launch(X1{}, std::false_type{}) : launch(X2{}, std::false_type{}));
-    if (rc != CDNET_OK) return rc;
-    return check_launch("conv_ws_kernel");
+    return with_bool(A.stats != nullptr, [&](auto st_c) {
+        return with_int<0, 1, 2>(xf, [&](auto xf_c) {
+            return with_bool(stream, [&](auto sm_c) {
+                return launch_lds<conv_ws_kernel<BN, TAPS, decltype(xf_c)::value, decltype(st_c)::value, decltype(sm_c)::value>>(
+                    grid, 512, 160 * 1024, smem, st, "hipFuncSetAttribute(conv_ws)", "conv_ws_kernel", A);
+            });
+        });
+    });
 }
 
 template <int TAPS>
@@ -1645,7 +1611,7 @@ extern "C" int cdnet_conv_forward(const cdnet_conv_args *args, void *stream) {
         CDNET_REQUIRE(!padded, "cdnet_conv_forward: a padding chunk (nchunk = real + 1) runs on conv_ws16_kernel only (ask cdnet_conv_ws_eligible)");
     }
     static const int dbg = getenv("CDNET_CONV_DEBUG") ? atoi(getenv("CDNET_CONV_DEBUG")) : 0;
-    if (!(A.debug & 32) && A.taps == 9 && A.npar == 1 && A.ostride == 1 && A.tile == 16 && A.CK == 16 && (A.BN == 64 || A.BN == 32)) {
+    if (!(A.debug & CONV_DBG_ONE_TILE) && A.taps == 9 && A.npar == 1 && A.ostride == 1 && A.tile == 16 && A.CK == 16 && (A.BN == 64 || A.BN == 32)) {
         const int rc = A.BN == 64 ? try_launch_conv_ws<64, 9>(A, st) : try_launch_conv_ws<32, 9>(A, st);
         if (rc >= 0) return rc;
     }
@@ -1654,7 +1620,7 @@ extern "C" int cdnet_conv_forward(const cdnet_conv_args *args, void *stream) {
     CDNET_REQUIRE(A.ws != 2, "cdnet_conv_forward: the BatchNorm-backward statistics epilogue (ws = 2) exists in fp32 mode on conv_ws32_kernel only "
                              "(ask cdnet_conv_ws_eligible first)");
     if (dbg) { ConvArgs B = A; B.debug = dbg; if (B.taps == 9) return dispatch_conv<9>(B, st); }
-    if (A.debug & 32) { ConvArgs B = A; B.debug = 0; if (B.taps == 9) return dispatch_conv<9>(B, st); if (B.taps == 4) return dispatch_conv<4>(B, st); return dispatch_conv<1>(B, st); }
+    if (A.debug & CONV_DBG_ONE_TILE) { ConvArgs B = A; B.debug = 0; if (B.taps == 9) return dispatch_conv<9>(B, st); if (B.taps == 4) return dispatch_conv<4>(B, st); return dispatch_conv<1>(B, st); }
     if (A.taps == 9) return dispatch_conv<9>(A, st);
     if (A.taps == 4) return dispatch_conv<4>(A, st);
     return dispatch_conv<1>(A, st);
@@ -1668,7 +1634,7 @@ extern "C" int cdnet_conv_ws_eligible(const cdnet_conv_args *args) {
     if (A.f32) return (!A.dot_out && conv_forward_f32_ws(A, nullptr, true) == CDNET_OK) ? 1 : 0;
     if (conv_forward_ws16(A, nullptr, true) == CDNET_OK) return 2;
     if ((A.taps1 != 0 && A.taps1 != A.taps) || A.pool_out || A.dot_out) return 0;
-    if (A.debug & 32) return 0;
+    if (A.debug & CONV_DBG_ONE_TILE) return 0;
     if (!(A.taps == 9 && A.npar == 1 && A.ostride == 1 && A.tile == 16 && A.CK == 16 && (A.BN == 64 || A.BN == 32))) return 0;
     const int rc = A.BN == 64 ? try_launch_conv_ws<64, 9>(A, nullptr, true) : try_launch_conv_ws<32, 9>(A, nullptr, true);
     return rc == CDNET_OK ? 1 : 0;

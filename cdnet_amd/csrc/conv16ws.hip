@@ -34,6 +34,7 @@
 #include <type_traits>
 #include "common.h"
 #include "conv_args.h"
+#include "launch.h"
 #include "xform.h"
 #include "stage16.h"
 #include <stdlib.h>
@@ -949,8 +950,7 @@ static int try_launch_ws16(const ConvArgs &A, hipStream_t st, bool dry_run) {
         const ConvSrc &s = A.src[i];
         if (s.pool || s.relu < 0 || s.relu > 2) return -1;
         ctot += s.C;
-        const long long rs = s.row_stride ? s.row_stride : (long long)s.Ws * s.C;
-        if ((long long)A.N * s.Hs * rs * 2 >= (1LL << 31)) return -1;      // the movers' requests: 31-bit byte offsets
+        if (!in_mover_reach(s, A.N, 2)) return -1;
         all_plain = all_plain && !s.scale && !s.relu && !s.res && !s.f16;
     }
     const bool mix = A.taps1 == 1 && A.nsrc == 2;
@@ -972,24 +972,14 @@ static int try_launch_ws16(const ConvArgs &A, hipStream_t st, bool dry_run) {
     if (A.dot_out && (!out || stream || A.pool_out || A.Cout > BN || A.out_coff || !A.dot_w)) return -1;      // ... and so does the fused 1x1 classifier
     if (!A.out && !A.dot_out) return -1;
     const int T = (A.W / 16) * (A.H / 16) * A.N;
-    static int n_cu = 0;
-    if (n_cu == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return check_launch("hipGetDeviceProperties");
-        n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
+    int n_cu = 0;
+    if (const int rc = cu_count(&n_cu)) return rc;
     const int ctiles = cdiv(A.Cout, BN);
     const int Gmax = n_cu / ctiles > 0 ? n_cu / ctiles : 1;
     // a persistent workgroup pays a few microseconds of start-up and a serial epilogue for its last tile
-    if (!(A.debug & 64) && ((long long)T * nch < 16LL * Gmax || (T < Gmax && nch < 16))) return -1;
-    int G = n_cu / ctiles;
-    G = G > T ? T : G;
-    if (G >= 8) G &= ~7;
-    if ((A.debug >> 8) > 0 && (A.debug >> 8) < G) G = A.debug >> 8;      // tests: few workgroups, long runs of tiles
-    if (G < 1) G = 1;
+    if (!(A.debug & CONV_DBG_PERSIST_SMALL) && ((long long)T * nch < 16LL * Gmax || (T < Gmax && nch < 16))) return -1;
     if (dry_run) return CDNET_OK;
-    dim3 grid(G, ctiles, 1);
+    dim3 grid(persistent_grid(n_cu, ctiles, T, 0, A.debug >> CONV_DBG_GRID_SHIFT), ctiles, 1);
 #ifndef CDNET_WS16_PAIR_DEFAULT
 #define CDNET_WS16_PAIR_DEFAULT 1
 #endif
@@ -1006,15 +996,8 @@ static int try_launch_ws16(const ConvArgs &A, hipStream_t st, bool dry_run) {
                 // bound by power and does not gain (round 5, without spills and with pair requests: 74.0 vs 72.5 us at 16 tiles, 298 vs 297.5 us at
                 // 64 - profiles/HISTORY.md); the one-tap form spilled.
                 if constexpr (STREAM_) {
-                    auto kern_k = conv_ws16_kernel<BN, XF, STREAM_, MIX_, 0, 4, decltype(pf_c)::value, true, true, PAIR_>;
-                    static bool attr_k = false;
-                    if (!attr_k) {
-                        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern_k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                            return check_launch("hipFuncSetAttribute(conv_ws16 k32)");
-                        attr_k = true;
-                    }
-                    kern_k<<<grid, 512, smem, st>>>(A);
-                    return check_launch("conv_ws16_kernel(k32)");
+                    return launch_lds<conv_ws16_kernel<BN, XF, STREAM_, MIX_, 0, 4, decltype(pf_c)::value, true, true, PAIR_>>(
+                        grid, 512, 160 * 1024, smem, st, "hipFuncSetAttribute(conv_ws16 k32)", "conv_ws16_kernel(k32)", A);
                 }
 #ifndef CDNET_WS16_QUAD_DEFAULT
 #define CDNET_WS16_QUAD_DEFAULT 1
@@ -1024,26 +1007,12 @@ static int try_launch_ws16(const ConvArgs &A, hipStream_t st, bool dry_run) {
                 // 64 tiles (1.32 -> 1.14 x the algorithmic traffic), the launch time unchanged on a box bound by power (310 vs 302-309 us); at 16
                 // tiles, where the L2 / Infinity Cache keep the line between its two pairs anyway, the pair form is 1-2 % faster and stays
                 const long long io_bytes = 2LL * A.N * A.H * A.W * (ctot + A.Cout);
-                if constexpr (!STREAM_ && PAIR_ && CDNET_WS16_QUAD_DEFAULT != 0) if (!(n0 & 3) && !(n1 & 3) && (io_bytes >= (512LL << 20) || (A.debug & 16))) {      // (debug bit 16: tests - the quad form on small launches)
-                    auto kern_q = conv_ws16_kernel<BN, XF, STREAM_, MIX_, 0, 4, decltype(pf_c)::value, true, false, true, true>;
-                    static bool attr_q = false;
-                    if (!attr_q) {
-                        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern_q), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                            return check_launch("hipFuncSetAttribute(conv_ws16 quad)");
-                        attr_q = true;
-                    }
-                    kern_q<<<grid, 512, smem, st>>>(A);
-                    return check_launch("conv_ws16_kernel(quad)");
+                if constexpr (!STREAM_ && PAIR_ && CDNET_WS16_QUAD_DEFAULT != 0) if (!(n0 & 3) && !(n1 & 3) && (io_bytes >= (512LL << 20) || (A.debug & CONV_DBG_WS16_QUAD))) {      // (tests: the quad form on small launches)
+                    return launch_lds<conv_ws16_kernel<BN, XF, STREAM_, MIX_, 0, 4, decltype(pf_c)::value, true, false, true, true>>(
+                        grid, 512, 160 * 1024, smem, st, "hipFuncSetAttribute(conv_ws16 quad)", "conv_ws16_kernel(quad)", A);
                 }
-                auto kern_o = conv_ws16_kernel<BN, XF, STREAM_, MIX_, 0, 4, decltype(pf_c)::value, true, false, PAIR_>;
-                static bool attr_o = false;
-                if (!attr_o) {
-                    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern_o), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                        return check_launch("hipFuncSetAttribute(conv_ws16 out)");
-                    attr_o = true;
-                }
-                kern_o<<<grid, 512, smem, st>>>(A);
-                return check_launch("conv_ws16_kernel(out)");
+                return launch_lds<conv_ws16_kernel<BN, XF, STREAM_, MIX_, 0, 4, decltype(pf_c)::value, true, false, PAIR_>>(
+                    grid, 512, 160 * 1024, smem, st, "hipFuncSetAttribute(conv_ws16 out)", "conv_ws16_kernel(out)", A);
             }
         }
         constexpr bool STREAM = decltype(sm_c)::value;
@@ -1051,26 +1020,15 @@ static int try_launch_ws16(const ConvArgs &A, hipStream_t st, bool dry_run) {
         constexpr int NCS = decltype(ncs_c)::value;
         constexpr int PFD = decltype(pf_c)::value;
         constexpr int NS = 4;
-        auto kern = conv_ws16_kernel<BN, XF, STREAM, MIX, NCS, NS, PFD, false>;
-        static bool attr_done = false;
-        if (!attr_done) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                return check_launch("hipFuncSetAttribute(conv_ws16)");
-            attr_done = true;
-        }
-        kern<<<grid, 512, smem, st>>>(A);
-        return check_launch("conv_ws16_kernel");
+        return launch_lds<conv_ws16_kernel<BN, XF, STREAM, MIX, NCS, NS, PFD, false>>(grid, 512, 160 * 1024, smem, st, "hipFuncSetAttribute(conv_ws16)", "conv_ws16_kernel", A);
     };
-    using X0 = std::integral_constant<int, 0>;
-    using X2 = std::integral_constant<int, 2>;
     using C0 = std::integral_constant<int, 0>;
     using C1 = std::integral_constant<int, 1>;
     using C2 = std::integral_constant<int, 2>;
     using F_ = std::false_type;
     using T_ = std::true_type;
     auto by_xf = [&](auto sm_c, auto mx_c, auto ncs_c) -> int {
-        if (!all_plain) return go(X2{}, sm_c, mx_c, ncs_c, std::integral_constant<int, 4>{});
-        return go(X0{}, sm_c, mx_c, ncs_c, std::integral_constant<int, 4>{});
+        return with_int<2, 0>(all_plain ? 0 : 2, [&](auto xf_c) { return go(xf_c, sm_c, mx_c, ncs_c, std::integral_constant<int, 4>{}); });
     };
     if (stream) return by_xf(T_{}, F_{}, C0{});                  // (an even chunk count >= 6)
     if (mix) return by_xf(F_{}, T_{}, C0{});
@@ -1081,7 +1039,7 @@ static int try_launch_ws16(const ConvArgs &A, hipStream_t st, bool dry_run) {
 
 // called by cdnet_conv_forward first (16-bit path); -1 = not eligible
 int conv_forward_ws16(const ConvArgs &A, hipStream_t st, bool dry_run) {
-    if ((A.debug & 32) || (A.debug & 128)) return -1;      // (128: tests - the older persistent kernel instead)
+    if (A.debug & (CONV_DBG_ONE_TILE | CONV_DBG_OLD_WS16)) return -1;
     if (A.f32 || A.taps != 9 || A.npar != 1 || A.ostride != 1 || A.tile != 16 || A.CK != 16 || A.eres || A.ws || A.stats || A.oscale || A.out_f16) return -1;
     if (A.H % 16 != 0 || A.W % 16 != 0 || A.nchunk < 1 || A.Cout % 16 != 0) return -1;
     if (A.BN == 64) return try_launch_ws16<64>(A, st, dry_run);

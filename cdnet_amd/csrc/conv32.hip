@@ -15,6 +15,7 @@
 #include <type_traits>
 #include "common.h"
 #include "conv_args.h"
+#include "launch.h"
 #include <stdlib.h>
 
 using namespace cdnet;
@@ -419,16 +420,8 @@ int launch_conv32(const ConvArgs &A, hipStream_t st) {
     int ctot = 0;
     for (int i = 0; i < A.nsrc; ++i) ctot += A.src[i].C;
     const int smem = L::bytes(ctot);
-    auto kern = conv_f32_kernel<TH, TW, BN, WM, WN, TAPS>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, L::bytes(XF_MAX)) != hipSuccess)
-            return check_launch("hipFuncSetAttribute(conv32)");
-        attr_done = true;
-    }
     dim3 grid(cdiv(A.W, TW) * cdiv(A.H, TH) * A.N * A.npar, cdiv(A.Cout, BN), 1);
-    kern<<<grid, 256, smem, st>>>(A);
-    return check_launch("conv_f32_kernel");
+    return launch_lds<conv_f32_kernel<TH, TW, BN, WM, WN, TAPS>>(grid, 256, L::bytes(XF_MAX), smem, st, "hipFuncSetAttribute(conv32)", "conv_f32_kernel", A);
 }
 
 template <int TAPS>
@@ -614,13 +607,8 @@ __global__ __launch_bounds__(256, 4) void conv1x1_f32_stream_kernel(ConvArgs A) 
 
 template <int BN, int NCH>
 int launch_conv1x1_stream(const ConvArgs &A, hipStream_t st) {
-    static int n_cu = 0;
-    if (n_cu == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return check_launch("hipGetDeviceProperties");
-        n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
+    int n_cu = 0;
+    if (const int rc = cu_count(&n_cu)) return rc;
     // sixteen waves per CU are resident; every wave gets the same number of pixel blocks, give or take one
     const long long nblk = ((long long)A.N * A.H * A.W + 31) / 32;
     const int ctiles = cdiv(A.Cout, BN);
@@ -628,17 +616,17 @@ int launch_conv1x1_stream(const ConvArgs &A, hipStream_t st) {
     const long long rounds = (nblk + waves - 1) / waves;
     const long long G = ((nblk + rounds - 1) / rounds + 3) / 4;
     dim3 grid((unsigned)G, ctiles, 1);
-    const bool xf = A.src[0].scale != nullptr, er = A.eres != nullptr;
-    if (xf && er) conv1x1_f32_stream_kernel<BN, NCH, true, true><<<grid, 256, 0, st>>>(A);
-    else if (xf) conv1x1_f32_stream_kernel<BN, NCH, true, false><<<grid, 256, 0, st>>>(A);
-    else if (er) conv1x1_f32_stream_kernel<BN, NCH, false, true><<<grid, 256, 0, st>>>(A);
-    else conv1x1_f32_stream_kernel<BN, NCH, false, false><<<grid, 256, 0, st>>>(A);
-    return check_launch("conv1x1_f32_stream_kernel");
+    return with_bool(A.src[0].scale != nullptr, [&](auto xf_c) {
+        return with_bool(A.eres != nullptr, [&](auto er_c) {
+            conv1x1_f32_stream_kernel<BN, NCH, decltype(xf_c)::value, decltype(er_c)::value><<<grid, 256, 0, st>>>(A);
+            return check_launch("conv1x1_f32_stream_kernel");
+        });
+    });
 }
 
 // -1 = not this kernel's launch (the caller goes on to conv_f32_kernel)
 int try_conv1x1_stream(const ConvArgs &A, hipStream_t st) {
-    if (A.debug & 256) return -1;                                 // tests / A-B: conv_f32_kernel instead
+    if (A.debug & CONV_DBG_NO_STREAM_1X1) return -1;                                 // tests / A-B: conv_f32_kernel instead
     if (A.taps != 1 || A.taps1 != 0 || A.npar != 1 || A.ostride != 1 || A.ws || A.stats || A.pool_out || A.nsrc != 1) return -1;
     const ConvSrc &s = A.src[0];
     if (s.off_y || s.off_x || s.Hs != A.H || s.Ws != A.W || (s.row_stride && s.row_stride != s.Ws * s.C) || s.pool || s.res) return -1;

@@ -30,6 +30,7 @@
 #include <type_traits>
 #include "common.h"
 #include "conv_args.h"
+#include "launch.h"
 #include <stdlib.h>
 
 using namespace cdnet;
@@ -755,9 +756,7 @@ static int try_launch_ws32(const ConvArgs &A, hipStream_t st, bool dry_run) {
     for (int i = 0; i < A.nsrc; ++i) {
         if (A.src[i].pool) return -1;
         ctot += A.src[i].C;
-        // the movers' requests: 31-bit byte offsets from the source's base (bit 31 marks a zero-fill vector)
-        const long long rs = A.src[i].row_stride ? A.src[i].row_stride : (long long)A.src[i].Ws * A.src[i].C;
-        if ((long long)A.N * A.src[i].Hs * rs * 4 >= (1LL << 31)) return -1;
+        if (!in_mover_reach(A.src[i], A.N, 4)) return -1;
     }
     const bool bns = A.ws == 2;
     const bool mix = A.taps1 == 1 && A.nsrc == 2;
@@ -767,44 +766,26 @@ static int try_launch_ws32(const ConvArgs &A, hipStream_t st, bool dry_run) {
     const int smem = L::bytes(ctot, bns);
     if (smem > 160 * 1024) return -1;
     const int T = (A.W / 16) * (A.H / 16) * A.N;
-    static int n_cu = 0;
-    if (n_cu == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return check_launch("hipGetDeviceProperties");
-        n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
+    int n_cu = 0;
+    if (const int rc = cu_count(&n_cu)) return rc;
     const int ctiles = cdiv(A.Cout, BN);
     const int Gmax = n_cu / ctiles > 0 ? n_cu / ctiles : 1;
     // a persistent workgroup pays a few microseconds of start-up and a serial epilogue for its last tile: worth it from a few tiles'
     // worth of chunk intervals per workgroup on
-    if (!(A.debug & 64) && (long long)T * A.nchunk < 16LL * Gmax) return -1;
+    if (!(A.debug & CONV_DBG_PERSIST_SMALL) && (long long)T * A.nchunk < 16LL * Gmax) return -1;
     bool all_plain = true, all_fast = true;
     for (int i = 0; i < A.nsrc; ++i) {
         const ConvSrc &s = A.src[i];
         all_plain = all_plain && !s.scale && !s.relu && !s.res;
         all_fast = all_fast && s.scale && s.shift && s.relu == 1 && !s.res;
     }
-    int G = n_cu / ctiles;
-    G = G > T ? T : G;
-    if (bns && G > 256) G = 256;                                  // ws == 2 writes 4 * G partial rows into the caller's CDNET_BNS_PARTIAL_ROWS = 1024
-    if (G >= 8) G &= ~7;
-    if ((A.debug >> 8) > 0 && (A.debug >> 8) < G) G = A.debug >> 8;      // tests: few workgroups, long runs of tiles
-    if (G < 1) G = 1;
-    dim3 grid(G, ctiles, 1);
+    // (ws == 2 writes 4 * G partial rows into the caller's CDNET_BNS_PARTIAL_ROWS = 1024: at most 256 workgroups)
+    dim3 grid(persistent_grid(n_cu, ctiles, T, bns ? 256 : 0, A.debug >> CONV_DBG_GRID_SHIFT), ctiles, 1);
     auto launch_n = [&](auto xf_c, auto st_c, auto ncs_c) -> int {
         constexpr int XF = decltype(xf_c)::value;
         constexpr bool STATS = decltype(st_c)::value;
         constexpr int NCS = decltype(ncs_c)::value;
-        auto kern = conv_ws32_kernel<BN, XF, STATS, false, NCS>;
-        static bool attr_done = false;
-        if (!attr_done) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                return check_launch("hipFuncSetAttribute(conv_ws32)");
-            attr_done = true;
-        }
-        kern<<<grid, 512, smem, st>>>(A);
-        return check_launch("conv_ws32_kernel");
+        return launch_lds<conv_ws32_kernel<BN, XF, STATS, false, NCS>>(grid, 512, 160 * 1024, smem, st, "hipFuncSetAttribute(conv_ws32)", "conv_ws32_kernel", A);
     };
     auto launch = [&](auto xf_c, auto st_c) -> int {
         // tiles of one / two or three chunks (16- to 48-channel inputs): their own instantiations, and only for the source forms that
@@ -817,68 +798,35 @@ static int try_launch_ws32(const ConvArgs &A, hipStream_t st, bool dry_run) {
         }
         return -1;
     };
-    using X0 = std::integral_constant<int, 0>;
-    using X1 = std::integral_constant<int, 1>;
-    using X2 = std::integral_constant<int, 2>;
     const int xf = all_plain ? 0 : (all_fast ? 1 : 2);
     if (A.nchunk < 4 && (BN != 64 || xf == 2)) return -1;          // (no small-tile instantiation for these)
     const bool pool = A.pool_out != nullptr;
     if (pool && (BN != 64 || bns || mix || A.stats || A.nchunk < 4 || xf != 0 || !A.orelu || A.out_coff || A.out_cstride != A.Cout)) return -1;
     if (dry_run) return CDNET_OK;
-    if (pool) {
-        if constexpr (BN == 64) {
-            auto kern = conv_ws32_kernel<64, 0, false, false, 0, false, true>;
-            static bool attr_done = false;
-            if (!attr_done) {
-                if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                    return check_launch("hipFuncSetAttribute(conv_ws32 pool)");
-                attr_done = true;
-            }
-            kern<<<grid, 512, smem, st>>>(A);
-            return check_launch("conv_ws32_kernel(pool)");
-        }
-        return -1;
-    }
     if (bns) {
         if constexpr (BN == 64) {
-            auto launch_bns = [&](auto xf_c) -> int {
-                constexpr int XF = decltype(xf_c)::value;
-                auto kern = conv_ws32_kernel<64, XF, false, true>;
-                static bool attr_done = false;
-                if (!attr_done) {
-                    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                        return check_launch("hipFuncSetAttribute(conv_ws32 bns)");
-                    attr_done = true;
-                }
-                kern<<<grid, 512, smem, st>>>(A);
-                return check_launch("conv_ws32_kernel(bns)");
-            };
-            return xf == 0 ? launch_bns(X0{}) : (xf == 1 ? launch_bns(X1{}) : launch_bns(X2{}));
+            return with_int<0, 1, 2>(xf, [&](auto xf_c) {
+                return launch_lds<conv_ws32_kernel<64, decltype(xf_c)::value, false, true>>(grid, 512, 160 * 1024, smem, st, "hipFuncSetAttribute(conv_ws32 bns)", "conv_ws32_kernel(bns)", A);
+            });
         }
         return -1;
     }
     if (mix) {
-        auto launch_mix = [&](auto xf_c) -> int {
-            constexpr int XF = decltype(xf_c)::value;
-            auto kern = conv_ws32_kernel<BN, XF, false, false, 0, true>;
-            static bool attr_done = false;
-            if (!attr_done) {
-                if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                    return check_launch("hipFuncSetAttribute(conv_ws32 mix)");
-                attr_done = true;
-            }
-            kern<<<grid, 512, smem, st>>>(A);
-            return check_launch("conv_ws32_kernel(mix)");
-        };
-        return xf == 0 ? launch_mix(X0{}) : launch_mix(X2{});
+        // (the one-tap second source exists for the plain and the generic transform only: the fast one runs as generic)
+        return with_int<0, 2>(xf == 1 ? 2 : xf, [&](auto xf_c) {
+            return launch_lds<conv_ws32_kernel<BN, decltype(xf_c)::value, false, false, 0, true>>(grid, 512, 160 * 1024, smem, st, "hipFuncSetAttribute(conv_ws32 mix)", "conv_ws32_kernel(mix)", A);
+        });
     }
-    if (A.stats) return xf == 0 ? launch(X0{}, std::true_type{}) : (xf == 1 ? launch(X1{}, std::true_type{}) : launch(X2{}, std::true_type{}));
-    return xf == 0 ? launch(X0{}, std::false_type{}) : (xf == 1 ? launch(X1{}, std::false_type{}) : launch(X2{}, std::false_type{}));
+    if (!pool) return with_bool(A.stats != nullptr, [&](auto st_c) { return with_int<0, 1, 2>(xf, [&](auto xf_c) { return launch(xf_c, st_c); }); });
+    if constexpr (BN == 64) {
+        return launch_lds<conv_ws32_kernel<64, 0, false, false, 0, false, true>>(grid, 512, 160 * 1024, smem, st, "hipFuncSetAttribute(conv_ws32 pool)", "conv_ws32_kernel(pool)", A);
+    }
+    return -1;
 }
 
 // called by conv_forward_f32 first; -1 = not eligible (the caller falls back to conv_f32_kernel)
 int conv_forward_f32_ws(const ConvArgs &A, hipStream_t st, bool dry_run) {
-    if (A.debug & 32) return -1;
+    if (A.debug & CONV_DBG_ONE_TILE) return -1;
     if (A.taps != 9 || A.npar != 1 || A.ostride != 1 || A.tile != 16 || A.CK != 16 || (A.eres && A.ws != 2) || (A.ws && A.ws != 2)) return -1;
     if (A.taps1 != 0 && A.taps1 != 9 && !(A.taps1 == 1 && A.nsrc == 2)) return -1;
     if (A.H % 16 != 0 || A.W % 16 != 0 || A.nchunk < (A.ws == 2 ? 4 : 1)) return -1;

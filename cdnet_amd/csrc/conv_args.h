@@ -38,6 +38,38 @@ struct ConvArgs {
     float *dot_out;
 };
 
+// Kernel-selection bits of cdnet_conv_args.debug, read by the host code (0 in production; the tests and tools pass the literals).
+// The lower bits, and 512 / 1024 in conv_ws_kernel, are ablations read inside the kernels (tools/bench_conv*.py) and keep their literals.
+//
+//   bit(s)   read by                                      meaning
+//   16       conv16ws.hip, launcher                       conv_ws16_kernel's quad-request form whatever the launch's size
+//            (in kernels: conv_fwd_kernel - dispatch-order ablation; conv_f32_kernel / store_tile_f32 - the general epilogue
+//             on full tiles too, for the tests that compare the two epilogues)
+//   32       conv.hip, conv32ws.hip, conv16ws.hip         the one-tile kernels only (conv_fwd_kernel / conv_f32_kernel)
+//   64       the three persistent launchers               the persistent kernel on small launches too
+//   128      conv16ws.hip                                 conv_ws_kernel, the older 16-bit persistent kernel, instead of conv_ws16_kernel
+//   256      conv32.hip, try_conv1x1_stream               conv_f32_kernel instead of conv1x1_f32_stream_kernel
+//   >> 8     conv32ws.hip, conv16ws.hip                   at most (debug >> 8) workgroups per output-channel tile
+//
+// 256 is also the lowest bit of the workgroup cap: debug = 256 caps a persistent launch of conv_ws32_kernel / conv_ws16_kernel at one
+// workgroup.  The two never meet - 256 is read for one-tap fp32 launches, the persistent kernels are nine-tap.  conv_ws_kernel reads
+// 512 and 1024 as ablations of its own, so its launcher applies no cap.
+enum : int {
+    CONV_DBG_WS16_QUAD = 16,
+    CONV_DBG_ONE_TILE = 32,
+    CONV_DBG_PERSIST_SMALL = 64,
+    CONV_DBG_OLD_WS16 = 128,
+    CONV_DBG_NO_STREAM_1X1 = 256,
+    CONV_DBG_GRID_SHIFT = 8,
+};
+// ... and of WgradArgs.debug (env CDNET_WGRAD_DEBUG; 1, 2, 4 are ablations inside the kernels), read by wgrad.hip's launchers:
+//   8        the 8-wave kernels instead of the wave-specialised ones (wgrad_kernel for wgrad_ws_kernel, wgrad_f32_kernel for wgrad_ws32_kernel)
+//   16       no small-channel forms: all four quadrants (QM = 0) in the fp32 kernels, the 32 x 128 form instead of wgrad_ws_kernel<1, 1>
+enum : int {
+    WGRAD_DBG_NO_WS = 8,
+    WGRAD_DBG_ALL_QUADS = 16,
+};
+
 static_assert(sizeof(ConvSrc) == sizeof(cdnet_conv_src), "ConvSrc layout");
 static_assert(sizeof(ConvArgs) == sizeof(cdnet_conv_args), "ConvArgs layout");
 

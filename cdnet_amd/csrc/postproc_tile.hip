@@ -14,6 +14,7 @@
 // Same arithmetic, expression by expression, as probmaps_kernel / ddm_codes_kernel / boost_argmax_kernel / the cc_* kernels of postproc.hip:
 // results are bit-identical to that chain (tests/test_gpu_tile_postproc.py) and to the CPU oracle.
 #include "common.h"
+#include "launch.h"
 
 using namespace cdnet;
 
@@ -775,16 +776,7 @@ namespace cdnet {
 bool label8_tile(const uint8_t *mask, int N, int H, int W, int32_t *labels, int32_t *counts, hipStream_t st, int *rc) {
     if (N <= 0 || W % 64 != 0 || (long long)H * W > 65536 || (((size_t)labels) & 15) != 0 || (((size_t)mask) & 15) != 0) return false;
     constexpr int SMEM = 131072 + 8192 + 64 * 4;
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(tile_label8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM) != hipSuccess) {
-            *rc = check_launch("hipFuncSetAttribute(tile_label8)");
-            return true;
-        }
-        attr = true;
-    }
-    tile_label8_kernel<<<N, 1024, SMEM, st>>>(mask, H, W, labels, counts);
-    *rc = check_launch("tile_label8_kernel");
+    *rc = launch_lds<tile_label8_kernel>(N, 1024, SMEM, SMEM, st, "hipFuncSetAttribute(tile_label8)", "tile_label8_kernel", mask, H, W, labels, counts);
     return true;
 }
 }  // namespace cdnet

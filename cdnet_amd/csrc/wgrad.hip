@@ -15,6 +15,7 @@
 #include <type_traits>
 #include "common.h"
 #include "conv_args.h"
+#include "launch.h"
 #include "xform.h"
 
 using namespace cdnet;
@@ -54,7 +55,7 @@ struct WgradArgs {
     int Cout;
     int taps, npar, ostride;
     int ksplit;
-    int debug;                // ablation bits for tools/bench_wgrad.py (env CDNET_WGRAD_DEBUG): 1 no MFMA loop, 2 no loads, 4 no LDS staging
+    int debug;                // ablation bits for tools/bench_wgrad.py (env CDNET_WGRAD_DEBUG): 1 no MFMA loop, 2 no loads, 4 no LDS staging; 8, 16: WGRAD_DBG_* (conv_args.h)
 };
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));   // register staging type (HIP's uint4 struct copies defeat SROA)
@@ -1441,16 +1442,8 @@ template <int CI_T, int CO_T, int TAPS, bool RES, int XF>
 int launch_wgrad_ws(const WgradArgs &A, hipStream_t st) {
     constexpr int CI = CI_T * 32, CO = CO_T * 32;
     constexpr int smem = 2 * (NPIX_A * pstride(CI) + NPIX_G * pstride(CO));
-    auto kern = wgrad_ws_kernel<CI_T, CO_T, TAPS, RES, XF>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-            return check_launch("hipFuncSetAttribute(wgrad_ws)");
-        attr_done = true;
-    }
     dim3 grid(cdiv(A.src.C, CI) * cdiv(A.Cout, CO), A.npar, A.ksplit);
-    kern<<<grid, NT, smem, st>>>(A);
-    return check_launch("wgrad_ws_kernel");
+    return launch_lds<wgrad_ws_kernel<CI_T, CO_T, TAPS, RES, XF>>(grid, NT, smem, smem, st, "hipFuncSetAttribute(wgrad_ws)", "wgrad_ws_kernel", A);
 }
 
 template <int CI_T, int CO_T, int TAPS, bool RES>
@@ -1459,16 +1452,8 @@ int launch_wgrad_gen(const WgradArgs &A, hipStream_t st) {
     constexpr int stage_bytes = NPIX_A * pstride(CI) + NPIX_G * pstride(CO);
     constexpr int fold_bytes = 4 * TAPS * 16 * 64 * 4;
     constexpr int smem = 2 * stage_bytes > fold_bytes ? 2 * stage_bytes : fold_bytes;
-    auto kern = wgrad_kernel<CI_T, CO_T, TAPS, RES>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-            return check_launch("hipFuncSetAttribute(wgrad)");
-        attr_done = true;
-    }
     dim3 grid(cdiv(A.src.C, CI) * cdiv(A.Cout, CO), A.npar, A.ksplit);
-    kern<<<grid, NT, smem, st>>>(A);
-    return check_launch("wgrad_kernel");
+    return launch_lds<wgrad_kernel<CI_T, CO_T, TAPS, RES>>(grid, NT, smem, smem, st, "hipFuncSetAttribute(wgrad)", "wgrad_kernel", A);
 }
 
 // the wave-specialised fp32 kernel: 3x3 layers on 64 x 64 channel blocks (ostride 1), tensors below 4 GB (32-bit byte offsets)
@@ -1480,34 +1465,20 @@ int launch_wgrad_ws32(const WgradArgs &A, hipStream_t st) {
         constexpr int XF = decltype(xf_c)::value, QM = decltype(qm_c)::value;
         constexpr int smem = QM == 1 ? 2 * (2 * (8 + 2) * HALO_W * pstride(32) + 2 * 8 * TW * pstride(32))
                                      : 2 * (2 * NPIX_A32 * pstride(64) + 2 * NPIX_G32 * pstride(64));
-        auto kern = wgrad_ws32_kernel<XF, TAPS, QM>;
-        static bool attr_done = false;
-        if (!attr_done) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-                return check_launch("hipFuncSetAttribute(wgrad_ws32)");
-            attr_done = true;
-        }
         dim3 grid(cdiv(A.src.C, 64) * cdiv(A.Cout, 64), A.npar, A.ksplit);
-        kern<<<grid, 512, smem, st>>>(A);
-        return check_launch("wgrad_ws32_kernel");
+        return launch_lds<wgrad_ws32_kernel<XF, TAPS, QM>>(grid, 512, smem, smem, st, "hipFuncSetAttribute(wgrad_ws32)", "wgrad_ws32_kernel", A);
     };
     // quadrants of zero padding are not multiplied (QM): at most 32 channels on the input side, the output side, or both
-    const bool csmall = s.C <= 32 && !(A.debug & 16), gsmall = A.Cout <= 32 && !(A.debug & 16);       // (16: tests / A-B - all four quadrants)
-    auto go = [&](auto xf_c) -> int {
-        if (csmall && gsmall) return go2(xf_c, std::integral_constant<int, 1>{});
-        if (gsmall) return go2(xf_c, std::integral_constant<int, 2>{});
-        if (csmall) return go2(xf_c, std::integral_constant<int, 3>{});
-        return go2(xf_c, std::integral_constant<int, 0>{});
-    };
-    if (plain) return go(std::integral_constant<int, 0>{});
-    if (fast) return go(std::integral_constant<int, 1>{});
-    return go(std::integral_constant<int, 2>{});
+    const bool all_quads = (A.debug & WGRAD_DBG_ALL_QUADS) != 0;       // (tests / A-B)
+    const bool csmall = s.C <= 32 && !all_quads, gsmall = A.Cout <= 32 && !all_quads;
+    const int qm = csmall && gsmall ? 1 : (gsmall ? 2 : (csmall ? 3 : 0));
+    return with_int<0, 1, 2>(plain ? 0 : (fast ? 1 : 2), [&](auto xf_c) { return with_int<1, 2, 3, 0>(qm, [&](auto qm_c) { return go2(xf_c, qm_c); }); });
 }
 
 template <int CI_T, int CO_T, int TAPS>
 int launch_wgrad_f32(const WgradArgs &A, hipStream_t st) {
     static const int use_ws32 = getenv("CDNET_WGRAD_WS32") ? atoi(getenv("CDNET_WGRAD_WS32")) : 1;
-    if (CI_T == 2 && CO_T == 2 && (TAPS == 9 || TAPS == 1) && use_ws32 && !(A.debug & 8) && A.ostride == 1 && A.npar == 1 && !A.src.pool &&
+    if (CI_T == 2 && CO_T == 2 && (TAPS == 9 || TAPS == 1) && use_ws32 && !(A.debug & WGRAD_DBG_NO_WS) && A.ostride == 1 && A.npar == 1 && !A.src.pool &&
         (long long)A.N * A.H * A.W * (A.src.C > A.Cout ? A.src.C : A.Cout) < (1LL << 30) &&
         (long long)A.N * A.src.Hs * (A.src.row_stride ? A.src.row_stride : A.src.Ws * A.src.C) < (1LL << 30))
         return launch_wgrad_ws32<(TAPS == 1 ? 1 : 9)>(A, st);
@@ -1515,20 +1486,12 @@ int launch_wgrad_f32(const WgradArgs &A, hipStream_t st) {
     constexpr int smem = 2 * (NPIX_A * pstride(CI) + NPIX_G * pstride(CO));
     auto go = [&](auto qm_c) -> int {
         constexpr int QM = decltype(qm_c)::value;
-        auto kern = wgrad_f32_kernel<CI_T, CO_T, TAPS, QM>;
-        static bool attr_done = false;
-        if (!attr_done) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-                return check_launch("hipFuncSetAttribute(wgrad_f32)");
-            attr_done = true;
-        }
         dim3 grid(cdiv(A.src.C, CI) * cdiv(A.Cout, CO), A.npar, A.ksplit);
-        kern<<<grid, NT32, smem, st>>>(A);
-        return check_launch("wgrad_f32_kernel");
+        return launch_lds<wgrad_f32_kernel<CI_T, CO_T, TAPS, QM>>(grid, NT32, smem, smem, st, "hipFuncSetAttribute(wgrad_f32)", "wgrad_f32_kernel", A);
     };
     if constexpr (CI_T == 2 && CO_T == 2 && TAPS != 9) {
         // quadrants of zero padding are not multiplied (the transposed convolutions into the decoder's 32- and 16-channel blocks)
-        if (A.Cout <= 32 && !A.src.pool && !(A.debug & 16)) return A.src.C <= 32 ? go(std::integral_constant<int, 1>{}) : go(std::integral_constant<int, 2>{});
+        if (A.Cout <= 32 && !A.src.pool && !(A.debug & WGRAD_DBG_ALL_QUADS)) return A.src.C <= 32 ? go(std::integral_constant<int, 1>{}) : go(std::integral_constant<int, 2>{});
     }
     return go(std::integral_constant<int, 0>{});
 }
@@ -1542,7 +1505,7 @@ int launch_wgrad(const WgradArgs &A, hipStream_t st) {
     const bool res = s.res != nullptr;
     if constexpr (CI_T == 1 && CO_T == 4) {
         // at most 32 output channels: one 32 x 32 block per workgroup, the consumer waves split the tile's rows (wgrad_ws_kernel<1, 1>)
-        if (A.Cout <= 32 && !s.pool && !(A.debug & (8 | 16))) {           // (16: tests - the 32 x 128 form)
+        if (A.Cout <= 32 && !s.pool && !(A.debug & (WGRAD_DBG_NO_WS | WGRAD_DBG_ALL_QUADS))) {           // (ALL_QUADS: tests - the 32 x 128 form)
             const bool plain = !s.scale && !s.relu && !s.f16 && !res;
             const bool fast = s.scale && s.relu && s.f16;
             if (plain) return launch_wgrad_ws<1, 1, TAPS, false, XF_PLAIN>(A, st);
@@ -1550,7 +1513,7 @@ int launch_wgrad(const WgradArgs &A, hipStream_t st) {
             if (!res) return launch_wgrad_ws<1, 1, TAPS, false, XF_GEN>(A, st);
         }
     }
-    if (CI_T != 4 && !s.pool && !(A.debug & 8)) {
+    if (CI_T != 4 && !s.pool && !(A.debug & WGRAD_DBG_NO_WS)) {
         const bool plain = !s.scale && !s.relu && !s.f16 && !res;
         const bool fast = s.scale && s.relu && s.f16;
         if (plain) return launch_wgrad_ws<CI_T, CO_T, TAPS, false, XF_PLAIN>(A, st);

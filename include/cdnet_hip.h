@@ -232,12 +232,15 @@ typedef struct cdnet_conv_args {
                                (bounded buffer descriptors): ask cdnet_conv_ws_eligible == 2 first, any other kernel returns CDNET_E_ARG) */
     int tile, CK, BN;       /* kernel configuration: spatial tile (16 or 8), Cin chunk, Cout tile */
     int out_f16;            /* 1: store the output as fp16 instead of bf16 */
-    int debug;              /* 0 in production.  Kernel-selection switches for the tests: 32 = never take the wave-specialised
-                               persistent kernels (conv_ws_kernel; conv_ws32_kernel of the fp32 path), 64 = take them even for
-                               small launches; bits 8..: at most (debug >> 8) persistent workgroups per output-channel tile (long
-                               runs of tiles on small test shapes; conv_ws32_kernel); 16 (16-bit path): conv_ws16_kernel's quad-request form whatever the
-                               launch's size (production: tensors beyond the Infinity Cache); 256 (fp32 mode, taps = 1): conv_f32_kernel
-                               also where conv1x1_f32_stream_kernel applies; other bits: ablations of tools/bench_conv.py */
+    int debug;              /* 0 in production.  Kernel-selection switches for the tests (named, with the kernels that read them, in
+                               cdnet_amd/csrc/conv_args.h): 32 = never take the wave-specialised persistent kernels (conv_ws16_kernel,
+                               conv_ws_kernel; conv_ws32_kernel of the fp32 path), 64 = take them even for small launches; 128 (16-bit
+                               path): conv_ws_kernel, the older persistent kernel, instead of conv_ws16_kernel; bits 8..: at most
+                               (debug >> 8) persistent workgroups per output-channel tile (long runs of tiles on small test shapes;
+                               conv_ws32_kernel, conv_ws16_kernel - so an odd cap also sets 256, which only a one-tap fp32 launch reads);
+                               16 (16-bit path): conv_ws16_kernel's quad-request form whatever the launch's size (production: tensors
+                               beyond the Infinity Cache); 256 (fp32 mode, taps = 1): conv_f32_kernel also where
+                               conv1x1_f32_stream_kernel applies; other bits: ablations of tools/bench_conv.py */
     int ws;                 /* 0, or 2 (fp32 mode, conv_ws32_kernel only - ask cdnet_conv_ws_eligible): the launch also leaves the first
                                BatchNorm-backward pass of the layer its output feeds; eres / oscale / oshift / eres_scale / eres_shift /
                                stats then carry that layer's raw output, scale, shift, mean, invstd and the partial rows f32
