@@ -90,6 +90,9 @@ SIGNATURES = {
     'cdnet_dam_loss_classes': (_i, [_vp] * 7 + [_i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     'cdnet_variance_loss_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'cdnet_variance_loss': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'cdnet_boundary_loss_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
+    'cdnet_boundary_loss': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp, _vp, _vp, _vp]),
+    'cdnet_boundary_loss_scratch_bytes': (_i, []),
     'cdnet_dam_val_sums_workspace_floats': (_sz, [_i, _i]),
     'cdnet_dam_val_sums': (_i, [_vp] * 8 + [_i, _i, _i, _vp, _sz, _vp, _vp]),
     'cdnet_dam_val_sums_classes_workspace_floats': (_sz, [_i, _i, _i]),

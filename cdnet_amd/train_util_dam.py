@@ -54,6 +54,21 @@ def _check_branches(opt, model):
         assert opt.model['mseloss'] == 1, 'three-output models train with the point branch (mseloss = 1)'
 
 
+def _boundary_value(mask, label, kind):
+    """value of the boundary / focal term `kind` (1 / 2 / 3) of the mask logits [B,3,H,W] against label u8 [B,H,W] (cdnet_boundary_loss, no
+    gradient)"""
+    from . import _lib
+    B, K, H, W = mask.shape
+    need = _lib.load().cdnet_boundary_loss_workspace_bytes(kind, B, K, H, W)
+    if need == 0:
+        raise ValueError('boundary_loss = %r on mask logits of shape %s: kinds 1, 2, 3 of three-class logits are built' % (kind, tuple(mask.shape)))
+    ws = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=mask.device)
+    out = torch.empty((1,), dtype=torch.float32, device=mask.device)
+    _lib.call('cdnet_boundary_loss', _lib.ptr(mask), _lib.ptr(label), kind, B, K, H, W, 1.0, _lib.ptr(ws), ws.numel() * 4, _lib.ptr(out), None,
+              None, _lib.stream_ptr())
+    return float(out.item())
+
+
 def train(train_loader, model, optimizer, criterion, epoch, opt, logger, get_process_worktime=1, get_process_detail=1,
           accuracy_tensor=0):
     trainer = optimizer
@@ -89,7 +104,8 @@ def validate(val_loader, model, criterion, opt, logger, get_process_worktime=1, 
     obj_AJI].  Eval-mode forward of the whole tile (all_img_test == 1) or through `utils.split_forward_dam` with
     opt.train['input_size'] / opt.train['val_overlap'] (:474); validate's OWN loss mix - unweighted mask CE + multi-class dice +
     weighted direction CE + plain dice on the background-gated direction probabilities + MSE against point / 255 - from one pass of
-    `cdnet_dam_val_sums` over the logits, combined here in float64; the pixel metrics of the mask arg-max (:585-590).  With
+    `cdnet_dam_val_sums` over the logits, combined here in float64, + the boundary / focal term of the same logits when
+    opt.model['boundary_loss'] is 1, 2 or 3 (:519-529, cdnet_boundary_loss); the pixel metrics of the mask arg-max (:585-590).  With
     do_object_metric = 0 (the reference's call, train.py:348) the object slots are 0 and obj_iou = pixel_iou (:617-619); with 1 they
     are utils.nuclei_accuracy_object_level of sample 0's post-processed inside class (:588-604)."""
     import ctypes as C
@@ -143,6 +159,9 @@ def validate(val_loader, model, criterion, opt, logger, get_process_worktime=1, 
         dice = sum(1.0 - np.mean(2.0 * (S[:, c] + 1.0) / (S[:, 3 + c] + S[:, 6 + c] + 1.0)) for c in range(3))          # loss.py:135-176
         ddice = sum(1.0 - np.mean(2.0 * (S[:, iq + c] + 1.0) / (S[:, pq + c] + S[:, tq + c] + 1.0)) for c in range(ND))
         loss = ce + dice + dce + ddice + mse
+        kind = int(opt.model.get('boundary_loss', 0))
+        if kind:                                       # :519-529: + beta * the boundary / focal term of the same logits, beta = 1; value only
+            loss += _boundary_value(mask.contiguous(), label, kind)
         tp, fp, fn = S[:, vs + 2], S[:, vs + 3], S[:, vs + 4]
         tn = H * W - tp - fp - fn
         precision, recall = tp / (tp + fp + 1e-10), tp / (tp + fn + 1e-10)

@@ -136,6 +136,8 @@ class Trainer:
         self.losses = torch.zeros((11,), dtype=torch.float32, device=self.dev)     # 6 loss values + 5 pixel metrics
         self.alpha = 0.0                                   # 1: + the instance variance term (train_util_dam.py:174-180), cdnet_variance_loss
         self.loss_var = torch.full((1,), -1.0, dtype=torch.float32, device=self.dev)       # -1 as long as the term is off (:192)
+        self.boundary = 0                                  # 1 / 2 / 3: + BoundaryLoss / FocalLoss2d / RobustFocalLoss2d of the mask logits (:195-205)
+        self.loss_boundary = torch.zeros((1,), dtype=torch.float32, device=self.dev)       # the term's value of the last step (0 while it is off)
         self.tape = []
         self._cat_cache = {}
         self._wstream, self._events = None, {}
@@ -276,6 +278,8 @@ class Trainer:
                   _lib.ptr(dpoint), _lib.ptr(ddir), _lib.stream_ptr())
         if self.alpha:
             self._variance_term(mask, label, dmask)
+        if self.boundary:
+            self._boundary_term(mask, label, dmask)
         return dmask, dpoint, ddir
 
     def _variance_term(self, mask, label, dmask):
@@ -287,6 +291,19 @@ class Trainer:
         ws = self._ws('variance', (need + 3) // 4)
         _lib.call('cdnet_variance_loss', _lib.ptr(mask), _lib.ptr(label.contiguous()), 1, B, K, H, W, float(self.alpha), _lib.ptr(ws),
                   ws.numel() * 4, _lib.ptr(self.loss_var), _lib.ptr(self.losses[0:1]), _lib.ptr(dmask), None, None, _lib.stream_ptr())
+
+    def _boundary_term(self, mask, label, dmask):
+        """boundary_loss = 1 / 2 / 3 (train_util_dam.py:195-205, beta = 1): the term of the mask logits into self.loss_boundary, added to
+        losses[0] and its gradient to dmask (cdnet_boundary_loss)"""
+        if self.boundary not in (1, 2, 3):
+            raise ValueError('boundary = %r: 1 (BoundaryLoss), 2 (FocalLoss2d) or 3 (RobustFocalLoss2d); 0 switches the term off' % (self.boundary,))
+        B, K, H, W = mask.shape
+        need = _lib.load().cdnet_boundary_loss_workspace_bytes(self.boundary, B, K, H, W)
+        if need == 0:
+            raise ValueError('the boundary term serves three-class mask logits, got %s' % (tuple(mask.shape),))
+        ws = self._ws('boundary', (need + 3) // 4)
+        _lib.call('cdnet_boundary_loss', _lib.ptr(mask), _lib.ptr(label.contiguous()), self.boundary, B, K, H, W, 1.0, _lib.ptr(ws),
+                  ws.numel() * 4, _lib.ptr(self.loss_boundary), _lib.ptr(self.losses[0:1]), _lib.ptr(dmask), _lib.stream_ptr())
 
     # ------------------------------------------------------------------------------------------------
     def backward(self, dmask, dpoint, ddir):
@@ -860,7 +877,7 @@ class Trainer:
 
 class UNetTrainer(Trainer):
     """Body of the plain-UNet train iteration (train_util.py:58-200 with the default options: log-softmax + NLL x weight
-    map mean, + MulticlassDiceLoss on the softmax, alpha = 0, no boundary loss) -> backward -> Adam.
+    map mean, + MulticlassDiceLoss on the softmax; `alpha` and `boundary` add their terms as in Trainer) -> backward -> Adam.
     The two loss terms are exactly the mask terms of the DAM loss kernel, which is fed constant point / direction
     branches here; `losses` = [total, CE x weight, dice]."""
 
@@ -881,6 +898,8 @@ class UNetTrainer(Trainer):
         self.unet_losses[0] = self.losses[4] + self.losses[5]
         if self.alpha:
             self.unet_losses[0] += self.loss_var[0]        # train_util.py: loss = loss_CE + alpha * loss_var (+ dice)
+        if self.boundary:
+            self.unet_losses[0] += self.loss_boundary[0]   # train_util.py:170-178: loss = loss + beta * boundary_loss, beta = 1
         return dmask
 
     def backward(self, dlogits):

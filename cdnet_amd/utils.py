@@ -169,12 +169,17 @@ def get_optimizer(args, model, world_size=1):
     `raise '<str>'` is a TypeError by accident).  The scheduler is an optim.LRSchedule for the four torch schedulers of :941-957 and None
     otherwise (the epoch loop then calls adjust_learning_rate, train.py:404-405)."""
     from . import optim
+    boundary = int(getattr(args, 'model', {}).get('boundary_loss', 0))           # (an options object without a model dict: the term is off)
+    if boundary not in (0, 1, 2, 3):
+        # the reference adds nothing for any other value and says nothing (train_util_dam.py:207-208)
+        raise ValueError('boundary_loss = %r: 0 (off), 1 (BoundaryLoss), 2 (FocalLoss2d) or 3 (RobustFocalLoss2d)' % (boundary,))
     name = str(args.train['optimizer']).lower()
     if name not in optim.OPTIMIZERS:
         raise ValueError('Optimizer {} not available'.format(args.train['optimizer']))
     trainer = trainer_class(model)(model, lr=args.train['lr'], weight_decay=args.train['weight_decay'], world_size=world_size,
                                    optimizer=name, momentum=getattr(args, 'momentum', 0.95))
     trainer.alpha = float(args.train.get('alpha', 0.0))           # 1: + the instance variance term (train_util_dam.py:174-180)
+    trainer.boundary = boundary                                   # 1 / 2 / 3: + the boundary / focal term (train_util_dam.py:195-205)
     scheduler = None
     if args.train['scheduler'] in optim.SCHEDULERS:
         scheduler = optim.LRSchedule(args.train['scheduler'], args.train['lr'], step=args.train['step'], lr_decay=args.train['lr_decay'])

@@ -532,6 +532,29 @@ int cdnet_variance_loss(const float *mask_logits, const uint8_t *label, int fg_v
                         void *workspace, size_t workspace_bytes, float *loss_var, float *total, float *dmask, int32_t *root_out,
                         int32_t *counts, void *stream);
 
+/* The boundary / focal term of the training loss (--boundary-loss 1|2|3).  Replaces train_util_dam.py:195-208 and train_util.py:170-178, which
+ * add BoundaryLoss (loss.py:331-393, kind 1), FocalLoss2d (loss.py:37-78, kind 2) or RobustFocalLoss2d (loss.py:81-127, kind 3) of the mask
+ * logits and the one-hot target to the loss, with the gradient autograd takes.
+ *   kind 1: p = softmax(z), t = [label == c], every pooling window clipped to the image (F.max_pool2d pads with -inf):
+ *     gt_b = t - min3x3(t), gt_ext = max5x5(gt_b), pr_b = p - min3x3(p) (the reference's maxpool(1 - p) - (1 - p)), pr_ext = max5x5(pr_b);
+ *     per (sample, class)  P = sum(pr_b gt_ext) / (sum(pr_b) + 1e-7),  R = sum(pr_ext gt_b) / (sum(gt_b) + 1e-7),  BF1 = 2PR / (P + R + 1e-7);
+ *     loss = mean over (sample, class) of 1 - BF1.  A pool's gradient goes to the window's FIRST maximum in raster order (ATen's rule).
+ *   kind 2: every logit element is one binary example: pt = t ? sigmoid(z) : 1 - sigmoid(z) clamped to [1e-8, 1 - 1e-8] (1 in fp32; gradient 0
+ *     outside), loss = mean of -(1 - pt)^2 log(pt) over the B K H W elements.  pt is formed in fp32 as the reference forms it.
+ *   kind 3: the robust form clamps (1 - pt)^2 to [0, 2], which never binds for a probability: the same kernel as kind 2, bitwise equal results.
+ * The one-hot target is [label == c] for the classes 0, 1, 2.  The reference builds it from np.unique over the batch (train_util_dam.py:85-100),
+ * which shifts the channels when a batch lacks a class; that accident is NOT reproduced.
+ * mask_logits f32 [B][3][H][W] (K != 3: CDNET_E_ARG), any H, W >= 1; label u8 [B][H][W] in {0,1,2} - a larger value makes loss_out NaN (as
+ * cdnet_dam_loss) and nothing is read or written out of bounds.  loss_out f32 [1] is always written; total (NULL or f32 [1]): *total += beta *
+ * loss; dmask (NULL or f32 [B][3][H][W]): += beta * d loss / d logits.  No host synchronisation, no atomics: per-workgroup partials summed in
+ * a fixed order, bit-identical from call to call, graph-capturable.  Two launches.
+ * workspace: cdnet_boundary_loss_workspace_bytes(kind, B, K, H, W) bytes, 8-byte aligned (0 for what the entry does not serve); a NULL or short
+ * workspace is an argument error (CDNET_E_ARG), found like the other argument errors before any HIP call. */
+size_t cdnet_boundary_loss_workspace_bytes(int kind, int B, int K, int H, int W);
+int cdnet_boundary_loss(const float *mask_logits, const uint8_t *label, int kind, int B, int K, int H, int W, float beta,
+                        void *workspace, size_t workspace_bytes, float *loss_out, float *total, float *dmask, void *stream);
+int cdnet_boundary_loss_scratch_bytes(void);   /* scratch bytes per lane of kind 1's gradient kernel as built (-1: query failed); expected 0 */
+
 /* validate() loss mix of train_util_dam.py:367-636 (default options): per-sample sums of ONE pass over the logits, combined on the
  * host by cdnet_amd.train_util_dam.validate.  sums f32 [B][CDNET_VAL_SUMS]:
  *   0..2 sum p_c [label==c], 3..5 sum p_c, 6..8 sum [label==c], 9 sum -log p_label (unweighted mask CE, :499-505);
