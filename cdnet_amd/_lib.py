@@ -108,6 +108,8 @@ SIGNATURES = {
     'cdnet_label_encoding_instances': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     'cdnet_augment_workspace_bytes': (_sz, [_i, _i, _i]),
     'cdnet_augment_batch': (_i, [_vp, _vp, _i, _i, _vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    'cdnet_augment_geo_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'cdnet_augment_batch_geo': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     'cdnet_label_encoding': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 

@@ -1,4 +1,4 @@
-"""Training augmentation of the reference's default recipe (my_transforms_direction.py:155-540), on the device.
+"""Training augmentation of the reference's recipe (my_transforms_direction.py:69-540), on the device.
 
   draw_params(rs, H, W, recipe)       one sample's parameters, drawn from the loader's RandomState in the reference's order
   augment_batch(sources, params, ...) one batch on the device: cdnet_augment_batch (csrc/augment.hip)
@@ -7,11 +7,12 @@
                                       restated OpenCV geometry; it serves TileBatches(device='cpu') and checks the device path
   Recipe                              which steps run, the elastic parameters (alpha, sigma, alpha_affine) and the crop size
 
-Per sample, on the whole source image: random_color -> horizontal / vertical flip -> random_elastic (random affine, then a
-Gaussian-smoothed displacement field) -> random_chooseAug -> random_crop.  The contract is the same distributions and the same operation
+Per sample, on the whole source image, in the order options.py:331-347 fixes: [random_resize] -> random_color -> [random_affine] ->
+horizontal / vertical flip -> random_elastic (random affine, then a Gaussian-smoothed displacement field) -> [random_rotation] ->
+random_chooseAug -> random_crop; the bracketed steps are off in the default recipe and go through cdnet_augment_batch_geo.  The contract is the same distributions and the same operation
 for given parameters, not the reference's random streams (Python `random`, np.random and albumentations' RandomState spread over
-DataLoader workers).  The colour chain and the filters equal Pillow's bit for bit; the geometry restates OpenCV 4's nearest rules (cv2
-parity unpinned); the field noise is a counter-based hash of (seed, plane, y, x), not numpy's MT19937.
+DataLoader workers).  The colour chain, the filters and random_affine equal Pillow's bit for bit; the other geometry (elastic, resize,
+rotation) restates OpenCV 4's nearest rules (cv2 / albumentations parity unpinned); the field noise is a counter-based hash of (seed, plane, y, x), not numpy's MT19937.
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -31,6 +32,14 @@ class AugSample(C.Structure):              # cdnet_aug_sample (include/cdnet_hip
         [('alpha', C.c_float), ('sigma', C.c_float), ('seed', C.c_uint32)]
 
 
+class AugGeo(C.Structure):                 # cdnet_aug_geo (include/cdnet_hip.h)
+    _fields_ = [('paff', C.c_double * 6), ('rinv', C.c_double * 6)] + [(n, C.c_int32) for n in ('Hr', 'Wr', 'fy0', 'fx0')] + \
+        [('flags', C.c_uint32), ('reserved', C.c_int32)]
+
+
+GEO_RESIZE, GEO_AFFINE, GEO_ROTATION = 1, 2, 4
+
+
 @dataclass
 class Recipe:
     """the steps of a transform dict (options.py:327-351) and the elastic parameters; the reference ignores random_elastic's [6, 15]
@@ -44,12 +53,27 @@ class Recipe:
     elastic_alpha: float = 1.0
     elastic_sigma: float = 50.0
     elastic_alpha_affine: float = 50.0
+    resize: tuple = None            # random_resize: None or (lb, ub), the scale's range (my_transforms_direction.py:95)
+    affine: float = None            # random_affine: None or the bound of the four coefficients' deviations (:195-199: inside [0, 0.5])
+    rotation: bool = False          # random_rotation: the reference ignores its `degrees` and always runs albu.Rotate(limit=(-90, 90)) (:417)
+    rotation_limit: float = 90.0
+
+    def __post_init__(self):
+        if self.affine is not None and not 0 <= self.affine <= 0.5:
+            raise ValueError('Bound is invalid, should be in range [0, 0.5)')
+        if self.resize is not None:
+            self.resize = (float(self.resize[0]), float(self.resize[1]))
+            if not 0 < self.resize[0] <= self.resize[1]:
+                raise ValueError('random_resize needs 0 < lb <= ub')
 
     @classmethod
     def from_transform(cls, transform, **elastic):
+        rr, ra = transform.get('random_resize'), transform.get('random_affine')
         return cls(size=int(transform['random_crop']), color=bool(transform.get('random_color')),
                    hflip=bool(transform.get('horizontal_flip')), vflip=bool(transform.get('vertical_flip')),
-                   elastic=bool(transform.get('random_elastic')), choose_aug=bool(transform.get('random_chooseAug')), **elastic)
+                   elastic=bool(transform.get('random_elastic')), choose_aug=bool(transform.get('random_chooseAug')),
+                   resize=tuple(rr) if rr else None, affine=float(ra) if ra is not None and ra is not False else None,
+                   rotation=bool(transform.get('random_rotation')), **elastic)
 
 
 @dataclass
@@ -65,6 +89,20 @@ class Params:
     filter: int                 # 0 none, 1 BLUR, 2 GaussianBlur, 3 MedianFilter
     y0: int
     x0: int
+    # the optional steps; the defaults mean "off"
+    scale: float = 1.0          # random_resize's scale
+    Hr: int = 0                 # the resized size (0: the source's)
+    Wr: int = 0
+    paff: tuple = None          # random_affine: Pillow's (a, b, c, d, e, f), output -> input pixel
+    angle: float = 0.0          # random_rotation's angle in degrees (counter-clockwise)
+    rinv: tuple = None          # its inverse matrix (2 x 3 row-major, float64): destination -> source pixel
+    fy0: int = None             # the displacement-field window's origin and edge (None: crop + 6 px at (y0 - 6, x0 - 6))
+    fx0: int = None
+    fedge: int = None
+
+    def dims(self, H, W):
+        """the size every step after random_resize works in"""
+        return (self.Hr or H, self.Wr or W)
 
 
 def affine_points(H, W):
@@ -83,7 +121,11 @@ def affine_inverse(pts1, pts2):
         A[2 * i, :3] = (x, y, 1.0)
         A[2 * i + 1, 3:] = (x, y, 1.0)
         rhs[2 * i], rhs[2 * i + 1] = float(pts2[i, 0]), float(pts2[i, 1])
-    M = np.linalg.solve(A, rhs)
+    return invert_affine(np.linalg.solve(A, rhs))
+
+
+def invert_affine(M):
+    """OpenCV's invertAffineTransform formula on M (6 doubles, row-major 2 x 3)"""
     D = M[0] * M[4] - M[1] * M[3]
     D = 1.0 / D if D != 0 else 0.0
     A11, A22, A12, A21 = M[4] * D, M[0] * D, -M[1] * D, -M[3] * D
@@ -95,10 +137,75 @@ def affine_inverse(pts1, pts2):
 IDENTITY = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0)
 
 
+def rotation_inverse(angle, H, W):
+    """the inverse of OpenCV's getRotationMatrix2D((W / 2, H / 2), angle, 1) - the centre albumentations' Rotate passed in the
+    reference's era (later versions use W / 2 - 0.5; parity unpinned)"""
+    t = angle * np.pi / 180.0
+    al, be = float(np.cos(t)), float(np.sin(t))
+    cx, cy = W / 2.0, H / 2.0
+    return invert_affine((al, be, (1 - al) * cx - be * cy, -be, al, be * cx + (1 - al) * cy))
+
+
+def resize_dims(H, W, scale):
+    """RandomResize's output size (my_transforms_direction.py:99-100)"""
+    return int(H * scale), int(W * scale)
+
+
+def resize_index(n_out, n_in):
+    """OpenCV INTER_NEAREST: the source index behind each of n_out output rows / columns"""
+    return np.minimum(np.floor(np.arange(n_out) * (1.0 / (n_out / n_in))).astype(np.int64), n_in - 1)
+
+
+def pil_affine_source(paff, H, W, y, x):
+    """Pillow's Image.transform(AFFINE, NEAREST) in its 16.16 fixed point (Geometry.c affine_fixed), restated: -> (yin, xin, inside)
+    of output pixels (y, x) of an H x W image"""
+    a = [float(v) for v in paff]
+    fix = lambda v: int(np.floor(v * 65536.0 + 0.5))
+    a0, a1, a3, a4 = fix(a[0]), fix(a[1]), fix(a[3]), fix(a[4])
+    a2, a5 = fix(a[2] + (a[0] * 0.5 + a[1] * 0.5)), fix(a[5] + (a[3] * 0.5 + a[4] * 0.5))
+    y, x = np.asarray(y, np.int64), np.asarray(x, np.int64)
+    xin = (a2 + a1 * y + a0 * x) >> 16
+    yin = (a5 + a4 * y + a3 * x) >> 16
+    return yin, xin, (xin >= 0) & (xin < W) & (yin >= 0) & (yin < H)
+
+
+def field_box(p, H, W, size):
+    """the displacement-field window a sample needs in a batch that holds a rotation: the bounding box of the four corners of the crop +
+    6 px, mapped through the rotation's inverse by the kernel's fixed-point rule (monotone in each coordinate, so the corners bound
+    every pixel), + 2 px, clipped to the H x W image -> (fy0, fx0, edge)"""
+    ys = np.array([p.y0 - HALO, p.y0 - HALO, p.y0 + size + HALO - 1, p.y0 + size + HALO - 1])
+    xs = np.array([p.x0 - HALO, p.x0 + size + HALO - 1, p.x0 - HALO, p.x0 + size + HALO - 1])
+    if p.rinv is not None:
+        ys, xs, _ = warp_source(p.rinv, H, W, ys, xs)
+    ylo, yhi = max(int(ys.min()) - 2, 0), min(int(ys.max()) + 2, H - 1)
+    xlo, xhi = max(int(xs.min()) - 2, 0), min(int(xs.max()) + 2, W - 1)
+    if yhi < ylo or xhi < xlo:                   # wholly outside the image: nothing is read
+        return 0, 0, 1
+    return ylo, xlo, max(yhi - ylo, xhi - xlo) + 1
+
+
 def draw_params(rs, H, W, recipe):
-    """the reference's draws in its order (RandomColor :162-172, flips :233 / :251, ElasticTransform's affine offsets and field,
-    RandomChooseAug :451, RandomCrop): `rs` is the loader's numpy RandomState"""
+    """the reference's draws in its order (RandomResize :95, RandomColor :162-172, RandomAffine :205-208, flips :233 / :251,
+    ElasticTransform's affine offsets and field, RandomRotation / albu.Rotate's angle, RandomChooseAug :451, RandomCrop): `rs` is the
+    loader's numpy RandomState.  With random_resize every later step is drawn for the resized size."""
+    geo = {}
+    if recipe.resize is not None:
+        scale = float(rs.uniform(*recipe.resize))
+        H, W = resize_dims(H, W, scale)
+        if H < 1 or W < 1:
+            raise ValueError('random_resize: the scale {} leaves no pixel'.format(scale))
+        geo.update(scale=scale, Hr=H, Wr=W)
     color = tuple(1 + (rs.rand() - 0.5) for _ in range(4)) if recipe.color else (1.0, 1.0, 1.0, 1.0)
+    if recipe.affine is not None:
+        v = recipe.affine
+        a = 1 + 2 * v * (rs.rand() - 0.5)
+        b = 2 * v * (rs.rand() - 0.5)
+        d = 2 * v * (rs.rand() - 0.5)
+        e = 1 + 2 * v * (rs.rand() - 0.5)
+        # :211-212: the transformation centre is the image centre (x = width, y = height)
+        c = -a * W / 2 - b * H / 2 + W / 2
+        f = -d * W / 2 - e * H / 2 + H / 2
+        geo['paff'] = tuple(float(t) for t in (a, b, c, d, e, f))
     hflip = int(rs.rand() < 0.5) if recipe.hflip else 0
     vflip = int(rs.rand() < 0.5) if recipe.vflip else 0
     minv, alpha, seed = IDENTITY, 0.0, 0
@@ -110,6 +217,9 @@ def draw_params(rs, H, W, recipe):
             minv = affine_inverse(pts1, pts2)
         alpha = float(recipe.elastic_alpha)
         seed = int(rs.randint(0, 2 ** 31))
+    if recipe.rotation:
+        angle = float(rs.uniform(-recipe.rotation_limit, recipe.rotation_limit))
+        geo.update(angle=angle, rinv=tuple(float(t) for t in rotation_inverse(angle, H, W)))
     filt = 0
     if recipe.choose_aug:
         r = rs.rand()
@@ -117,7 +227,10 @@ def draw_params(rs, H, W, recipe):
     s = recipe.size
     y0 = int(rs.randint(0, max(H - s, 0) + 1))
     x0 = int(rs.randint(0, max(W - s, 0) + 1))
-    return Params(color, hflip, vflip, tuple(float(v) for v in minv), alpha, float(recipe.elastic_sigma), seed, filt, y0, x0)
+    p = Params(color, hflip, vflip, tuple(float(v) for v in minv), alpha, float(recipe.elastic_sigma), seed, filt, y0, x0, **geo)
+    if p.rinv is not None:
+        p.fy0, p.fx0, p.fedge = field_box(p, H, W, s)
+    return p
 
 
 def gauss_radius(sigma):
@@ -186,13 +299,37 @@ def warp_source(minv, H, W, ry, rx):
     return Y, X, (X >= 0) & (X < W) & (Y >= 0) & (Y < H)
 
 
-def augment_host(img, weight, label, p, size, field=None):
-    """one sample through the whole chain on the host.  img u8 [H, W, 3], weight u8 [H, W], label u8 / i32 [H, W]; `field` (f32 [2,
-    size + 12, size + 12], as augment_batch returns it) replaces the host's own dx, dy when given.  Returns the crop (img u8 [s, s, 3],
-    weight u8 [s, s], label [s, s]) before the division by 255."""
-    H, W = weight.shape
-    im = colour_chain(img, p.color)
-    planes = [im[..., c] for c in range(3)] + [weight, label]
+def field_full(p, H, W):
+    """dx, dy (f32 [2, H, W]) over the whole image as the host computes them (field_window's rule)"""
+    from scipy.ndimage import gaussian_filter
+    return np.stack([gaussian_filter(field_noise(p.seed, k, H, W), p.sigma, mode='reflect', truncate=4.0) * np.float32(p.alpha)
+                     for k in range(2)])
+
+
+def _gather(planes, Y, X, ok):
+    Yc, Xc = np.where(ok, Y, 0), np.where(ok, X, 0)
+    return [np.where(ok if a.ndim == 2 else ok[..., None], a[Yc, Xc], 0).astype(a.dtype) for a in planes]
+
+
+def augment_host(img, weight, label, p, size, field=None, origin=None):
+    """one sample through the whole chain on the host.  img u8 [H, W, 3], weight u8 [H, W], label u8 / i32 [H, W]; `field` (f32 [2, E, E],
+    as augment_batch returns it) replaces the host's own dx, dy when given, `origin` = the (row, column) of its first element in the
+    (resized) image (default: the crop origin - 6, the window without a rotation).  Returns the crop (img u8 [s, s, 3], weight u8 [s, s],
+    label [s, s]) before the division by 255."""
+    planes = [img, weight, label]
+    if p.Hr:                                     # random_resize: OpenCV's nearest index rule
+        iy, ix = resize_index(p.Hr, weight.shape[0]), resize_index(p.Wr, weight.shape[1])
+        planes = [a[iy][:, ix] for a in planes]
+    H, W = planes[1].shape
+    im = colour_chain(planes[0], p.color)
+    planes = [im[..., c] for c in range(3)] + planes[1:]
+    if p.paff is not None:                       # random_affine: through PIL itself, per plane (my_transforms_direction.py:216-218)
+        from PIL import Image
+        rgb = Image.fromarray(np.ascontiguousarray(im)).transform((W, H), Image.AFFINE, p.paff)
+        rest = [np.asarray(Image.fromarray(np.ascontiguousarray(a)).transform((W, H), Image.AFFINE, p.paff)).astype(a.dtype)
+                for a in planes[3:]]
+        rgb = np.asarray(rgb)
+        planes = [rgb[..., c] for c in range(3)] + rest
     if p.hflip:
         planes = [a[:, ::-1] for a in planes]
     if p.vflip:
@@ -202,20 +339,22 @@ def augment_host(img, weight, label, p, size, field=None):
     ry, rx, inside = qy, qx, np.ones((H, W), bool)
     if p.alpha != 0.0:
         if field is None:
-            field = field_window(p, H, W, size)
-        d = np.zeros((2, H, W), np.float32)
-        FS = size + 2 * HALO
-        ys, xs = np.arange(p.y0 - HALO, p.y0 - HALO + FS), np.arange(p.x0 - HALO, p.x0 - HALO + FS)
-        iy, ix = (ys >= 0) & (ys < H), (xs >= 0) & (xs < W)
-        for k in range(2):
-            d[k][np.ix_(ys[iy], xs[ix])] = np.asarray(field[k], np.float32)[np.ix_(iy, ix)]
+            d = field_full(p, H, W)
+        else:
+            d = np.zeros((2, H, W), np.float32)
+            fy0, fx0 = origin if origin is not None else (p.y0 - HALO, p.x0 - HALO)
+            FS = np.asarray(field[0]).shape[0]
+            ys, xs = np.arange(fy0, fy0 + FS), np.arange(fx0, fx0 + FS)
+            iy, ix = (ys >= 0) & (ys < H), (xs >= 0) & (xs < W)
+            for k in range(2):
+                d[k][np.ix_(ys[iy], xs[ix])] = np.asarray(field[k], np.float32)[np.ix_(iy, ix)]
         rx = np.rint(qx.astype(np.float32) + d[0]).astype(np.int64)
         ry = np.rint(qy.astype(np.float32) + d[1]).astype(np.int64)
         inside = (rx >= 0) & (rx < W) & (ry >= 0) & (ry < H)
     Y, X, ok = warp_source(p.minv, H, W, ry, rx)
-    ok &= inside
-    Yc, Xc = np.where(ok, Y, 0), np.where(ok, X, 0)
-    warped = [np.where(ok, a[Yc, Xc], 0).astype(a.dtype) for a in planes]
+    warped = _gather(planes, Y, X, ok & inside)
+    if p.rinv is not None:                       # random_rotation: warpAffine nearest, zero border
+        warped = _gather(warped, *warp_source(p.rinv, H, W, qy, qx))
     im = apply_filter(np.stack(warped[:3], -1), p.filter)
     s = size
     out = [im, warped[3], warped[4]]
@@ -242,10 +381,34 @@ class Source:
 _WS = {}
 
 
-def augment_batch(sources, params, size, normalize=None, want_field=False):
-    """the batch on the device (one call of cdnet_augment_batch, csrc/augment.hip).  sources: [Source], params: [Params].
-    Returns (image f32 [B, 3, s, s], weight u8 [B, s, s], label u8 / i32 [B, s, s], varied i32 [B][, field f32 [B, 2, s + 12, s + 12]]);
-    varied[b] == 0: the label crop holds one value (re-draw)."""
+def _geo_table(sources, params, size):
+    """(AugGeo table, field edge) of a batch that needs cdnet_augment_batch_geo, else (None, size + 12).  With a rotation in the batch
+    every sample's field window is its field_box and the edge is the largest; else the windows are the crop + 6 px."""
+    if not any(p.Hr or p.paff is not None or p.rinv is not None for p in params):
+        return None, size + 2 * HALO
+    rot = any(p.rinv is not None for p in params)
+    geo = (AugGeo * len(params))()
+    edge = 1 if rot else size + 2 * HALO
+    for g, src, p in zip(geo, sources, params):
+        g.Hr, g.Wr = p.dims(src.H, src.W)
+        g.flags = (GEO_RESIZE if p.Hr else 0) | (GEO_AFFINE if p.paff is not None else 0) | (GEO_ROTATION if p.rinv is not None else 0)
+        g.paff[:] = p.paff if p.paff is not None else IDENTITY
+        g.rinv[:] = p.rinv if p.rinv is not None else IDENTITY
+        g.fy0, g.fx0 = p.y0 - HALO, p.x0 - HALO
+        if rot:
+            box = (p.fy0, p.fx0, p.fedge) if p.fedge is not None else field_box(p, g.Hr, g.Wr, size)
+            g.fy0, g.fx0 = box[0], box[1]
+            edge = max(edge, box[2])
+    return geo, edge
+
+
+def augment_batch(sources, params, size, normalize=None, want_field=False, want_origin=False):
+    """the batch on the device (one call of cdnet_augment_batch, or of cdnet_augment_batch_geo when a sample has one of the optional
+    steps; csrc/augment.hip).  sources: [Source], params: [Params].
+    Returns (image f32 [B, 3, s, s], weight u8 [B, s, s], label u8 / i32 [B, s, s], varied i32 [B][, field f32 [B, 2, E, E]][, origin
+    i64 [B, 2]]); varied[b] == 0: the label crop holds one value (re-draw).  The field window's edge E is s + 12 and its origin (y0 - 6,
+    x0 - 6) unless the batch holds a rotation.  want_field keeps its five values; the origins, each sample's (row, column), are a
+    separate request (want_origin) so that earlier callers of want_field stay as they are."""
     B = len(sources)
     assert B == len(params) and B > 0
     dev = sources[0].img.device
@@ -261,8 +424,9 @@ def augment_batch(sources, params, size, normalize=None, want_field=False):
         t.alpha, t.sigma, t.seed = p.alpha, p.sigma, p.seed
         if p.alpha != 0.0:
             rmax = max(rmax, gauss_radius(p.sigma))
+    geo, FS = _geo_table(sources, params, size)
     lib = _lib.load()
-    nbytes = lib.cdnet_augment_workspace_bytes(B, size, rmax)
+    nbytes = lib.cdnet_augment_geo_workspace_bytes(B, size, rmax, FS)
     key = (dev.index, torch.cuda.current_stream().cuda_stream)
     ws = _WS.get(key)
     if ws is None or ws.numel() < nbytes:
@@ -273,11 +437,16 @@ def augment_batch(sources, params, size, normalize=None, want_field=False):
     weight = torch.empty((B, size, size), dtype=torch.uint8, device=dev)
     label = torch.empty((B, size, size), dtype=torch.int32 if label_i32 else torch.uint8, device=dev)
     varied = torch.empty((B,), dtype=torch.int32, device=dev)
-    FS = size + 2 * HALO
     field = torch.zeros((B, 2, FS, FS), dtype=torch.float32, device=dev) if want_field else None
     norm = (C.c_float * 6)(*(list(normalize[0]) + list(normalize[1]))) if normalize else None
-    _lib.call('cdnet_augment_batch', _lib.ptr(table_dev), table, B, size, norm, _lib.ptr(ws), ws.numel(), _lib.ptr(image),
-              _lib.ptr(weight), _lib.ptr(label), label_i32, _lib.ptr(varied), _lib.ptr(field), _lib.stream_ptr())
-    if want_field:
-        return image, weight, label, varied, field
-    return image, weight, label, varied
+    if geo is None:
+        _lib.call('cdnet_augment_batch', _lib.ptr(table_dev), table, B, size, norm, _lib.ptr(ws), ws.numel(), _lib.ptr(image),
+                  _lib.ptr(weight), _lib.ptr(label), label_i32, _lib.ptr(varied), _lib.ptr(field), _lib.stream_ptr())
+        origin = np.array([(p.y0 - HALO, p.x0 - HALO) for p in params], np.int64)
+    else:
+        geo_dev = torch.frombuffer(bytearray(bytes(geo)), dtype=torch.uint8).to(dev)
+        _lib.call('cdnet_augment_batch_geo', _lib.ptr(table_dev), table, _lib.ptr(geo_dev), geo, FS, B, size, norm, _lib.ptr(ws), ws.numel(),
+                  _lib.ptr(image), _lib.ptr(weight), _lib.ptr(label), label_i32, _lib.ptr(varied), _lib.ptr(field), _lib.stream_ptr())
+        origin = np.array([(g.fy0, g.fx0) for g in geo], np.int64)
+    out = (image, weight, label, varied) + ((field,) if want_field else ()) + ((origin,) if want_origin else ())
+    return out

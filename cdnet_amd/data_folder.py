@@ -7,9 +7,10 @@
                                       cdnet_label_encoding launch per batch makes the 3-class label, the centre-point map and
                                       the centripetal direction classes (the reference does this per sample in DataLoader
                                       workers, seconds per sample: SURVEY 8f.1).  With augment=True the reference's whole
-                                      default recipe runs on the device (cdnet_amd/augment.py: random_color, flips,
-                                      random_elastic, random_chooseAug and random_crop in one cdnet_augment_batch call per
-                                      batch, the sources resident there)
+                                      recipe runs on the device (cdnet_amd/augment.py: random_color, flips, random_elastic,
+                                      random_chooseAug and random_crop, and random_resize / random_affine / random_rotation
+                                      when the transform dict holds them, in one cdnet_augment_batch[_geo] call per batch,
+                                      the sources resident there)
 
 Samples leave TileBatches in the layout train_util_dam.train expects: (input f32 [B,3,H,W], weight u8 [B,1,H,W],
 label i64 [B,1,H,W] in {0,127,255}, point f16 [B,H,W], direction u8 [B,H,W]).  Without `augment` the photometric / elastic
@@ -103,7 +104,8 @@ class TileBatches:
     unless the images share one size)."""
 
     SKIPPED = ('random_color', 'random_elastic', 'random_chooseAug', 'random_resize', 'random_affine', 'random_rotation')
-    AUGMENTED = ('random_color', 'random_elastic', 'random_chooseAug')          # what augment=True adds (cdnet_amd/augment.py)
+    AUGMENTED = ('random_color', 'random_elastic', 'random_chooseAug', 'random_resize', 'random_affine',
+                 'random_rotation')                                             # what augment=True adds (cdnet_amd/augment.py)
 
     def __init__(self, dataset, transform, batch_size, device, seed=0, shuffle=True, drop_last=False, logger=None, augment=False,
                  elastic=None):

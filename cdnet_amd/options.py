@@ -19,6 +19,24 @@ def get_transformString(names):
     return '_' + ''.join(tags.get(n, n[:2]) for n in names)
 
 
+# the training transform chain in the reference's fixed order with its arguments (options.py:331-357); vertical_flip, label_encoding and
+# to_tensor are always present there
+TRANS_TRAIN_ORDER = ('random_resize', 'random_color', 'random_affine', 'horizontal_flip', 'vertical_flip', 'random_elastic',
+                     'random_rotation', 'random_chooseAug', 'random_crop', 'label_encoding', 'to_tensor')
+
+
+def build_train_transform(names, input_size, label_encoding):
+    """transform['train'] from a list of step names"""
+    unknown = [n for n in names if n not in TRANS_TRAIN_ORDER]
+    if unknown:
+        raise ValueError('unknown training transforms {} (known: {})'.format(unknown, ', '.join(TRANS_TRAIN_ORDER)))
+    args = {'random_resize': [1, 2], 'random_color': 1, 'random_affine': 0.3, 'horizontal_flip': True, 'vertical_flip': True,
+            'random_elastic': [6, 15], 'random_rotation': 90, 'random_chooseAug': 1, 'random_crop': input_size,
+            'label_encoding': label_encoding, 'to_tensor': 1}
+    always = ('vertical_flip', 'label_encoding', 'to_tensor')
+    return {k: args[k] for k in TRANS_TRAIN_ORDER if k in names or k in always}
+
+
 class Options:
 
     def __init__(self, isTrain):
@@ -99,6 +117,8 @@ class Options:
             p.add_argument('--save-dir', type=str, default=self.train['save_dir'])
             p.add_argument('--checkpoint-path', type=str, default=self.train['checkpoint'])
             p.add_argument('--transform-train', type=str, default=self.transform_str)
+            p.add_argument('--trans-train', type=str, default=','.join(self.train['trans_train']),
+                           help='comma-separated training transforms, applied in the fixed order ' + ' -> '.join(TRANS_TRAIN_ORDER))
             p.add_argument('--exp-filename', type=str, default=self.model['exp_filename'])
             p.add_argument('--validation', type=int, default=self.train['validation'])
         else:
@@ -132,10 +152,9 @@ class Options:
             self._derive()
             if a.save_dir != p.get_default('save_dir'):
                 t['save_dir'] = a.save_dir
-            # default training transform chain as the reference builds it
-            self.transform['train'] = {'random_color': 1, 'horizontal_flip': True, 'vertical_flip': True, 'random_elastic': [6, 15],
-                                       'random_chooseAug': 1, 'random_crop': t['input_size'],
-                                       'label_encoding': [m['out_c'], 2, m['direction']], 'to_tensor': 1}
+            # the training transform chain as the reference builds it from the list (options.py:331-357)
+            t['trans_train'] = [n.strip() for n in a.trans_train.split(',') if n.strip()]
+            self.transform['train'] = build_train_transform(t['trans_train'], t['input_size'], [m['out_c'], 2, m['direction']])
             self.transform['val'] = {'to_tensor': 1}
         else:
             te = self.test

@@ -8,7 +8,10 @@ followed by the scheduler step -> checkpoint.
 The reference's augmentation pipeline (albumentations / PIL RNG streams) and its CSV / tensorboard logging are outside
 the accelerated path: with a real dataset the loader below applies random 256x256 crops and flips,
 `LabelEncoding` (on the GPU) and `ToTensor` - with --device-augment the reference's whole default recipe (colour, flips, elastic,
-filter, crop) on the GPU; `nn.DataParallel` (train.py:185) is replaced by one process per GPU."""
+filter, crop) on the GPU, and with `--trans-train name,name,...` (options.py:331-347: random_resize, random_color, random_affine,
+horizontal_flip, random_elastic, random_rotation, random_chooseAug, random_crop; vertical_flip always) the steps of that list, in the
+reference's fixed order, random_resize / random_affine / random_rotation included; `nn.DataParallel` (train.py:185) is replaced by
+one process per GPU."""
 import argparse
 import logging
 import os

@@ -659,6 +659,40 @@ int cdnet_augment_batch(const cdnet_aug_sample *samples, const cdnet_aug_sample 
                         void *workspace, size_t workspace_bytes, float *image, uint8_t *weight, void *label, int label_i32, int32_t *varied,
                         float *field, void *stream);
 
+/* The three optional steps of the reference's chain (options.py:331-347 fixes the order random_resize -> random_color -> random_affine ->
+ * flips -> random_elastic -> random_rotation -> random_chooseAug -> random_crop), all nearest-neighbour geometry on image, weight and label
+ * together, traced back per output pixel like the rest:
+ *   random_resize (my_transforms_direction.py:69-151, albu.Resize nearest): the source is seen as a virtual Hr x Wr image, row y reading
+ *     stored row min(floor(y * (1 / (Hr / H))), H - 1) (OpenCV's INTER_NEAREST rule, cv2 parity unpinned); every later step - the Contrast
+ *     mean, Sharpness's neighbours, the elastic affine, the field, the crop origin - works in Hr x Wr.  Nothing is materialised.
+ *   random_affine (:185-220, PIL Image.transform(AFFINE), NEAREST): paff = Pillow's a b c d e f (output -> input pixel), applied in Pillow's
+ *     16.16 fixed point, bit for bit; outside reads 0.  (For b = d = 0 Pillow itself takes a scaling path that accumulates in double;
+ *     the two agree for the identity, which is all random_affine can draw with b = d = 0, and are not pinned for other pure scales.)
+ *   random_rotation (:354-440, albu.Rotate nearest, zero border): rinv = the inverse (invertAffineTransform's formula) of
+ *     getRotationMatrix2D((Wr / 2, Hr / 2), angle, 1), applied in OpenCV's fixed point like minv (cv2 / albumentations parity unpinned).
+ *   cdnet_aug_geo: one row per sample beside cdnet_aug_sample: flags = 1 resize | 2 affine | 4 rotation (a step whose bit is clear is
+ *     skipped; without bit 1, Hr x Wr must equal H x W); (fy0, fx0) = the origin of the sample's displacement-field window.
+ *   field_edge: the window's edge, one per batch.  The field is needed where the rotation's pre-image of the crop + 6 px falls: with no
+ *     rotation that is size + 12 at (y0 - 6, x0 - 6) - then the call computes what cdnet_augment_batch does; else the caller takes the
+ *     bounding box of the four corner pre-images (+ 2 px, clipped to the image).  The fixed-point map is monotone in each coordinate,
+ *     so that box holds every pixel's pre-image: the entry checks before any launch that, for a sample with alpha != 0, the part of
+ *     the box inside the image lies in the window (every field lookup then does), and that 1 <= Hr, Wr <= 32767, the matrices are
+ *     finite, the affine stays in Pillow's 16.16 range and the crop origin lies inside Hr x Wr (CDNET_E_ARG otherwise).
+ *   field (optional output): f32 [B][2][field_edge][field_edge], origin (fy0, fx0) per sample, 0 outside the image.
+ * cdnet_augment_geo_workspace_bytes: as cdnet_augment_workspace_bytes for a window of field_edge; 0 for bad sizes. */
+typedef struct cdnet_aug_geo {
+    double paff[6];
+    double rinv[6];
+    int32_t Hr, Wr, fy0, fx0;
+    uint32_t flags;
+    int32_t reserved;
+} cdnet_aug_geo;
+size_t cdnet_augment_geo_workspace_bytes(int B, int size, int max_radius, int field_edge);
+int cdnet_augment_batch_geo(const cdnet_aug_sample *samples, const cdnet_aug_sample *samples_host, const cdnet_aug_geo *geo,
+                            const cdnet_aug_geo *geo_host, int field_edge, int B, int size, const float *norm_host, void *workspace,
+                            size_t workspace_bytes, float *image, uint8_t *weight, void *label, int label_i32, int32_t *varied, float *field,
+                            void *stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Training-target generation.  Replaces my_transforms_direction.py:687-885 `LabelEncoding.__call__` (3-class-PNG input,
  * do_direction = 1) with get_centerpoint2 (:650-685), Sobel.kernel (SegFix_offset_helper.py:97-132) and

@@ -1,10 +1,12 @@
 """Rate of the device training augmentation (cdnet_amd/augment.py, csrc/augment.hip) against its host implementation.
 
-    python tools/bench_augment.py [--batch 16] [--src 1000] [--size 256] [--iters 50] [--host-samples 2]
+    python tools/bench_augment.py [--batch 16] [--src 1000] [--size 256] [--iters 50] [--host-samples 2] [--recipe full]
 
 Prints one JSON line: ms per batch of B sources of src x src into size x size tiles for augmentation alone (default recipe: alpha 1,
 sigma 50), augmentation + label encoding, and the host implementation (PIL + numpy + scipy, one core) per batch (extrapolated from
---host-samples samples), with the box record (device name, clocks as torch reports them)."""
+--host-samples samples), with the box record (device name, clocks as torch reports them).  With --recipe full the nine-step recipe
+(random_resize [1, 2], random_affine 0.3 and random_rotation added) is timed beside the default one in the same process, and the line
+carries both times and their ratio."""
 import argparse
 import json
 import os
@@ -62,6 +64,8 @@ def main():
     ap.add_argument('--size', type=int, default=256)
     ap.add_argument('--iters', type=int, default=50)
     ap.add_argument('--host-samples', type=int, default=2)
+    ap.add_argument('--recipe', choices=('default', 'full'), default='default',
+                    help='full: also time all nine steps (resize, affine and rotation added) beside the default recipe')
     ap.add_argument('--epoch-rate', action='store_true',
                     help='also: tiles/s of `python -m cdnet_amd.train` epochs over a folder of --batch x 2 sources, with and without --device-augment')
     a = ap.parse_args()
@@ -78,7 +82,7 @@ def main():
     rec = augment.Recipe(size=a.size)
     params = [[augment.draw_params(rs, a.src, a.src, rec) for _ in srcs] for _ in range(a.iters)]
 
-    def run(with_le):
+    def run(with_le, params=params):
         for it in range(3):
             augment.augment_batch(srcs, params[it], a.size)
         torch.cuda.synchronize()
@@ -93,6 +97,15 @@ def main():
         return ev0.elapsed_time(ev1) / a.iters
     aug_ms = run(False)
     aug_le_ms = run(True)
+    full = None
+    if a.recipe == 'full':
+        frec = augment.Recipe(size=a.size, resize=(1, 2), affine=0.3, rotation=True)
+        fparams = [[augment.draw_params(rs, a.src, a.src, frec) for _ in srcs] for _ in range(a.iters)]
+        full_ms, again_ms = run(False, fparams), run(False)              # the default recipe once more after it: drift shows as a gap
+        edges = [max(augment.field_box(p, *p.dims(a.src, a.src), a.size)[2] for p in ps) for ps in fparams]
+        full = {'augment_ms_per_batch': round(full_ms, 4), 'default_again_ms_per_batch': round(again_ms, 4),
+                'full_over_default': round(full_ms / aug_ms, 2), 'mean_field_edge': round(float(np.mean(edges)), 1),
+                'default_field_edge': a.size + 2 * augment.HALO}
     t0 = time.perf_counter()
     for k in range(a.host_samples):
         augment.augment_host(*items[k], params[0][k], a.size)
@@ -102,7 +115,7 @@ def main():
     print(json.dumps({'tool': 'bench_augment', 'batch': a.batch, 'src': a.src, 'size': a.size, 'iters': a.iters,
                       'augment_ms_per_batch': round(aug_ms, 4), 'augment_label_encoding_ms_per_batch': round(aug_le_ms, 4),
                       'tiles_per_s': round(a.batch / aug_le_ms * 1e3, 1), 'host_ms_per_batch': round(host_ms, 1),
-                      'host_over_device': round(host_ms / aug_le_ms, 1), 'epoch_tiles_per_s': epochs,
+                      'host_over_device': round(host_ms / aug_le_ms, 1), 'epoch_tiles_per_s': epochs, 'full_recipe': full,
                       'box': {'device': p.name, 'gcn_arch': getattr(p, 'gcnArchName', ''), 'cus': p.multi_processor_count}}))
 
 
