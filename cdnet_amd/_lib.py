@@ -9,7 +9,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CDNET_LIB_PATH') or os.path.join(_HERE, 'libcdnet_hip.so')      # (the override: A/B builds of tools/build_variant.sh)
 
-_vp, _i, _sz, _f = C.c_void_p, C.c_int, C.c_size_t, C.c_float
+_vp, _i, _sz, _f, _u = C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_uint
 
 class WgradReduceDesc(C.Structure):          # cdnet_wgrad_reduce_desc (include/cdnet_hip.h)
     _fields_ = [('slab', C.c_void_p), ('dw', C.c_void_p)] + [(n, C.c_int) for n in (
@@ -88,6 +88,9 @@ SIGNATURES = {
     'cdnet_dam_loss': (_i, [_vp] * 7 + [_i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     'cdnet_dam_loss_classes_workspace_floats': (_sz, [_i, _i, _i]),
     'cdnet_dam_loss_classes': (_i, [_vp] * 7 + [_i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    'cdnet_dam_loss_terms': (_i, [_vp] * 7 + [_i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _u]),
+    'cdnet_mask_loss_workspace_floats': (_sz, [_i, _i]),
+    'cdnet_mask_loss': (_i, [_vp, _vp, _vp, _i, _i, _i, _u, _vp, _sz, _vp, _vp, _vp]),
     'cdnet_variance_loss_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'cdnet_variance_loss': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     'cdnet_boundary_loss_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),

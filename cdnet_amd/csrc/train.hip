@@ -686,6 +686,7 @@ struct LossIn {
     const int *single;                       // [B]: 1 if the sample's direction map is constant (train_util_dam.py:133,141)
     int B, P;
     int quirk0;                              // mask the direction one-hot with SAMPLE 0's foreground (:139)
+    unsigned terms;                          // CDNET_LOSS_WMAP | CDNET_LOSS_CE | CDNET_LOSS_DICE (cdnet_dam_loss_terms)
 };
 
 // per sample: is the direction label constant (the one-hot of a single class, train_util_dam.py:131-137)?  The same scan
@@ -748,15 +749,6 @@ __device__ __forceinline__ void softmax_n(const float *l, float *p, float *logp)
 #pragma unroll
     for (int c = 0; c < NC; ++c) { p[c] = e[c] / s; logp[c] = l[c] - m - ls; }
 }
-__device__ __forceinline__ void softmax3(const float *l, float *p, float *logp) {
-    const float m = fmaxf(l[0], fmaxf(l[1], l[2]));
-    float e[3], s = 0.f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { e[c] = expf(l[c] - m); s += e[c]; }
-    const float ls = logf(s);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { p[c] = e[c] / s; logp[c] = l[c] - m - ls; }
-}
 __device__ __forceinline__ void softmax9(const float *l, float *p, float *logp) { softmax_n<9>(l, p, logp); }
 
 // target class of the weighted dice for pixel i of sample b: -1 = all one-hot channels are zero
@@ -787,7 +779,7 @@ __global__ __launch_bounds__(LossLay<ND>::TPB) void loss_reduce_kernel(LossIn L,
         for (int c = 0; c < ND; ++c) l9[c] = L.dirn[((size_t)b * ND + c) * L.P + i];
         softmax3(l3, p3, lp3);
         softmax_n<ND>(l9, p9, lp9);
-        const float w = (float)L.weight[ob + i] / 20.f;
+        const float w = (L.terms & CDNET_LOSS_WMAP) ? (float)L.weight[ob + i] / 20.f : 1.f;      // clear: both CE maps and the dice sums unweighted
         int lab = L.label[ob + i], dl = L.dirlab[ob + i];
         lab = lab > 2 ? 2 : lab; dl = dl > ND - 1 ? ND - 1 : dl;   // (out-of-range content is reported through *err, see loss_single_kernel)
         acc[lab][tid] += p3[lab];
@@ -832,9 +824,12 @@ __global__ __launch_bounds__(LossLay<ND>::TPB) void loss_reduce_kernel(LossIn L,
 template <int ND>
 __global__ __launch_bounds__(256) void loss_finalize_kernel(const float *__restrict__ partial, int nchunk, int B, int P,
                                                             float *__restrict__ sums, float *__restrict__ coef,
-                                                            float *__restrict__ losses, const int *__restrict__ err) {
+                                                            float *__restrict__ losses, const int *__restrict__ err, unsigned terms) {
     using Y = LossLay<ND>;
     constexpr int NS = Y::SUMS;
+    // WMAP clear (train_util_dam.py:241-244): the direction dice is the plain MulticlassDiceLoss over the ND classes - a sum over the
+    // classes of the (i, i) ratios, no / ND, no doubled class 0, no neighbour terms - of the sums the reduce kernel took with w = 1
+    const bool plain = !(terms & CDNET_LOSS_WMAP);
     __shared__ float s_sum[64 * NS];      // B <= 64
     const int tid = threadIdx.x;
     for (int idx = tid; idx < B * NS; idx += 256) {
@@ -867,11 +862,12 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(const float *__restr
         for (int i = 0; i < ND; ++i) bsum[i] = 0.f;
         for (int j = 0; j < ND; ++j) {
             {   // (i=j, j)
-                const float U = S[Y::PW + j] + S[Y::TW + j], Sij = S[Y::SS + j], m = j == 0 ? 2.f : 1.f;
+                const float U = S[Y::PW + j] + S[Y::TW + j], Sij = S[Y::SS + j], m = j == 0 && !plain ? 2.f : 1.f;
                 cf[6 + ND + j] = m * -2.f / (fB * (U + 1.f));
                 bsum[j] += m * 2.f * (Sij + 1.f) / (fB * (U + 1.f) * (U + 1.f));
             }
-            if (j >= 1) {
+            if (plain) { cf[6 + 2 * ND + j] = 0.f; cf[6 + 3 * ND + j] = 0.f; }
+            else if (j >= 1) {
                 const int in = dnext<ND>(j), ip = dprev<ND>(j);
                 {   const float U = S[Y::PW + in] + S[Y::TW + j], Sij = S[Y::SN + j];
                     cf[6 + 2 * ND + j] = -2.f / (fB * (U + 1.f));
@@ -911,7 +907,11 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(const float *__restr
             else wd += s_term[3 + i] - (1.f - s_term[T_PREV + i - 1]) - (1.f - s_term[T_NEXT + i - 1]);
         }
         wd /= (float)ND;
-        losses[0] = ce + dice + dce + wd + mse;
+        if (plain) {
+            wd = 0.f;
+            for (int i = 0; i < ND; ++i) wd += s_term[3 + i];
+        }
+        losses[0] = (terms & CDNET_LOSS_CE) ? ce + dice + dce + wd + mse : dice + dce + wd + mse;
         losses[1] = dce; losses[2] = wd; losses[3] = mse; losses[4] = ce; losses[5] = dice;
         // pixel-level metrics, mean over the samples (utils.py:67-110): accuracy, IoU, recall, precision, F1
         double m[5] = {0, 0, 0, 0, 0};
@@ -948,7 +948,7 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(LossIn L, const float *_
         for (int c = 0; c < ND; ++c) l9[c] = L.dirn[((size_t)b * ND + c) * L.P + i];
         softmax3(l3, p3, lp3);
         softmax_n<ND>(l9, p9, lp9);
-        const float w = (float)L.weight[ob + i] / 20.f;
+        const float w = (L.terms & CDNET_LOSS_WMAP) ? (float)L.weight[ob + i] / 20.f : 1.f;      // clear: both CE maps and the dice sums unweighted
         int lab = L.label[ob + i], dl = L.dirlab[ob + i];
         lab = lab > 2 ? 2 : lab; dl = dl > ND - 1 ? ND - 1 : dl;   // (out-of-range content is reported through *err, see loss_single_kernel)
         // mask: dice gradient w.r.t. probabilities, through the softmax, plus the weighted CE
@@ -957,7 +957,8 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(LossIn L, const float *_
         for (int c = 0; c < 3; ++c) { gp[c] = cf[3 + c] + (c == lab ? cf[c] : 0.f); dot = fmaf(p3[c], gp[c], dot); }
 #pragma unroll
         for (int c = 0; c < 3; ++c)
-            dmask[((size_t)b * 3 + c) * L.P + i] = p3[c] * (gp[c] - dot) + w * inv_n * (p3[c] - (c == lab ? 1.f : 0.f));
+            dmask[((size_t)b * 3 + c) * L.P + i] = (L.terms & CDNET_LOSS_CE) ? p3[c] * (gp[c] - dot) + w * inv_n * (p3[c] - (c == lab ? 1.f : 0.f))
+                                                                              : p3[c] * (gp[c] - dot);
         // direction: weighted cyclic dice (average over the ND classes) + weighted CE
         const int t = dice_target<ND>(L, b, i);
         float gq[ND], dotq = 0.f;
@@ -974,7 +975,7 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(LossIn L, const float *_
             }
         }
 #pragma unroll
-        for (int c = 0; c < ND; ++c) { gq[c] *= w * (1.f / (float)ND); dotq = fmaf(p9[c], gq[c], dotq); }
+        for (int c = 0; c < ND; ++c) { if (L.terms & CDNET_LOSS_WMAP) gq[c] *= w * (1.f / (float)ND); dotq = fmaf(p9[c], gq[c], dotq); }
 #pragma unroll
         for (int c = 0; c < ND; ++c)
             ddir[((size_t)b * ND + c) * L.P + i] = p9[c] * (gq[c] - dotq) + w * inv_n * (p9[c] - (c == dl ? 1.f : 0.f));
@@ -1298,11 +1299,6 @@ extern "C" int cdnet_dam_head_backward_fused(const cdnet_head_feat *f1, const cd
     return check_launch("cdnet_dam_head_backward_fused");
 }
 
-static int loss_nchunk(int P, int tpb) {
-    int nchunk = cdiv(P, tpb * 8);
-    return nchunk > 64 ? 64 : nchunk;
-}
-
 template <int ND>
 static size_t dam_loss_ws(int B, int P) {
     using Y = LossLay<ND>;
@@ -1323,7 +1319,7 @@ static int dam_loss_impl(LossIn L, int B, int P, float *workspace, float *losses
     L.single = single;
     loss_single_kernel<<<B, 1024, 0, st>>>(L.dirlab, L.label, P, ND, single, err);
     loss_reduce_kernel<ND><<<dim3(nchunk, B), Y::TPB, 0, st>>>(L, partial);
-    loss_finalize_kernel<ND><<<1, 256, 0, st>>>(partial, nchunk, B, P, sums, coef, losses, err);
+    loss_finalize_kernel<ND><<<1, 256, 0, st>>>(partial, nchunk, B, P, sums, coef, losses, err, L.terms);
     if (dmask) loss_grad_kernel<ND><<<dim3(lin_grid((size_t)P, 256), B), 256, 0, st>>>(L, coef, dmask, dpoint, ddir);
     return check_launch("cdnet_dam_loss");
 }
@@ -1333,12 +1329,14 @@ extern "C" size_t cdnet_dam_loss_classes_workspace_floats(int B, int P, int dire
 }
 extern "C" size_t cdnet_dam_loss_workspace_floats(int B, int P) { return dam_loss_ws<9>(B, P); }
 
-extern "C" int cdnet_dam_loss_classes(const float *mask, const float *point, const float *dirn, const uint8_t *label, const uint8_t *dirlab,
-                                      const uint16_t *point_target_f16, const uint8_t *weight_u8, int B, int H, int W, int direction_classes,
-                                      int quirk_sample0, float *workspace, size_t workspace_floats, float *losses, float *dmask,
-                                      float *dpoint, float *ddir, void *stream) {
-    CDNET_REQUIRE(mask && point && dirn && label && dirlab && point_target_f16 && weight_u8 && workspace && losses,
-                  "cdnet_dam_loss: null pointer");
+extern "C" int cdnet_dam_loss_terms(const float *mask, const float *point, const float *dirn, const uint8_t *label, const uint8_t *dirlab,
+                                    const uint16_t *point_target_f16, const uint8_t *weight_u8, int B, int H, int W, int direction_classes,
+                                    int quirk_sample0, float *workspace, size_t workspace_floats, float *losses, float *dmask,
+                                    float *dpoint, float *ddir, void *stream, unsigned terms) {
+    CDNET_REQUIRE(mask && point && dirn && label && dirlab && point_target_f16 && workspace && losses, "cdnet_dam_loss: null pointer");
+    CDNET_REQUIRE((terms & ~(CDNET_LOSS_WMAP | CDNET_LOSS_CE | CDNET_LOSS_DICE)) == 0, "cdnet_dam_loss: terms %u has unknown bits", terms);
+    CDNET_REQUIRE(terms & CDNET_LOSS_DICE, "cdnet_dam_loss: the DAM loss has no configuration without the dice terms (train_util_dam.py:297)");
+    CDNET_REQUIRE(weight_u8 || !(terms & CDNET_LOSS_WMAP), "cdnet_dam_loss: CDNET_LOSS_WMAP needs the weight map");
     CDNET_REQUIRE(B >= 1 && B <= 64 && H > 0 && W > 0, "cdnet_dam_loss: batch %d not in [1,64]", B);
     CDNET_REQUIRE(direction_classes == 5 || direction_classes == 9 || direction_classes == 17,
                   "cdnet_dam_loss: direction_classes %d must be 5, 9 or 17 (options.py:45)", direction_classes);
@@ -1347,11 +1345,21 @@ extern "C" int cdnet_dam_loss_classes(const float *mask, const float *point, con
     if (dmask) CDNET_REQUIRE(dpoint && ddir, "cdnet_dam_loss: all three gradient outputs or none");
     LossIn L;
     L.mask = mask; L.point = point; L.dirn = dirn; L.label = label; L.dirlab = dirlab; L.point_t = point_target_f16;
-    L.weight = weight_u8; L.single = nullptr; L.B = B; L.P = P; L.quirk0 = quirk_sample0;
+    L.weight = weight_u8; L.single = nullptr; L.B = B; L.P = P; L.quirk0 = quirk_sample0; L.terms = terms;
     hipStream_t st = (hipStream_t)stream;
     if (direction_classes == 5) return dam_loss_impl<5>(L, B, P, workspace, losses, dmask, dpoint, ddir, st);
     if (direction_classes == 17) return dam_loss_impl<17>(L, B, P, workspace, losses, dmask, dpoint, ddir, st);
     return dam_loss_impl<9>(L, B, P, workspace, losses, dmask, dpoint, ddir, st);
+}
+
+extern "C" int cdnet_dam_loss_classes(const float *mask, const float *point, const float *dirn, const uint8_t *label, const uint8_t *dirlab,
+                                      const uint16_t *point_target_f16, const uint8_t *weight_u8, int B, int H, int W, int direction_classes,
+                                      int quirk_sample0, float *workspace, size_t workspace_floats, float *losses, float *dmask,
+                                      float *dpoint, float *ddir, void *stream) {
+    CDNET_REQUIRE(weight_u8, "cdnet_dam_loss: null pointer");
+    return cdnet_dam_loss_terms(mask, point, dirn, label, dirlab, point_target_f16, weight_u8, B, H, W, direction_classes, quirk_sample0,
+                                workspace, workspace_floats, losses, dmask, dpoint, ddir, stream,
+                                CDNET_LOSS_WMAP | CDNET_LOSS_CE | CDNET_LOSS_DICE);
 }
 
 extern "C" int cdnet_dam_loss(const float *mask, const float *point, const float *dirn, const uint8_t *label, const uint8_t *dirlab,

@@ -1,6 +1,6 @@
 """Training entry point with the reference's shape (train.py:59-530, the part that is the hot path): options -> seeds ->
-`chooseModel` -> optimiser and scheduler (`utils.get_optimizer`) -> epochs of `train_util_dam.train` (or the plain-UNet step), each
-followed by the scheduler step -> checkpoint.
+`chooseModel` -> optimiser and scheduler (`utils.get_optimizer`) -> epochs of `train_util_dam.train` (the plain UNet: `train_util.train`),
+each followed by validation, the scheduler step and the checkpoint.
 
     python -m cdnet_amd.train --synthetic 64 --epochs 2              # synthetic tiles (no dataset needed)
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m cdnet_amd.train ...   # one process per GPU, RCCL all-reduce
@@ -21,7 +21,7 @@ import time
 import numpy as np
 import torch
 
-from . import checkpoint, synth, train_util_dam, utils
+from . import checkpoint, synth, train_util, train_util_dam, utils
 from .options import Options
 
 
@@ -111,7 +111,7 @@ def main(argv=None):
         logger.info('{:d} training images in {:s}'.format(len(dset), dir_list[0]))
     # validation set (train.py:262-290: <img_dir>/val etc.) for the best-checkpoint / early-stopping logic of train.py:348-447
     val_loader = None
-    if opt.train['validation'] == 1 and not plain_unet:
+    if opt.train['validation'] == 1:
         if own.synthetic > 0:
             val_loader = _SyntheticLoader(max(1, own.synthetic_val), B, dev, seed=opt.train['seed'] + 777 + 1000 * rank)
         else:
@@ -130,21 +130,23 @@ def main(argv=None):
     for epoch in range(opt.train['start_epoch'], opt.train['num_epochs']):
         t0 = time.time()
         if plain_unet:
-            tot = np.zeros(3)
-            for x, w, target0, _, _ in loader:
-                tot += trainer.train_step(x, train_util_dam._label3(target0), w[:, 0].contiguous()).cpu().numpy()
-            res = trainer.reduce_scalars(tot / len(loader))
+            dice_out = []
+            res8 = train_util.train(loader, model, trainer, None, epoch, opt, logger, dice_out=dice_out)
+            res = np.array([res8[0], res8[1], dice_out[0]])          # [loss, CE, dice]
         else:
             res = train_util_dam.train(loader, model, trainer, None, epoch, opt, logger)
         torch.cuda.synchronize()
         dt = time.time() - t0
         logger.info('epoch {:d}: loss {:.4f}  ({:.1f} tiles/s on {:d} GPU(s))'.format(epoch + 1, float(res[0]), world * B * len(loader) / dt, world))
         # train.py:348-387: validation results (or the training results standing in for them), best model by val_iou
-        if val_loader is not None:
+        if plain_unet:
+            val = None
+            if val_loader is not None:
+                val = trainer.reduce_scalars(train_util.validate(val_loader, model, None, epoch, opt, logger, all_img_test=opt.all_img_test))
+            val_loss, val_iou, val_F1 = train_util.epoch_scores(res8, val)
+        elif val_loader is not None:
             val = trainer.reduce_scalars(train_util_dam.validate(val_loader, model, None, opt, logger, all_img_test=opt.all_img_test))
             val_loss, val_iou, val_F1 = float(val[0]), float(val[5]), float(val[8])
-        elif plain_unet:
-            val_loss, val_iou, val_F1 = float(res[0]), 0.0, 0.0
         else:
             val_loss, val_iou, val_F1 = float(res[0]), float(res[7]), float(res[10])
         is_best = val_iou > best_iou                       # train.py:385
@@ -160,8 +162,6 @@ def main(argv=None):
             logger.info('===================== Updating learning rate from {} to {} ====================='.format(prev_lr, trainer.lr))
         if rank == 0 and opt.train.get('save_dir'):
             # train.py:406-427: checkpoint.pth.tar every epoch, numbered copies at checkpoint_freq, checkpoint_best on a new best
-            if val_loader is None and plain_unet:
-                is_best = val_loss < best_loss
             best_loss = new_best_loss
             cp_flag = int((epoch + 1) % opt.train['checkpoint_freq'] == 0 or epoch + 1 == opt.train['num_epochs'])
             os.makedirs(opt.train['save_dir'], exist_ok=True)

@@ -35,18 +35,27 @@ def _label3(target0, boundary=2):
     return t.to(torch.uint8)
 
 
-def _check_branches(opt, model):
+def _check_branches(opt, model, alphas=(0, 1)):
     """the option combinations the reference's loops accept for the model at hand (train_util_dam.py:152-166): three outputs ->
     direction = 1 and mseloss = 1 (the defaults); the two-output ablation models (mask + direction) -> direction = 1 and mseloss = 0
     (with mseloss = 1 the reference would read the direction logits as the point map).  alpha = 0: no variance term; alpha = 1: loss_CE +
-    the instance variance term (:174-180, cdnet_variance_loss).  Every other value raises: the reference ignores it silently (:191-193),
-    except 2, its "variance instead of cross-entropy" (:182-189), which is not built here."""
+    the instance variance term (:174-180, cdnet_variance_loss); alpha = 2: twice that term instead of the mask cross-entropy (:182-189).
+    `alphas` are the values the caller's loss path serves: a caller of the all-terms entry (cdnet_dam_loss_classes) serves 0 and 1 - the
+    default -, train() and validate() below go through the term word (cdnet_dam_loss_terms, CDNET_LOSS_CE clear) and pass (0, 1, 2).
+    Every other value raises: the reference ignores it silently (:191-193).  dice must be 1: with 0 or 2 the reference's DAM loop dies
+    on an unbound loss_direction_dice (:297)."""
     two = getattr(model, 'VARIANT', 'rev1') == 'MandD'
     alpha = opt.train['alpha']
-    if alpha not in (0, 1):
-        raise ValueError('alpha = %r: 0 (no variance term) or 1 (loss_CE + loss_var) are built%s' % (
-            alpha, '; alpha = 2 (the variance term instead of the cross-entropy) would need the cross-entropy gradient taken out of the '
-                   'fused loss kernel and is out of scope' if alpha == 2 else ''))
+    if alpha not in alphas:
+        raise ValueError('alpha = %r: %s are served here%s' % (
+            alpha, ', '.join('%d' % a for a in alphas),
+            '; alpha = 2 (the variance term instead of the cross-entropy) needs the cross-entropy gradient taken out of the loss, which is out '
+            'of scope of the all-terms loss entry: pass alphas=(0, 1, 2) and use cdnet_dam_loss_terms' if alpha == 2 else ''))
+    if opt.model.get('dice', 1) != 1:
+        raise ValueError("dice = %r with a DAM model: the reference's loop raises UnboundLocalError on loss_direction_dice for anything but 1 "
+                         '(train_util_dam.py:297); --dice 0|2 serve the plain UNet' % (opt.model.get('dice'),))
+    if opt.model.get('add_weightMap', 1) not in (0, 1):
+        raise ValueError('weight_map = %r: 0 or 1' % (opt.model.get('add_weightMap'),))
     assert opt.model['direction'] == 1, 'the fused loss implements direction = 1'
     if two:
         assert opt.model['mseloss'] in (0, 1), opt.model['mseloss']       # 0 is the reference's setting; 1 is tolerated (no point term either way)
@@ -72,7 +81,7 @@ def _boundary_value(mask, label, kind):
 def train(train_loader, model, optimizer, criterion, epoch, opt, logger, get_process_worktime=1, get_process_detail=1,
           accuracy_tensor=0):
     trainer = optimizer
-    _check_branches(opt, trainer.model)
+    _check_branches(opt, trainer.model, alphas=(0, 1, 2))
     results = utils.AverageMeter(11)
     dev = trainer.dev
     for i, sample in enumerate(train_loader):
@@ -84,7 +93,7 @@ def train(train_loader, model, optimizer, criterion, epoch, opt, logger, get_pro
                                     target_point0.to(dev).to(torch.float16).contiguous(), w)
         r = losses.detach().cpu().numpy().astype(np.float64)
         # slot 5 of the device tensor is the dice term; the reference logs loss_var there: torch.ones(1) * -1 when alpha == 0 (:191-193)
-        r[5] = float(trainer.loss_var.item()) if opt.train['alpha'] == 1 else -1.0
+        r[5] = float(trainer.loss_var.item()) if opt.train['alpha'] in (1, 2) else -1.0
         results.update(r, input.size(0))
         if i % opt.train['log_interval'] == 0 and logger is not None:
             logger.info('\tIteration: [{:d}/{:d}]\tLoss {r[0]:.4f}\tloss_direction_CE {r[1]:.4f}\tloss_direction_dice {r[2]:.4f}'
@@ -110,8 +119,7 @@ def validate(val_loader, model, criterion, opt, logger, get_process_worktime=1, 
     are utils.nuclei_accuracy_object_level of sample 0's post-processed inside class (:588-604)."""
     import ctypes as C
     from . import _lib
-    _check_branches(opt, model)
-    assert opt.model['dice'] == 1, 'validate implements the default configuration (dice = 1)'
+    _check_branches(opt, model, alphas=(0, 1, 2))
     results = utils.AverageMeter(16)
     model.eval()
     dev = next(model.parameters()).device
@@ -122,6 +130,8 @@ def validate(val_loader, model, criterion, opt, logger, get_process_worktime=1, 
         label = _label3(target0.to(dev), 2 if opt.model['multi_class'] else 1).contiguous()
         w = weight_map.to(dev)
         w = (w[:, 0] if w.dim() == 4 else w).to(torch.uint8).contiguous()
+        if opt.model.get('add_weightMap', 1) == 0:
+            w = torch.full_like(w, 20)               # :549-550: the direction CE map stays unweighted - a weight plane of 20 / 20 = 1.0 exactly
         dirlab = target_direction0.to(dev).to(torch.uint8).contiguous()
         point_t = target_point0.to(dev).to(torch.float16).contiguous()
         x = input.to(dev).float()

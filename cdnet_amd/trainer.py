@@ -134,7 +134,9 @@ class Trainer:
         self._bufs = {}
         self._wss = {}
         self.losses = torch.zeros((11,), dtype=torch.float32, device=self.dev)     # 6 loss values + 5 pixel metrics
-        self.alpha = 0.0                                   # 1: + the instance variance term (train_util_dam.py:174-180), cdnet_variance_loss
+        self.alpha = 0.0                                   # 1: + the instance variance term (train_util_dam.py:174-180), cdnet_variance_loss;
+        #                                                    2: 2 x that term instead of the mask cross-entropy (:182-189)
+        self.dice, self.weight_map = 1, 1                  # --dice 0|1|2, --weight-map 0|1: the `terms` word of the loss entries (utils.loss_terms)
         self.loss_var = torch.full((1,), -1.0, dtype=torch.float32, device=self.dev)       # -1 as long as the term is off (:192)
         self.boundary = 0                                  # 1 / 2 / 3: + BoundaryLoss / FocalLoss2d / RobustFocalLoss2d of the mask logits (:195-205)
         self.loss_boundary = torch.zeros((1,), dtype=torch.float32, device=self.dev)       # the term's value of the last step (0 while it is off)
@@ -272,29 +274,41 @@ class Trainer:
         ddir = self.buf('ddir', direction.shape, torch.float32)
         assert label.dtype == torch.uint8 and dirlab.dtype == torch.uint8 and weight.dtype == torch.uint8
         assert point_t.dtype == torch.float16
-        _lib.call('cdnet_dam_loss_classes', _lib.ptr(mask), _lib.ptr(point), _lib.ptr(direction), _lib.ptr(label.contiguous()),
-                  _lib.ptr(dirlab.contiguous()), _lib.ptr(point_t.contiguous()), _lib.ptr(weight.contiguous()), B, H, W, ND,
-                  self.quirk, _lib.ptr(ws), ws.numel(), _lib.ptr(self.losses), _lib.ptr(dmask),
-                  _lib.ptr(dpoint), _lib.ptr(ddir), _lib.stream_ptr())
+        if self.dice != 1:
+            raise ValueError('dice = %r with a DAM model: the reference dies on an unbound loss_direction_dice (train_util_dam.py:297); only 1 works'
+                             % (self.dice,))
+        from .utils import loss_terms
+        terms = loss_terms(self.dice, self.weight_map, self.alpha)
+        args = (_lib.ptr(mask), _lib.ptr(point), _lib.ptr(direction), _lib.ptr(label.contiguous()),
+                _lib.ptr(dirlab.contiguous()), _lib.ptr(point_t.contiguous()), _lib.ptr(weight.contiguous()), B, H, W, ND,
+                self.quirk, _lib.ptr(ws), ws.numel(), _lib.ptr(self.losses), _lib.ptr(dmask),
+                _lib.ptr(dpoint), _lib.ptr(ddir), _lib.stream_ptr())
+        if terms == 7:                                 # every term: the entry of the default configuration
+            _lib.call('cdnet_dam_loss_classes', *args)
+        else:                                          # --weight-map 0 and / or --alpha 2
+            _lib.call('cdnet_dam_loss_terms', *args, terms)
         if self.alpha:
             self._variance_term(mask, label, dmask)
         if self.boundary:
             self._boundary_term(mask, label, dmask)
         return dmask, dpoint, ddir
 
-    def _variance_term(self, mask, label, dmask):
-        """alpha = 1 (train_util_dam.py:174-180): loss_var of the mask logits into self.loss_var, added to losses[0] and its gradient to dmask"""
-        if self.alpha != 1:
-            raise ValueError('alpha = %r: the variance term is built for alpha = 1 (0 switches it off)' % (self.alpha,))
+    def _variance_term(self, mask, label, dmask, total=None):
+        """alpha = 1 or 2 (train_util_dam.py:174-189): loss_var of the mask logits into self.loss_var, alpha x it added to `total` (losses[0]
+        unless given) and alpha x its gradient to dmask; dmask None: the value alone (total stays untouched)"""
+        if self.alpha not in (1, 2):
+            raise ValueError('alpha = %r: the variance term is built for alpha = 1 and 2 (0 switches it off)' % (self.alpha,))
         B, K, H, W = mask.shape
         need = _lib.load().cdnet_variance_loss_workspace_bytes(B, K, H, W)
         ws = self._ws('variance', (need + 3) // 4)
+        total = self.losses[0:1] if total is None else total
         _lib.call('cdnet_variance_loss', _lib.ptr(mask), _lib.ptr(label.contiguous()), 1, B, K, H, W, float(self.alpha), _lib.ptr(ws),
-                  ws.numel() * 4, _lib.ptr(self.loss_var), _lib.ptr(self.losses[0:1]), _lib.ptr(dmask), None, None, _lib.stream_ptr())
+                  ws.numel() * 4, _lib.ptr(self.loss_var), None if dmask is None else _lib.ptr(total), None if dmask is None else _lib.ptr(dmask),
+                  None, None, _lib.stream_ptr())
 
-    def _boundary_term(self, mask, label, dmask):
+    def _boundary_term(self, mask, label, dmask, total=None):
         """boundary_loss = 1 / 2 / 3 (train_util_dam.py:195-205, beta = 1): the term of the mask logits into self.loss_boundary, added to
-        losses[0] and its gradient to dmask (cdnet_boundary_loss)"""
+        `total` (losses[0] unless given) and its gradient to dmask (cdnet_boundary_loss)"""
         if self.boundary not in (1, 2, 3):
             raise ValueError('boundary = %r: 1 (BoundaryLoss), 2 (FocalLoss2d) or 3 (RobustFocalLoss2d); 0 switches the term off' % (self.boundary,))
         B, K, H, W = mask.shape
@@ -302,8 +316,9 @@ class Trainer:
         if need == 0:
             raise ValueError('the boundary term serves three-class mask logits, got %s' % (tuple(mask.shape),))
         ws = self._ws('boundary', (need + 3) // 4)
+        total = self.losses[0:1] if total is None else total
         _lib.call('cdnet_boundary_loss', _lib.ptr(mask), _lib.ptr(label.contiguous()), self.boundary, B, K, H, W, 1.0, _lib.ptr(ws),
-                  ws.numel() * 4, _lib.ptr(self.loss_boundary), _lib.ptr(self.losses[0:1]), _lib.ptr(dmask), _lib.stream_ptr())
+                  ws.numel() * 4, _lib.ptr(self.loss_boundary), _lib.ptr(total), _lib.ptr(dmask), _lib.stream_ptr())
 
     # ------------------------------------------------------------------------------------------------
     def backward(self, dmask, dpoint, ddir):
@@ -876,30 +891,44 @@ class Trainer:
 
 
 class UNetTrainer(Trainer):
-    """Body of the plain-UNet train iteration (train_util.py:58-200 with the default options: log-softmax + NLL x weight
-    map mean, + MulticlassDiceLoss on the softmax; `alpha` and `boundary` add their terms as in Trainer) -> backward -> Adam.
-    The two loss terms are exactly the mask terms of the DAM loss kernel, which is fed constant point / direction
-    branches here; `losses` = [total, CE x weight, dice]."""
+    """Body of the plain-UNet train iteration (train_util.py:58-234): log-softmax + NLL (x weight map / 20 with `weight_map`) mean,
+    + MulticlassDiceLoss on the softmax (`dice` 1; 2: the dice term alone; 0: none), `alpha` 1 adds the variance term and 2 puts twice
+    that term in the cross-entropy's place, `boundary` adds its term -> backward -> the optimiser step.  The loss, its gradient and the
+    pixel metrics of the arg-max come from one cdnet_mask_loss call: `unet_losses` = [total, CE, dice], `unet_metrics` = [accuracy, IoU,
+    recall, precision, F1] (:209-218)."""
 
     def __init__(self, model, **kw):
         super().__init__(model, **kw)
-        self.unet_losses = torch.zeros((3,), dtype=torch.float32, device=self.dev)
+        self.mask_losses = torch.zeros((8,), dtype=torch.float32, device=self.dev)      # cdnet_mask_loss: total, ce, dice, 5 metrics
+        self.unet_losses = self.mask_losses[0:3]
+        self.unet_metrics = self.mask_losses[3:8]
+
+    def mask_loss(self, logits, label, weight, terms, dmask):
+        """one cdnet_mask_loss call into `mask_losses`; dmask None: values only (validate)"""
+        B, K, H, W = logits.shape
+        if K != 3:
+            raise ValueError('the mask loss serves the 3-class configuration (options.py: out_c = 3), got %d classes' % K)
+        assert label.dtype == torch.uint8 and (weight is None or weight.dtype == torch.uint8)
+        ws = self._ws('mask_loss', _lib.load().cdnet_mask_loss_workspace_floats(B, H * W))
+        _lib.call('cdnet_mask_loss', _lib.ptr(logits), _lib.ptr(label.contiguous()), None if weight is None else _lib.ptr(weight.contiguous()),
+                  B, H, W, terms, _lib.ptr(ws), ws.numel(), _lib.ptr(self.mask_losses), None if dmask is None else _lib.ptr(dmask),
+                  _lib.stream_ptr())
 
     def loss_and_grads(self, logits, label, weight):
-        B, K, H, W = logits.shape
-        assert K == 3, 'the fused loss serves the 3-class configuration (options.py: out_c = 3)'
-        z = lambda shape, dt: self.buf(('zero',) + tuple(shape) + (dt,), shape, dt)
-        point, dirn = z((B, 1, H, W), torch.float32), z((B, 9, H, W), torch.float32)
-        dirlab, point_t = z((B, H, W), torch.uint8), z((B, H, W), torch.float16)
-        for t in (point, dirn, dirlab, point_t):
-            t.zero_()
-        dmask, _, _ = super().loss_and_grads(logits, point, dirn, label, dirlab, point_t, weight)
-        self.unet_losses[1:3] = self.losses[4:6]
-        self.unet_losses[0] = self.losses[4] + self.losses[5]
+        from .utils import loss_terms
+        terms = loss_terms(self.dice, self.weight_map, self.alpha)
+        dmask = self.buf('dmask', logits.shape, torch.float32)
+        self.mask_loss(logits, label, weight, terms, dmask)
+        total = self.mask_losses[0:1]
+        if self.dice == 2:
+            # train_util.py:187-190: loss = loss_dice - the variance term is computed for the log only, the boundary term not at all
+            if self.alpha:
+                self._variance_term(logits, label, None)
+            return dmask
         if self.alpha:
-            self.unet_losses[0] += self.loss_var[0]        # train_util.py: loss = loss_CE + alpha * loss_var (+ dice)
+            self._variance_term(logits, label, dmask, total)       # loss = loss_CE + loss_var (alpha 1) | 2 * loss_var (alpha 2) (+ dice)
         if self.boundary:
-            self.unet_losses[0] += self.loss_boundary[0]   # train_util.py:170-178: loss = loss + beta * boundary_loss, beta = 1
+            self._boundary_term(logits, label, dmask, total)       # train_util.py:170-178: loss = loss + beta * boundary_loss, beta = 1
         return dmask
 
     def backward(self, dlogits):

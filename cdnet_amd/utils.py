@@ -162,6 +162,30 @@ def trainer_class(model):
     return AblationTrainer if getattr(model, 'VARIANT', 'rev1') != 'rev1' else Trainer
 
 
+LOSS_WMAP, LOSS_CE, LOSS_DICE = 1, 2, 4              # CDNET_LOSS_* (include/cdnet_hip.h)
+
+
+def loss_terms(dice=1, weight_map=1, alpha=0):
+    """the `terms` word of cdnet_mask_loss / cdnet_dam_loss_terms for the option triple (--dice, --weight-map, --alpha):
+      weight_map 1 -> WMAP: the CE map x weight / 20 (train_util.py:134-135);
+      dice 1 / 2   -> DICE: + MulticlassDiceLoss (:183-186) / the dice term alone (:187-190), which takes CE out of the total;
+      alpha 2      -> the variance term instead of the cross-entropy (:148-155): CE out of the total.
+    Any other value raises ValueError: the reference ignores it silently, except alpha = 3 (its SSIM experiment, not built)."""
+    if dice not in (0, 1, 2):
+        raise ValueError('dice = %r: 0 (no dice term), 1 (+ MulticlassDiceLoss) or 2 (the dice term alone)' % (dice,))
+    if weight_map not in (0, 1):
+        raise ValueError('weight_map = %r: 0 (plain cross-entropy) or 1 (cross-entropy x weight map / 20)' % (weight_map,))
+    if alpha not in (0, 1, 2):
+        raise ValueError('alpha = %r: 0 (no variance term), 1 (loss_CE + loss_var) or 2 (2 * loss_var instead of loss_CE)%s'
+                         % (alpha, '; alpha = 3 (SSIM) is not built' if alpha == 3 else ''))
+    terms = LOSS_WMAP if weight_map == 1 else 0
+    if alpha != 2 and dice != 2:
+        terms |= LOSS_CE
+    if dice != 0:
+        terms |= LOSS_DICE
+    return terms
+
+
 def get_optimizer(args, model, world_size=1):
     """utils.py:907-962: returns (Trainer, scheduler).  cdnet_amd.trainer.Trainer steps the fused device optimiser (cdnet_amd.optim.stepper) - 'adam'
     (lr, betas=(0.9, 0.99), weight_decay; cdnet_adam_step) or one of 'sgd' (momentum = args.momentum), 'radam', 'radam4s', 'adamw',
@@ -173,6 +197,10 @@ def get_optimizer(args, model, world_size=1):
     if boundary not in (0, 1, 2, 3):
         # the reference adds nothing for any other value and says nothing (train_util_dam.py:207-208)
         raise ValueError('boundary_loss = %r: 0 (off), 1 (BoundaryLoss), 2 (FocalLoss2d) or 3 (RobustFocalLoss2d)' % (boundary,))
+    md = getattr(args, 'model', {})
+    dice, weight_map, alpha = md.get('dice', 1), md.get('add_weightMap', 1), args.train.get('alpha', 0.0)
+    loss_terms(dice, weight_map, alpha)                                          # ValueError on anything but 0|1|2, 0|1, 0|1|2
+    dice, weight_map = int(dice), int(weight_map)
     name = str(args.train['optimizer']).lower()
     if name not in optim.OPTIMIZERS:
         raise ValueError('Optimizer {} not available'.format(args.train['optimizer']))
@@ -180,6 +208,7 @@ def get_optimizer(args, model, world_size=1):
                                    optimizer=name, momentum=getattr(args, 'momentum', 0.95))
     trainer.alpha = float(args.train.get('alpha', 0.0))           # 1: + the instance variance term (train_util_dam.py:174-180)
     trainer.boundary = boundary                                   # 1 / 2 / 3: + the boundary / focal term (train_util_dam.py:195-205)
+    trainer.dice, trainer.weight_map = dice, weight_map           # --dice 0|1|2, --weight-map 0|1 (train_util.py:134-136, 183-190)
     scheduler = None
     if args.train['scheduler'] in optim.SCHEDULERS:
         scheduler = optim.LRSchedule(args.train['scheduler'], args.train['lr'], step=args.train['step'], lr_decay=args.train['lr_decay'])

@@ -518,7 +518,41 @@ int cdnet_dam_loss_classes(const float *mask, const float *point, const float *d
                            int direction_classes, int quirk_sample0, float *workspace, size_t workspace_floats, float *losses,
                            float *dmask, float *dpoint, float *ddir, void *stream);
 
-/* The instance variance term of the training loss (--alpha 1).  Replaces train_util_dam.py:174-180: F.softmax of the mask logits, the per-sample
+/* The switches of the mask and DAM losses (options.py --weight-map, --dice, --alpha 2): one word of term bits. */
+#define CDNET_LOSS_WMAP 1u   /* CE map x weight / 20 (train_util.py:134-135) */
+#define CDNET_LOSS_CE   2u   /* mask CE in total and gradient */
+#define CDNET_LOSS_DICE 4u   /* MulticlassDiceLoss of softmax(mask) in total and gradient */
+
+/* cdnet_dam_loss_classes with the term word; cdnet_dam_loss_classes is this entry with every term set, with unchanged results.
+ *   WMAP clear (--weight-map 0, train_util_dam.py:170-172, 229-246): both CE maps are unweighted and weight_u8 may be NULL; the direction dice
+ *     becomes the plain MulticlassDiceLoss over the direction classes (:241-244: a sum over the classes, no / classes, no doubled class 0, no
+ *     neighbour terms) against the same one-hot target (sample-0 quirk and constant-map rule kept); slot 2 of `losses` reports it.
+ *   CE clear (--alpha 2, :182-189): the mask CE leaves the total and dmask and stays in slot 4.
+ *   DICE clear: CDNET_E_ARG - the reference has no working DAM configuration without it (--dice 0|2 dies at :297 on an unbound
+ *     loss_direction_dice). */
+int cdnet_dam_loss_terms(const float *mask, const float *point, const float *direction, const uint8_t *label,
+                         const uint8_t *dirlab, const uint16_t *point_target_f16, const uint8_t *weight_u8, int B, int H, int W,
+                         int direction_classes, int quirk_sample0, float *workspace, size_t workspace_floats, float *losses,
+                         float *dmask, float *dpoint, float *ddir, void *stream, unsigned terms);
+
+/* The plain UNet's loss and pixel metrics (mask_loss.hip).  Replaces train_util.py:128-136 (log-softmax + NLL, x weight map / 20 with
+ * add_weightMap), :183-190 (MulticlassDiceLoss of the softmax, loss.py:131-176; dice = 2: the dice term alone), :209-218 with utils.py:67-110
+ * (accuracy_pixel_level of the arg-max), and the gradient autograd takes; validate's unweighted CE (:387-389) is the same entry with WMAP clear.
+ * mask_logits f32 [B][3][H][W]; label u8 [B][H][W] in {0,1,2}; weight_u8 u8 [B][H][W], NULL allowed when WMAP is clear; 1 <= B <= 64.
+ * losses f32 [8] = {total, ce, dice, accuracy, IoU, recall, precision, F1}: ce = mean of -log p_label (x w / 20 with WMAP), dice = sum_c
+ * (1 - mean_b 2 (I_c + 1) / (P_c + T_c + 1)); both are always reported, total holds the terms that are on (both: the fp32 sum ce + dice).  The
+ * metrics score arg-max (first maximum) == 1 against label == 1 from per-sample tp / fp / fn counts, finished in double.
+ * dmask NULL or f32 [B][3][H][W]: written (not accumulated) with d total / d logits - zeros when neither term is on; cdnet_variance_loss and
+ * cdnet_boundary_loss add to it afterwards.  A label above 2 makes all eight values NaN and nothing is read or written out of bounds.
+ * With WMAP | CE | DICE the values and the gradient equal cdnet_dam_loss_classes' mask terms bit for bit.  No atomics except the error flag,
+ * no host synchronisation, fixed-order sums; argument errors (CDNET_E_ARG, a short workspace included) are found before any HIP call.
+ * workspace: cdnet_mask_loss_workspace_floats(B, H * W) floats. */
+size_t cdnet_mask_loss_workspace_floats(int B, int P);
+int cdnet_mask_loss(const float *mask_logits, const uint8_t *label, const uint8_t *weight_u8, int B, int H, int W, unsigned terms,
+                    float *workspace, size_t workspace_floats, float *losses, float *dmask, void *stream);
+
+/* The instance variance term of the training loss (--alpha 1; --alpha 2, :182-189: alpha = 2 here and CDNET_LOSS_CE clear in the loss entry).
+ * Replaces train_util_dam.py:174-180: F.softmax of the mask logits, the per-sample
  * skimage.measure.label(target == 1) on the CPU (8-connectivity) and LossVariance (loss.py:9-33), with the gradient autograd takes through both:
  *   loss_var = (1/B) sum_k [ sum over the instances with n > 1 pixels and the K channels of  sum_i (p_ci - mu_c)^2 / (n - 1) ] / (U_k + 1e-8),
  *   U_k = number of instances of sample k (single pixels included); a sample without foreground contributes 0.
