@@ -1,6 +1,6 @@
-// Host-side launch helpers of the convolution and weight-gradient launchers (conv.hip, conv32.hip, conv32ws.hip, conv16ws.hip,
-// wgrad.hip): the CU count, the large-LDS opt-in, the persistent-grid rule, the movers' reach check and the run-time -> template
-// argument dispatch.  Host code only.
+// Host-side launch helpers: the CU count, the large-LDS opt-in, the persistent-grid rule and the movers' reach check of the
+// convolution and weight-gradient launchers (conv.hip, conv32.hip, conv32ws.hip, conv16ws.hip, wgrad.hip); the linear-grid rule of the
+// streaming kernels and the run-time -> template argument dispatch for every launcher.  Host code only.
 // One device per process is assumed: the CU count and the opt-in flags are kept per process, not per device.
 #pragma once
 #include <type_traits>
@@ -61,6 +61,12 @@ inline int persistent_grid(int n_cu, int ctiles, int tiles, int max_g, int test_
 inline bool in_mover_reach(const ConvSrc &s, long long images, int elem_bytes) {
     const long long rs = s.row_stride ? s.row_stride : (long long)s.Ws * s.C;
     return images * s.Hs * rs * elem_bytes < (1LL << 31);
+}
+
+// Linear grid of 256-thread workgroups over `total` items, at most `cap` workgroups (the kernels stride beyond), at least 1.
+inline int lin_grid(size_t total, int cap) {
+    const size_t g = (total + 255) / 256;
+    return (int)(g > (size_t)cap ? cap : (g < 1 ? 1 : g));
 }
 
 // f(std::integral_constant<int, V>{}) for the listed V that equals `value`: only the listed values are instantiated, any other is an error

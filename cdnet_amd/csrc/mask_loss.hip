@@ -2,14 +2,16 @@
 // that switches the weight map, the cross-entropy and the dice term (--weight-map, --alpha 2 / --dice 2, --dice 0), and the pixel
 // metrics of the mask arg-max.  Three launches: per-chunk sums, one finalize block, the gradient.
 //
-// The reduction has the shape of train.hip's loss_reduce_kernel<9> / loss_finalize_kernel (256 threads, pixel i = chunk * 256 + tid,
-// stride nchunk * 256, the 256 per-thread partials summed serially in lane order, the chunks in four chains) and the expressions of
-// loss_grad_kernel's mask part, so with every term on the results equal cdnet_dam_loss_classes' mask terms bit for bit.  The private
+// The reduction has the shape of dam_loss.hip's loss_reduce_kernel<9> / loss_finalize_kernel (256 threads, pixel i = chunk * 256 + tid,
+// stride nchunk * 256, the 256 per-thread partials summed serially in lane order, the chunks in four chains: loss_util.h holds that
+// text once for both) and the expressions of loss_grad_kernel's mask part, so with every term on the results equal
+// cdnet_dam_loss_classes' mask terms bit for bit.  The private
 // sums live in registers here (the DAM kernel keeps them in LDS because its direction sums are indexed by the target class): a sum
 // that class `lab` does not touch adds +0.f, which leaves a non-negative float unchanged.
 //
 // Traffic per pixel: 12 B logits + 1 B label (+ 1 B weight) in each pass, 12 B gradient out: 38-40 B.
-#include "train_util.h"
+#include "loss_util.h"
+#include "launch.h"
 
 using namespace cdnet;
 
@@ -73,11 +75,7 @@ __global__ __launch_bounds__(MS_TPB) void mask_loss_reduce_kernel(MaskIn L, floa
 #pragma unroll
     for (int k = 0; k < MS_SUMS; ++k) acc[k][tid] = s[k];
     __syncthreads();
-    if (tid < MS_SUMS) {
-        float t = 0.f;
-        for (int k = 0; k < MS_TPB; ++k) t += acc[tid][k];
-        partial[((size_t)b * gridDim.x + blockIdx.x) * MS_SUMS + tid] = t;
-    }
+    row_sum<MS_TPB>(acc, tid, b, partial);
 }
 
 // single block: per-sample sums -> the eight reported values and the dice coefficients of the gradient pass
@@ -90,32 +88,12 @@ __global__ __launch_bounds__(256) void mask_loss_finalize_kernel(const float *__
     const int tid = threadIdx.x;
     for (int idx = tid; idx < B * NS; idx += 256) {
         const int b = idx / NS, k = idx % NS;
-        const float *pp = partial + (size_t)b * nchunk * NS + k;
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-        int ch = 0;
-        for (; ch + 3 < nchunk; ch += 4) {
-            s0 += pp[(size_t)ch * NS]; s1 += pp[(size_t)(ch + 1) * NS];
-            s2 += pp[(size_t)(ch + 2) * NS]; s3 += pp[(size_t)(ch + 3) * NS];
-        }
-        for (; ch < nchunk; ++ch) s0 += pp[(size_t)ch * NS];
-        s_sum[idx] = (s0 + s1) + (s2 + s3);
+        s_sum[idx] = chunk_sum<NS>(partial + (size_t)b * nchunk * NS + k, nchunk);
     }
     __syncthreads();
     const float fB = (float)B;
-    for (int b = tid; b < B; b += 256) {
-        const float *S = s_sum + b * NS;
-        float *cf = coef + (size_t)b * MS_COEF;
-        for (int c = 0; c < 3; ++c) {
-            const float I = S[c], U = S[3 + c] + S[6 + c];
-            cf[c] = -2.f / (fB * (U + 1.f));
-            cf[3 + c] = 2.f * (I + 1.f) / (fB * (U + 1.f) * (U + 1.f));
-        }
-    }
-    if (tid < 3) {                        // mean_b 2 (I_c + 1) / (P_c + T_c + 1)
-        float acc = 0.f;
-        for (int b = 0; b < B; ++b) { const float *S = s_sum + b * NS; acc += 2.f * (S[tid] + 1.f) / (S[3 + tid] + S[6 + tid] + 1.f); }
-        s_term[tid] = 1.f - acc / fB;
-    }
+    for (int b = tid; b < B; b += 256) mask_dice_coef(s_sum + b * NS, fB, coef + (size_t)b * MS_COEF);
+    if (tid < 3) s_term[tid] = dice_term<NS>(s_sum, B, fB, tid, 3 + tid, 6 + tid);      // 1 - mean_b 2 (I_c + 1) / (P_c + T_c + 1)
     __syncthreads();
     if (tid == 0) {
         const float n = (float)B * (float)P;
@@ -127,22 +105,8 @@ __global__ __launch_bounds__(256) void mask_loss_finalize_kernel(const float *__
         const bool on_ce = (terms & CDNET_LOSS_CE) != 0, on_dice = (terms & CDNET_LOSS_DICE) != 0;
         losses[0] = on_ce && on_dice ? ce + dice : on_ce ? ce : on_dice ? dice : 0.f;
         losses[1] = ce; losses[2] = dice;
-        // pixel-level metrics, mean over the samples (utils.py:67-110): accuracy, IoU, recall, precision, F1
-        double m[5] = {0, 0, 0, 0, 0};
-        for (int b = 0; b < B; ++b) {
-            const double tp = s_sum[b * NS + 10], fp = s_sum[b * NS + 11], fn = s_sum[b * NS + 12];
-            const double tn = (double)P - tp - fp - fn;
-            const double precision = tp / (tp + fp + 1e-10), recall = tp / (tp + fn + 1e-10);
-            m[0] += (tp + tn) / (tp + fp + tn + fn + 1e-10);
-            m[1] += tp / (tp + fp + fn + 1e-10);
-            m[2] += recall;
-            m[3] += precision;
-            m[4] += 2 * precision * recall / (precision + recall + 1e-10);
-        }
-        for (int k = 0; k < 5; ++k) losses[3 + k] = (float)(m[k] / B);
-        if (*err) {                          // label content out of range: no silent garbage
-            for (int k = 0; k < 8; ++k) losses[k] = __builtin_nanf("");
-        }
+        pixel_metrics<NS>(s_sum, 10, B, P, losses + 3);
+        poison_on_error(err, losses, 8);
     }
 }
 
@@ -182,11 +146,6 @@ __global__ __launch_bounds__(256) void mask_loss_grad_kernel(MaskIn L, const flo
     }
 }
 
-inline int mask_grid(int P) {
-    const int g = cdiv(P, 256);
-    return g > 2048 ? 2048 : g;
-}
-
 }  // namespace
 
 extern "C" size_t cdnet_mask_loss_workspace_floats(int B, int P) {
@@ -213,6 +172,6 @@ extern "C" int cdnet_mask_loss(const float *mask_logits, const uint8_t *label, c
     if (hipMemsetAsync(err, 0, sizeof(int), st) != hipSuccess) return check_launch("cdnet_mask_loss(memset)");
     mask_loss_reduce_kernel<<<dim3(nchunk, B), MS_TPB, 0, st>>>(L, partial, err);
     mask_loss_finalize_kernel<<<1, 256, 0, st>>>(partial, nchunk, B, P, terms, coef, losses, err);
-    if (dmask) mask_loss_grad_kernel<<<dim3(mask_grid(P), B), 256, 0, st>>>(L, coef, dmask);
+    if (dmask) mask_loss_grad_kernel<<<dim3(lin_grid((size_t)P, 2048), B), 256, 0, st>>>(L, coef, dmask);
     return check_launch("cdnet_mask_loss");
 }

@@ -7,6 +7,8 @@
 //     (models/dam/model_unet_rev1.py:8-17, 227-231, 258-263)
 #include <algorithm>
 #include "common.h"
+#include "head_feat.h"
+#include "launch.h"
 #include "xform.h"
 
 using namespace cdnet;
@@ -106,24 +108,8 @@ __global__ __launch_bounds__(256) void bn_finalize_train_kernel(const float *__r
 
 // ------------------------------------------------------------------------------------------------------
 // DAM head.  Each feature F_k = relu(raw*scale + shift + res) is recomputed from its stored pieces
-// (scale==NULL: the tensor already holds the activated feature).
+// (scale==NULL: the tensor already holds the activated feature): HeadFeat and the weight block HeadW are in head_feat.h.
 // ------------------------------------------------------------------------------------------------------
-struct HeadFeat {
-    const unsigned short *raw;
-    const unsigned short *res;
-    const float *scale;
-    const float *shift;
-    int relu;
-    int f16;
-};
-
-struct HeadW {            // 64-channel 1x1 heads, fp32
-    float wp[64], wd[9][64], wm[3][64];
-    float bp, bd[9], bm[3];
-    float a1;             // directionAtt.Conv1x1 (1->1, no bias)
-    float a2[9];          // maskAtt.Conv1x1 (9->1, no bias)
-};
-
 // fp32-stored feature (f16 == 2): NC channels starting at c0, plain fp32 arithmetic (no 16-bit rounding anywhere)
 template <int NC>
 __device__ __forceinline__ void load_feat_f32(const HeadFeat &f, size_t pix, int c0, const float *s_sc, const float *s_sh, float *v) {
@@ -228,8 +214,6 @@ __device__ __forceinline__ void load_feat16(const HeadFeat &f, size_t pix, int q
     feat_from_raw16(f, R, q, s_sc, s_sh, v);
 }
 
-__device__ __forceinline__ float quad_sum(float v) { return xf_quad_sum(v); }        // sum over the 4 lanes of a pixel
-
 // four lanes per pixel, 16 channels each: 4x the parallelism and a quarter of the registers of one-thread-per-pixel.
 // FM: the storage / transform of all three features, decided by the launcher - 1 fp16 raw x scale + shift + residual -> ReLU
 // (training-mode residual-unit outputs of the unfused form), 2 anything (run-time flags; with them the kernel is 9 000 instructions of
@@ -299,14 +283,14 @@ __global__ __launch_bounds__(256, (FM == 2 ? 1 : 4)) void dam_head_fwd_kernel(He
         } else {
             load_feat16(f3, ii, q, s_sc[2], s_sh[2], v);
         }
-        const float pt = quad_sum(xf_dot16(w.wp + q * 16, v)) + w.bp;
+        const float pt = xf_quad_sum(xf_dot16(w.wp + q * 16, v)) + w.bp;
         const float g1 = 1.f + 1.f / (1.f + expf(-(w.a1 * pt)));
         if (all16) conv(f2, R2, 1, v);
         else load_feat16(f2, ii, q, s_sc[1], s_sh[1], v);
         float d[9], q2 = 0.f;
 #pragma unroll
         for (int k = 0; k < 9; ++k) {
-            d[k] = fmaf(g1, quad_sum(xf_dot16(w.wd[k] + q * 16, v)), w.bd[k]);
+            d[k] = fmaf(g1, xf_quad_sum(xf_dot16(w.wd[k] + q * 16, v)), w.bd[k]);
             q2 = fmaf(w.a2[k], d[k], q2);
         }
         const float g2 = 1.f + 1.f / (1.f + expf(-q2));
@@ -315,7 +299,7 @@ __global__ __launch_bounds__(256, (FM == 2 ? 1 : 4)) void dam_head_fwd_kernel(He
         float mk[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            mk[k] = fmaf(g2, quad_sum(xf_dot16(w.wm[k] + q * 16, v)), w.bm[k]);
+            mk[k] = fmaf(g2, xf_quad_sum(xf_dot16(w.wm[k] + q * 16, v)), w.bm[k]);
         }
         if (ok) {
             // the 13 outputs of a pixel are spread over its 4 lanes: lane q writes outputs q, q+4, q+8, (q+12)
@@ -578,11 +562,6 @@ __global__ __launch_bounds__(256) void window_stitch_kernel(const float *__restr
         int kx = x < half_ov ? 0 : (x - half_ov) / stride; kx = kx > nx - 1 ? nx - 1 : kx;
         out[i] = tiles[(((size_t)(ky * nx + kx) * K + k) * th + (y - ky * stride)) * tw + (x - kx * stride)];
     }
-}
-
-inline int lin_grid(size_t total) {
-    size_t g = (total + 255) / 256;
-    return (int)(g > 4096 ? 4096 : (g < 1 ? 1 : g));
 }
 
 
@@ -925,14 +904,14 @@ __global__ __launch_bounds__(256) void grad_sum_kernel(const GradSumArgs A) {
 extern "C" int cdnet_input_pack(const float *x, int N, int C, int H, int W, void *out, void *stream) {
     CDNET_REQUIRE(x && out, "cdnet_input_pack: null pointer");
     CDNET_REQUIRE(N > 0 && C > 0 && C <= 16 && H > 0 && W > 0, "cdnet_input_pack: bad size (C=%d must be <= 16)", C);
-    input_pack_kernel<<<lin_grid((size_t)N * H * W), 256, 0, (hipStream_t)stream>>>(x, N, C, H * W, (unsigned short *)out);
+    input_pack_kernel<<<lin_grid((size_t)N * H * W, 4096), 256, 0, (hipStream_t)stream>>>(x, N, C, H * W, (unsigned short *)out);
     return check_launch("cdnet_input_pack");
 }
 
 extern "C" int cdnet_input_pack_f32(const float *x, int N, int C, int H, int W, float *out, void *stream) {
     CDNET_REQUIRE(x && out, "cdnet_input_pack_f32: null pointer");
     CDNET_REQUIRE(N > 0 && C > 0 && C <= 16 && H > 0 && W > 0, "cdnet_input_pack_f32: bad size (C=%d must be <= 16)", C);
-    input_pack_f32_kernel<<<lin_grid((size_t)N * H * W), 256, 0, (hipStream_t)stream>>>(x, N, C, H * W, out);
+    input_pack_f32_kernel<<<lin_grid((size_t)N * H * W, 4096), 256, 0, (hipStream_t)stream>>>(x, N, C, H * W, out);
     return check_launch("cdnet_input_pack_f32");
 }
 
@@ -955,22 +934,15 @@ extern "C" int cdnet_bn_finalize_train(const float *stats, int T, int C, float c
     return check_launch("cdnet_bn_finalize_train");
 }
 
-static HeadFeat mk_feat(const cdnet_head_feat &f) {
-    HeadFeat h;
-    h.raw = f.raw; h.res = f.res; h.scale = f.scale; h.shift = f.shift; h.relu = f.relu; h.f16 = f.f16;
-    return h;
-}
-
 extern "C" int cdnet_dam_head_forward(const cdnet_head_feat *f1, const cdnet_head_feat *f2, const cdnet_head_feat *f3,
                                       const float *head_weights, int N, int H, int W, float *mask, float *point,
                                       float *direction, void *stream) {
     CDNET_REQUIRE(f1 && f2 && f3 && head_weights && mask && point && direction, "cdnet_dam_head_forward: null pointer");
     CDNET_REQUIRE(f1->raw && f2->raw && N > 0 && H > 0 && W > 0, "cdnet_dam_head_forward: bad args");
-    static_assert(sizeof(HeadW) == CDNET_HEAD_WEIGHT_FLOATS * 4, "head weight block layout");
-    const HeadFeat a = mk_feat(*f1), b = mk_feat(*f2), c = mk_feat(*f3);
+    const HeadFeat a = mk_hf(*f1), b = mk_hf(*f2), c = mk_hf(*f3);
     auto plain = [](const HeadFeat &f) { return f.f16 == 0 && !f.scale && !f.relu && !f.res; };
     auto train = [](const HeadFeat &f) { return f.f16 == 1 && f.scale && f.relu && f.res; };
-    const int grid = lin_grid((size_t)N * H * W * 4);
+    const int grid = lin_grid((size_t)N * H * W * 4, 4096);
     const HeadW *hw = reinterpret_cast<const HeadW *>(head_weights);
     // plain stored features (eval mode, the fused training forward): the matrix-core kernel
     const size_t total = (size_t)N * H * W;
@@ -1000,7 +972,7 @@ extern "C" int cdnet_final_conv1x1(const cdnet_head_feat *f, const float *w, con
                                    float *out, void *stream) {
     CDNET_REQUIRE(f && f->raw && w && b && out, "cdnet_final_conv1x1: null pointer");
     CDNET_REQUIRE(K >= 1 && K <= 32 && N > 0 && H > 0 && W > 0, "cdnet_final_conv1x1: K=%d must be in [1,32]", K);
-    final_conv1x1_kernel<<<lin_grid((size_t)N * H * W), 256, 0, (hipStream_t)stream>>>(mk_feat(*f), w, b, K, N, H * W, out);
+    final_conv1x1_kernel<<<lin_grid((size_t)N * H * W, 4096), 256, 0, (hipStream_t)stream>>>(mk_hf(*f), w, b, K, N, H * W, out);
     return check_launch("cdnet_final_conv1x1");
 }
 
@@ -1009,7 +981,7 @@ extern "C" int cdnet_window_pack(const float *img, int C, int H, int W, int view
     CDNET_REQUIRE(img && out_bf16_nhwc16, "cdnet_window_pack: null pointer");
     CDNET_REQUIRE(C > 0 && C <= 16 && H > 0 && W > 0 && tile_h > 0 && tile_w > 0 && stride > 0 && ny > 0 && nx > 0 &&
                   view_xform >= 0 && view_xform < 8, "cdnet_window_pack: bad arguments");
-    window_pack_kernel<<<lin_grid((size_t)ny * nx * tile_h * tile_w), 256, 0, (hipStream_t)stream>>>(
+    window_pack_kernel<<<lin_grid((size_t)ny * nx * tile_h * tile_w, 4096), 256, 0, (hipStream_t)stream>>>(
         img, C, H, W, view_xform, tile_h, tile_w, stride, ny, nx, (unsigned short *)out_bf16_nhwc16);
     return check_launch("cdnet_window_pack");
 }
@@ -1019,7 +991,7 @@ extern "C" int cdnet_window_pack_f32(const float *img, int C, int H, int W, int 
     CDNET_REQUIRE(img && out_f32_nhwc16, "cdnet_window_pack_f32: null pointer");
     CDNET_REQUIRE(C > 0 && C <= 16 && H > 0 && W > 0 && tile_h > 0 && tile_w > 0 && stride > 0 && ny > 0 && nx > 0 &&
                   view_xform >= 0 && view_xform < 8, "cdnet_window_pack_f32: bad arguments");
-    window_pack_f32_kernel<<<lin_grid((size_t)ny * nx * tile_h * tile_w), 256, 0, (hipStream_t)stream>>>(
+    window_pack_f32_kernel<<<lin_grid((size_t)ny * nx * tile_h * tile_w, 4096), 256, 0, (hipStream_t)stream>>>(
         img, C, H, W, view_xform, tile_h, tile_w, stride, ny, nx, out_f32_nhwc16);
     return check_launch("cdnet_window_pack_f32");
 }
@@ -1030,7 +1002,7 @@ extern "C" int cdnet_window_stitch(const float *tiles, int K, int tile_h, int ti
     CDNET_REQUIRE(K > 0 && tile_h > 0 && tile_w > 0 && stride > 0 && ny > 0 && nx > 0 && Hv > 0 && Wv > 0 && overlap >= 0,
                   "cdnet_window_stitch: bad arguments");
     CDNET_REQUIRE((ny - 1) * stride + tile_h >= Hv && (nx - 1) * stride + tile_w >= Wv, "cdnet_window_stitch: windows do not cover the view");
-    window_stitch_kernel<<<lin_grid((size_t)K * Hv * Wv), 256, 0, (hipStream_t)stream>>>(tiles, K, tile_h, tile_w, stride, overlap / 2,
+    window_stitch_kernel<<<lin_grid((size_t)K * Hv * Wv, 4096), 256, 0, (hipStream_t)stream>>>(tiles, K, tile_h, tile_w, stride, overlap / 2,
                                                                                          ny, nx, Hv, Wv, out);
     return check_launch("cdnet_window_stitch");
 }
@@ -1055,7 +1027,7 @@ static int fuse_sum_impl(const cdnet_fuse_term *terms, int nterm, int N, int H, 
     A.out_cstride = out_cstride ? out_cstride : C; A.out_coff = out_coff;
     CDNET_REQUIRE(A.out_cstride % 8 == 0 && out_coff % 8 == 0 && out_coff + C <= A.out_cstride, "cdnet_fuse_sum: output channel slice");
     const size_t total = (size_t)N * H * W * (C / 8);
-    const int grid = lin_grid(total);
+    const int grid = lin_grid(total, 4096);
     CDNET_REQUIRE(f32 || total < (1ull << 31), "cdnet_fuse_sum: more than 2^31 output vectors (the 16-bit kernels index in 32 bits)");
     if (f32) fuse_sum_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(A);
     else {
@@ -1088,8 +1060,8 @@ static int upsample_bwd_impl(const void *dout, int N, int H, int W, int C, int d
                   "cdnet_upsample_bilinear_backward: (2 Hs + 1) H does not fit 32 bits");
     const unsigned short *d = reinterpret_cast<const unsigned short *>(dout);
     unsigned short *o = reinterpret_cast<unsigned short *>(din);
-    if (f32) upsample_bwd_kernel<true><<<lin_grid((size_t)N * Hs * Ws * (C / 8)), 256, 0, (hipStream_t)stream>>>(d, N, H, W, C, cs, dout_coff, Hs, Ws, o);
-    else upsample_bwd_kernel<false><<<lin_grid((size_t)N * Hs * Ws * (C / 8)), 256, 0, (hipStream_t)stream>>>(d, N, H, W, C, cs, dout_coff, Hs, Ws, o);
+    if (f32) upsample_bwd_kernel<true><<<lin_grid((size_t)N * Hs * Ws * (C / 8), 4096), 256, 0, (hipStream_t)stream>>>(d, N, H, W, C, cs, dout_coff, Hs, Ws, o);
+    else upsample_bwd_kernel<false><<<lin_grid((size_t)N * Hs * Ws * (C / 8), 4096), 256, 0, (hipStream_t)stream>>>(d, N, H, W, C, cs, dout_coff, Hs, Ws, o);
     return check_launch("cdnet_upsample_bilinear_backward");
 }
 
@@ -1105,13 +1077,13 @@ extern "C" int cdnet_upsample_bilinear_backward_f32(const float *dout, int N, in
 
 extern "C" int cdnet_s2d_to_nhwc(const uint16_t *in, int N, int H2, int W2, int C, uint16_t *out, void *stream) {
     CDNET_REQUIRE(in && out && N > 0 && H2 > 0 && W2 > 0 && C % 8 == 0 && C >= 8, "cdnet_s2d_to_nhwc: bad args");
-    s2d_to_nhwc_kernel<unsigned short><<<lin_grid((size_t)N * H2 * W2 * 4 * (C / 8)), 256, 0, (hipStream_t)stream>>>(in, N, H2, W2, C, out);
+    s2d_to_nhwc_kernel<unsigned short><<<lin_grid((size_t)N * H2 * W2 * 4 * (C / 8), 4096), 256, 0, (hipStream_t)stream>>>(in, N, H2, W2, C, out);
     return check_launch("cdnet_s2d_to_nhwc");
 }
 
 extern "C" int cdnet_s2d_to_nhwc_f32(const float *in, int N, int H2, int W2, int C, float *out, void *stream) {
     CDNET_REQUIRE(in && out && N > 0 && H2 > 0 && W2 > 0 && C % 4 == 0 && C >= 4, "cdnet_s2d_to_nhwc_f32: bad args");
-    s2d_to_nhwc_kernel<float><<<lin_grid((size_t)N * H2 * W2 * 4 * (C / 4)), 256, 0, (hipStream_t)stream>>>(
+    s2d_to_nhwc_kernel<float><<<lin_grid((size_t)N * H2 * W2 * 4 * (C / 4), 4096), 256, 0, (hipStream_t)stream>>>(
         reinterpret_cast<const unsigned short *>(in), N, H2, W2, C, reinterpret_cast<unsigned short *>(out));
     return check_launch("cdnet_s2d_to_nhwc_f32");
 }
@@ -1134,7 +1106,7 @@ static int grad_sum_impl(const cdnet_grad_term *terms, int nterm, const uint16_t
         CDNET_REQUIRE(A.g[k] && A.cstride[k] % 8 == 0 && A.coff[k] % 8 == 0 && A.coff[k] + C <= A.cstride[k], "cdnet_grad_sum: channel slice");
     }
     A.nterm = nterm; A.mask = mask; A.npix = (size_t)npix; A.C = C; A.out = out;
-    if (f32) grad_sum_kernel<true><<<lin_grid((size_t)npix * (C / 8)), 256, 0, (hipStream_t)stream>>>(A);
-    else grad_sum_kernel<false><<<lin_grid((size_t)npix * (C / 8)), 256, 0, (hipStream_t)stream>>>(A);
+    if (f32) grad_sum_kernel<true><<<lin_grid((size_t)npix * (C / 8), 4096), 256, 0, (hipStream_t)stream>>>(A);
+    else grad_sum_kernel<false><<<lin_grid((size_t)npix * (C / 8), 4096), 256, 0, (hipStream_t)stream>>>(A);
     return check_launch("cdnet_grad_sum");
 }

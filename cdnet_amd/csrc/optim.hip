@@ -1,11 +1,13 @@
-// The reference's other optimisers on flat fp32 buffers (utils.py:907-939): RAdam, RAdam_4step, AdamW with warm-up
+// The optimisers on flat fp32 buffers (utils.py:907-939): the default Adam (adam_kernel: optimizer.step() of train_util_dam.py:308
+// with utils.py:915-918), and the reference's other ones: RAdam, RAdam_4step, AdamW with warm-up
 // (hhl_utils/radam.py:6-252), Ranger = RAdam + lookahead (hhl_utils/ranger.py:26-165) and torch.optim.SGD with momentum.
-// Two streaming kernels: moment_kernel (the four moment rules) and sgd_kernel.  Every step-dependent coefficient is a host
+// Two streaming kernels for the latter: moment_kernel (the four moment rules) and sgd_kernel.  Every step-dependent coefficient is a host
 // scalar (cdnet_amd/optim.py computes them in double like the reference's math.sqrt / ** and hands them over as float);
 // the kernels branch on host scalars only.  16-byte loads and stores on the aligned body, scalar head and tail: a slice
 // [a, b) of the flat buffers (bucket-wise stepping behind the all-reduce) starts at any 4-byte boundary.
 // The operation order is the reference's (mul_ / addcmul_ / add_ / addcdiv_), no contraction (-ffp-contract=off).
 #include "common.h"
+#include "launch.h"
 #include <math.h>
 
 namespace {
@@ -120,9 +122,26 @@ bool aligned4(const void *const *ptrs, int count) {
     return true;
 }
 
-int stream_grid(size_t nvec) {
-    const size_t g = (nvec + 255) / 256;
-    return (int)(g > 2048 ? 2048 : (g < 1 ? 1 : g));              // 256 CUs x 8 workgroups, grid-stride beyond
+constexpr int STREAM_GRID_CAP = 2048;      // moment_kernel, sgd_kernel: 256 CUs x 8 workgroups, grid-stride beyond
+
+// ======================================================================================================
+// Adam (torch.optim.Adam semantics: L2 weight decay folded into the gradient, bias correction)
+// ======================================================================================================
+__global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
+                                                   float *__restrict__ v, size_t n, float lr, float b1, float b2, float eps,
+                                                   float wd, float bc1, float bc2_sqrt, float gscale) {
+    const float step = lr / bc1;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        float gi = g[i] * gscale;
+        const float pi = p[i];
+        gi = fmaf(wd, pi, gi);
+        float mi = m[i], vi = v[i];
+        mi = mi + (gi - mi) * (1.f - b1);
+        vi = vi * b2 + (1.f - b2) * gi * gi;
+        m[i] = mi; v[i] = vi;
+        const float denom = sqrtf(vi) / bc2_sqrt + eps;
+        p[i] = pi - step * (mi / denom);
+    }
 }
 
 }  // namespace
@@ -147,7 +166,7 @@ extern "C" int cdnet_moment_step(float *param, const float *grad, float *exp_avg
     c.gscale = grad_scale; c.ndecay = -decay; c.nstep = -step_size; c.vdiv = v_div; c.eps = eps; c.alpha = alpha;
     c.move = move; c.rect = rect; c.sync = sync;
     const size_t head = scalar_head(n, ptrs, np), nvec = (n - head) / 4;
-    moment_kernel<<<stream_grid(nvec), 256, 0, (hipStream_t)stream>>>(param, grad, exp_avg, exp_avg_sq, sync ? slow : nullptr, n, head,
+    moment_kernel<<<lin_grid(nvec, STREAM_GRID_CAP), 256, 0, (hipStream_t)stream>>>(param, grad, exp_avg, exp_avg_sq, sync ? slow : nullptr, n, head,
                                                                       nvec, c);
     return check_launch("cdnet_moment_step");
 }
@@ -165,6 +184,17 @@ extern "C" int cdnet_sgd_step(float *param, const float *grad, float *momentum_b
     SgdCoef c;
     c.gscale = grad_scale; c.wd = weight_decay; c.momentum = momentum; c.nlr = -lr; c.first = step == 1;
     const size_t head = scalar_head(n, ptrs, 3), nvec = (n - head) / 4;
-    sgd_kernel<<<stream_grid(nvec), 256, 0, (hipStream_t)stream>>>(param, grad, momentum_buffer, n, head, nvec, c);
+    sgd_kernel<<<lin_grid(nvec, STREAM_GRID_CAP), 256, 0, (hipStream_t)stream>>>(param, grad, momentum_buffer, n, head, nvec, c);
     return check_launch("cdnet_sgd_step");
+}
+
+extern "C" int cdnet_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, size_t n, float lr, float beta1,
+                               float beta2, float eps, float weight_decay, int step, float grad_scale, void *stream) {
+    CDNET_REQUIRE(param && grad && exp_avg && exp_avg_sq && step >= 1, "cdnet_adam_step: bad args");
+    if (n == 0) return CDNET_OK;
+    const double bc1 = 1.0 - pow((double)beta1, (double)step);
+    const double bc2 = 1.0 - pow((double)beta2, (double)step);
+    adam_kernel<<<lin_grid(n, 4096), 256, 0, (hipStream_t)stream>>>(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps,
+                                                                    weight_decay, (float)bc1, (float)sqrt(bc2), grad_scale);
+    return check_launch("cdnet_adam_step");
 }

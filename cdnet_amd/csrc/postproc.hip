@@ -8,6 +8,7 @@
 // the CPU oracle (tests/test_gpu_postproc.py).
 #include "common.h"
 #include "cc_forest.h"
+#include "launch.h"
 
 using namespace cdnet;
 
@@ -699,8 +700,6 @@ __global__ __launch_bounds__(256) void dilate_disk_kernel(const int32_t *__restr
     out[(size_t)n * H * W + (size_t)y * W + x] = v;
 }
 
-inline int grid_lin(int plane) { int g = cdiv(plane, 256); return g > 2048 ? 2048 : (g < 1 ? 1 : g); }
-
 }  // namespace
 
 // internal (not part of the C ABI): 8-connected components of a binary mask with skimage.measure.label numbering.
@@ -714,7 +713,7 @@ int label8_raster(const uint8_t *mask, int N, int H, int W, int *L, int *aux, in
     }
     const int plane = H * W, nchunk = cdiv(plane, CHUNK);
     const dim3 gr = grid_rows(N, H, W), br(64, 4);
-    const dim3 gl(grid_lin(plane), N);
+    const dim3 gl(lin_grid(plane, 2048), N);
     cc_init_kernel<1><<<gr, br, 0, st>>>(mask, 0, H, W, L);
     cc_merge_kernel<1, 8><<<gr, br, 0, st>>>(mask, 0, H, W, L);
     cc_flatten_kernel<FLAT_PLAIN><<<gr, br, 0, st>>>(H, W, L, nullptr);
@@ -756,7 +755,7 @@ extern "C" int cdnet_ddm_normalize(const uint8_t *code, const int32_t *minmax, i
                                    void *stream) {
     CDNET_REQUIRE(code && minmax && out, "cdnet_ddm_normalize: null pointer");
     CDNET_REQUIRE(N > 0 && H > 0 && W > 0, "cdnet_ddm_normalize: bad size");
-    ddm_normalize_kernel<<<dim3(grid_lin(H * W), N), 256, 0, (hipStream_t)stream>>>(code, minmax, H * W, out);
+    ddm_normalize_kernel<<<dim3(lin_grid(H * W, 2048), N), 256, 0, (hipStream_t)stream>>>(code, minmax, H * W, out);
     return check_launch("cdnet_ddm_normalize");
 }
 
@@ -765,7 +764,7 @@ extern "C" int cdnet_probmaps(const float *mask_logits, const float *dir_logits,
     CDNET_REQUIRE(mask_logits && dir_logits && prob && dcm, "cdnet_probmaps: null pointer");
     CDNET_REQUIRE(N > 0 && H > 0 && W > 0, "cdnet_probmaps: bad size");
     hipStream_t st = (hipStream_t)stream;
-    dim3 grid(grid_lin(H * W), N);
+    dim3 grid(lin_grid(H * W, 2048), N);
     if (C == 9) probmaps_kernel<9><<<grid, 256, 0, st>>>(mask_logits, dir_logits, H * W, prob, dcm);
     else if (C == 5) probmaps_kernel<5><<<grid, 256, 0, st>>>(mask_logits, dir_logits, H * W, prob, dcm);
     else if (C == 17) probmaps_kernel<17><<<grid, 256, 0, st>>>(mask_logits, dir_logits, H * W, prob, dcm);
@@ -873,7 +872,7 @@ extern "C" int cdnet_cc_chain(const uint8_t *pred, int fg_value, int N, int H, i
     uint8_t *B = small ? small : (uint8_t *)(ws + oB);
     const int plane = H * W, nchunk = cdiv(plane, CHUNK);
     const dim3 gr = grid_rows(N, H, W), br(64, 4);
-    const dim3 gl(grid_lin(plane), N);
+    const dim3 gl(lin_grid(plane, 2048), N);
 
     // 1. fill holes: 4-connected components of the background; those touching the border stay background
     cc_init_kernel<0><<<gr, br, 0, st>>>(pred, fg_value, H, W, L);
@@ -1127,7 +1126,7 @@ extern "C" int cdnet_watershed_process(const uint8_t *pred, int N, int H, int W,
     const int plane = H * W, nchunk = cdiv(plane, CHUNK);
     const size_t P = (size_t)N * plane;
     const dim3 gr = grid_rows(N, H, W), br(64, 4);
-    const dim3 gl(grid_lin(plane), N);
+    const dim3 gl(lin_grid(plane, 2048), N);
     int32_t *marker = marker_out ? marker_out : (int32_t *)L2;
 
     // 1. components of the prediction (measurements.label, 4-connected), exact EDT per component, scaled distance map
@@ -1180,7 +1179,7 @@ extern "C" int cdnet_fill_label_process(const uint8_t *pred, int N, int H, int W
     const int plane = H * W, nchunk = cdiv(plane, CHUNK);
     const size_t P = (size_t)N * plane;
     const dim3 gr = grid_rows(N, H, W), br(64, 4);
-    const dim3 gl(grid_lin(plane), N);
+    const dim3 gl(lin_grid(plane, 2048), N);
     ws_binarize_kernel<<<gl, 256, 0, st>>>(pred, plane, m);                           // non-zero -> 1
     // fill holes: 4-connected components of the background, those touching the border stay background
     cc_init_kernel<0><<<gr, br, 0, st>>>(m, 1, H, W, L2);

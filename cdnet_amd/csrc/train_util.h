@@ -1,4 +1,4 @@
-// Device helpers shared by the training-only streaming kernels (train.hip, bn_bwd.hip): fp32 8-channel loads / stores, the
+// Device helpers shared by the backward streaming kernels (head_bwd.hip, bn_bwd.hip): fp32 8-channel loads / stores, the
 // threads-per-pixel block layout and the fixed-order sum of per-block partial rows.  The 16-bit formats come from stage16.h.
 #pragma once
 #include "common.h"
@@ -33,23 +33,6 @@ static __global__ __launch_bounds__(256) void reduce_partials_kernel(const float
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
     if (lane == 0) out[k] = s;
-}
-
-// softmax and log-softmax of the three mask logits (train.hip's loss kernels and mask_loss.hip: one text, so both compute the same bits)
-__device__ __forceinline__ void softmax3(const float *l, float *p, float *logp) {
-    const float m = fmaxf(l[0], fmaxf(l[1], l[2]));
-    float e[3], s = 0.f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { e[c] = expf(l[c] - m); s += e[c]; }
-    const float ls = logf(s);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { p[c] = e[c] / s; logp[c] = l[c] - m - ls; }
-}
-
-// chunks (workgroups) per sample of the loss reductions: 8 pixels per thread, at most 64 chunks - beyond that the threads loop
-static int loss_nchunk(int P, int tpb) {
-    int nchunk = cdiv(P, tpb * 8);
-    return nchunk > 64 ? 64 : nchunk;
 }
 
 }  // namespace cdnet

@@ -1,7 +1,7 @@
 """Host side of the reference's optimisers and learning-rate schedulers (utils.py:907-977).
 
   FlatState                           the flat fp32 buffers of a trainer: parameters, gradients, the optimiser's state
-  stepper(tr, grad_scale)             step(a, b) of the trainer's rule over a range of the flat buffers: cdnet_adam_step (csrc/train.hip),
+  stepper(tr, grad_scale)             step(a, b) of the trainer's rule over a range of the flat buffers: cdnet_adam_step (csrc/optim.hip),
                                       cdnet_sgd_step / cdnet_moment_step (csrc/optim.hip)
   state_dict / load_state_dict        the optimiser entry of a checkpoint in the layout of the reference's object for the rule
   moment_scalars(rule, t, lr, wd)     the host scalars of step t of 'radam' / 'radam4s' / 'adamw' / 'ranger', computed in
@@ -98,7 +98,7 @@ def sgd_step_host(p, g, buf, t, lr, momentum, wd, grad_scale=1.0):
     p[:] = p + f(-lr) * buf
 
 
-# the order of cdnet_dam_head_backward's weight block (csrc/train.hip), which FlatState puts first
+# the order of cdnet_dam_head_backward's weight block (csrc/head_bwd.hip), which FlatState puts first
 HEAD_PARAMS = ['point_conv.weight', 'direction_conv.weight', 'mask_conv.weight', 'point_conv.bias',
                'direction_conv.bias', 'mask_conv.bias', 'directionAtt.Conv1x1.weight', 'maskAtt.Conv1x1.weight']
 

@@ -243,7 +243,7 @@ def bias_blocks(npix, Cc):
 
 
 def bias_depth(npix, Cc):
-    """longest chain of fp32 additions of the scheme train.hip documents: a thread of the nb <= 512 workgroups adds its
+    """longest chain of fp32 additions of the scheme head_bwd.hip documents: a thread of the nb <= 512 workgroups adds its
     ceil(npix / (nb * ppb)) pixels one after the other (ppb = 256 / (C / 8) pixels per workgroup and trip), one thread per channel adds
     the workgroup's ceil(256 / (C / 8)) per-thread sums in order, the reduction of the nb partial rows adds ceil(nb / 64) per lane and
     then takes the 6 steps of a 64-lane butterfly.  Each addition rounds a partial sum of the column, bounded by sum_p |g[p, c]|."""

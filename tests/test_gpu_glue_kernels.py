@@ -1,5 +1,5 @@
 """Kernel-level tests of the streaming "glue" kernels of HRNet training (csrc/model.hip: cdnet_fuse_sum, cdnet_upsample_bilinear_backward,
-cdnet_s2d_to_nhwc, cdnet_grad_sum, each with its _f32 twin) and of the UNet bias gradient (csrc/train.hip: cdnet_bias_grad[_f32]) through
+cdnet_s2d_to_nhwc, cdnet_grad_sum, each with its _f32 twin) and of the UNet bias gradient (csrc/head_bwd.hip: cdnet_bias_grad[_f32]) through
 the C ABI, against fp64 references built on the CPU.  Inputs, references and the derivation of every bound: tests/_glue_cases.py.
 
 Exact-input cases (small integers, dyadic scales and weights) demand equality; real-input cases a per-element bound counted from the

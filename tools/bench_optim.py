@@ -1,4 +1,4 @@
-"""Rate of the optimiser kernels (csrc/optim.hip: moment_kernel, sgd_kernel) beside adam_kernel (csrc/train.hip), one process, one box.
+"""Rate of the optimiser kernels (csrc/optim.hip: moment_kernel, sgd_kernel, adam_kernel), one process, one box.
 
     python tools/bench_optim.py [--n 20470000] [--launches 40] [--warmup 10] [--offset 0]
 
