@@ -43,6 +43,13 @@ SIGNATURES = {
     'cdnet_grad_sum_f32': (_i, [_vp, _i, _vp, C.c_longlong, _i, _vp, _vp]),
     'cdnet_label_pair_histogram': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     'cdnet_remap_label': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'cdnet_label_areas': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    'cdnet_label_apply': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    'cdnet_label_csr_workspace_bytes': (_sz, [_i]),
+    'cdnet_label_csr': (_i, [_vp, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    'cdnet_hausdorff_tile_pixels': (_i, []),
+    'cdnet_hausdorff_chunk_pixels': (_i, []),
+    'cdnet_hausdorff_pairs': (_i, [_vp] * 8 + [_i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp]),
     'cdnet_watershed_workspace_bytes': (_sz, [_i, _i, _i]),
     'cdnet_watershed_process': (_i, [_vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
     'cdnet_fill_label_process': (_i, [_vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),

@@ -278,15 +278,34 @@ def measure_label(a):
     return lut[lab].astype(np.int32)
 
 
-def nuclei_accuracy_object_level(pred, gt):
+def object_hausdorff_host(true, pred, pairs):
+    """float64 [M, 2]: (h(P -> T), h(T -> P)) of every pair (true id, pred id) with scipy's directed_hausdorff on np.argwhere of the two
+    objects - the calls the reference makes per matched object (utils.py:6, :303), O(pixels) each.  The host path: what
+    stats_utils.object_hausdorff is compared with, and what it falls back to for pairs beyond its work bound."""
+    from scipy.spatial.distance import directed_hausdorff
+    out = np.zeros((len(pairs), 2), np.float64)
+    for m, (ti, pi) in enumerate(np.asarray(pairs).reshape(-1, 2)):
+        seg_ind, gt_ind = np.argwhere(pred == pi), np.argwhere(true == ti)
+        out[m] = directed_hausdorff(seg_ind, gt_ind)[0], directed_hausdorff(gt_ind, seg_ind)[0]
+    return out
+
+
+def nuclei_accuracy_object_level_host(pred, gt):
+    """nuclei_accuracy_object_level with the Hausdorff distances from object_hausdorff_host: one scipy call pair per matched object"""
+    return nuclei_accuracy_object_level(pred, gt, hausdorff=lambda g, p, pairs: object_hausdorff_host(g, p, pairs).max(1))
+
+
+def nuclei_accuracy_object_level(pred, gt, hausdorff=None):
     """(recall, precision, F1, dice, iou, haus, AJI) of utils.nuclei_accuracy_object_level (utils.py:245-330): ground-truth objects in
     id order, each greedily paired with the not-yet-used predicted object of largest IoU (first maximum in id order), used objects
     removed (:312).  The pixel pass (areas + sparse pairwise intersections) runs on the device (`stats_utils.pair_table`); the
-    per-pair arithmetic is the reference's float arithmetic; the Hausdorff distance of a matched pair is scipy's
-    directed_hausdorff on both sides, exactly the call the reference makes (:6, :303).
+    per-pair arithmetic is the reference's float arithmetic; the Hausdorff distances of all matched pairs come from one
+    `stats_utils.object_hausdorff` call (exact integer squared distances on the device, sqrt in float64: the bits of scipy's
+    directed_hausdorff on both sides, the call the reference makes, :6, :303) and are summed in the reference's order.
+    `hausdorff(gt_labels, pred_labels, pairs [M, 2] of (gt id, pred id)) -> float64 [M]` replaces that call (see
+    nuclei_accuracy_object_level_host).
     pred / gt: integer label or binary images; both are re-labelled like the reference does with skimage.measure.label (8-connected
     regions of equal value, raster-order ids)."""
-    from scipy.spatial.distance import directed_hausdorff
     from . import stats_utils
 
     p, g = measure_label(pred), measure_label(gt)
@@ -295,7 +314,7 @@ def nuclei_accuracy_object_level(pred, gt):
     by_gt = {}
     for ti, pi, inter in pairs:
         by_gt.setdefault(int(ti), []).append((int(pi), float(inter)))
-    used = set()
+    used, matched = set(), []
     TP = FN = 0.0
     dice = iou = haus = C = U = count = 0.0
     for i in range(1, Ng + 1):
@@ -314,11 +333,15 @@ def nuclei_accuracy_object_level(pred, gt):
         a_p, a_g = float(ap[best]), float(ag[i])
         dice += 2 * overlap_area / (a_p + a_g)
         iou += overlap_area / (a_p + a_g - overlap_area)
-        seg_ind, gt_ind = np.argwhere(p == best), np.argwhere(g == i)
-        haus += max(directed_hausdorff(seg_ind, gt_ind)[0], directed_hausdorff(gt_ind, seg_ind)[0])
+        matched.append((i, best))
         C += overlap_area
         U += a_p + a_g - overlap_area
         used.add(best)
+    if matched:
+        if hausdorff is None:                                   # (the device packs a coordinate into 15 bits)
+            hausdorff = stats_utils.object_hausdorff if max(g.shape) <= 32767 else (lambda a, b, m: object_hausdorff_host(a, b, m).max(1))
+        for h in hausdorff(g, p, np.array(matched, dtype=np.int64)):
+            haus += float(h)
     FP = Ns - TP
     recall = TP / (TP + FN + 1e-10)
     precision = TP / (TP + FP + 1e-10)

@@ -810,6 +810,37 @@ int cdnet_label_pair_histogram(const int32_t *true_lab, const int32_t *pred_lab,
                                int32_t *area_true, int32_t *area_pred, uint32_t *hash_keys, int32_t *hash_counts, int32_t *err_flag,
                                void *stream);
 int cdnet_remap_label(const int32_t *lab, int N, int plane, int cap, int32_t *scratch, int32_t *out, int32_t *err_flag, void *stream);
+/* remap_label by_size = True in two halves: cdnet_label_areas counts the pixels of every id (area[N][cap]; err_flag 1 = id outside
+ * [0, cap)), the host orders the ids, cdnet_label_apply writes out = lut[N][cap][lab] (ids outside (0, cap) -> 0). */
+int cdnet_label_areas(const int32_t *lab, int N, int plane, int cap, int32_t *area, int32_t *err_flag, void *stream);
+int cdnet_label_apply(const int32_t *lab, int N, int plane, int cap, const int32_t *lut, int32_t *out, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Object-level Hausdorff distances (utils.py:303: scipy's directed_hausdorff both ways between the pixel sets of a true and a predicted
+ * object), exact: integer squared distances, minima and maxima only.
+ *
+ * cdnet_label_csr, once per label image [H][W] i32 (H, W <= 32767, ids < cap <= 65536): tab[4][cap] = pixels per id, boundary pixels per
+ * id, start of the id's segment in pix, start of its segment in bpix; pix[H * W] = the coordinates (y << 16 | x) of all labelled pixels
+ * grouped by id, bpix[H * W] = the same for boundary pixels only (on the image edge, or a 4-neighbour carries another id).  The order
+ * inside a segment is arbitrary.  workspace: cdnet_label_csr_workspace_bytes(cap).  err_flag 1 = id outside [0, cap).  Four launches.
+ *
+ * cdnet_hausdorff_pairs, one launch for all pairs: pairs[M][2] = (true id, pred id); items[n_items][2] = (2 * pair + direction, tile),
+ * one per cdnet_hausdorff_tile_pixels() pixels of the direction's source object A (direction 0: A = the predicted object, 1: the true
+ * one), written by the caller from tab's counts - so the caller also decides which pairs run here.  d2[M][2] = (h(P -> T)^2,
+ * h(T -> P)^2), h(A -> B) = max over a in A of min over b in B of |a - b|; pairs without items keep 0.  Objects may be of any size: a
+ * block holds one tile of A in registers and streams B's boundary through LDS cdnet_hausdorff_chunk_pixels() at a time.  The work is
+ * about |A \ B| x |boundary of B| distance evaluations per item set, which the caller should bound.  err_flag: 1 = pair id outside
+ * (0, cap), 3 = an item out of range or an id without pixels.
+ * ---------------------------------------------------------------------------------------------------- */
+size_t cdnet_label_csr_workspace_bytes(int cap);
+int cdnet_label_csr(const int32_t *lab, int H, int W, int cap, void *workspace, size_t workspace_bytes, int32_t *tab, int32_t *pix,
+                    int32_t *bpix, int32_t *err_flag, void *stream);
+int cdnet_hausdorff_tile_pixels(void);
+int cdnet_hausdorff_chunk_pixels(void);
+int cdnet_hausdorff_pairs(const int32_t *true_lab, const int32_t *true_tab, const int32_t *true_pix, const int32_t *true_bpix,
+                          const int32_t *pred_lab, const int32_t *pred_tab, const int32_t *pred_pix, const int32_t *pred_bpix, int H, int W,
+                          int cap, const int32_t *pairs, int M, const int32_t *items, int n_items, int32_t *d2, int32_t *err_flag,
+                          void *stream);
 
 #ifdef __cplusplus
 }
