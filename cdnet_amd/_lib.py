@@ -121,6 +121,8 @@ SIGNATURES = {
     'cdnet_augment_geo_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'cdnet_augment_batch_geo': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     'cdnet_label_encoding': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'cdnet_weight_map_radius': (_i, [C.c_double, C.c_double]),
+    'cdnet_weight_map': (_i, [_vp, _i, _i, C.c_double, C.c_double, _vp, _vp]),
 }
 
 _lib = None

@@ -59,6 +59,28 @@ def _dataset_layout(opt, x, logger=None):
     return [img, wmap, pick[0]], pick[1]
 
 
+def _prepare_weight_maps(dir_list, post_fix, make, rank, world, dev, logger):
+    """the weight maps of one split before its DataFolder is built.  `make` (--make-weight-maps): rank 0 writes every missing
+    <weight_map_dir>/<split>/<stem>_weight.png from the split's label directory (data_prepare/weight_maps.py, on the device), the other
+    ranks wait.  Either way a warning tells how many images get_imgs_list drops for want of a companion."""
+    img_dir, wmap_dir, label_dir = dir_list
+    if make and os.path.isdir(label_dir):
+        if rank == 0:
+            from .data_prepare import weight_maps
+            made, kept = weight_maps.make_missing(label_dir, wmap_dir, device=dev)
+            logger.info('--make-weight-maps: {:d} weight maps written to {:s} ({:d} were there)'.format(made, wmap_dir, kept))
+        if world > 1:
+            import torch.distributed as dist
+            dist.barrier()
+    if rank == 0 and all(os.path.isdir(d) for d in dir_list):
+        from .data_folder import get_imgs_list, is_image_file
+        images = sum(1 for name in os.listdir(img_dir) if is_image_file(name))
+        dropped = images - len(get_imgs_list(dir_list, post_fix))
+        if dropped > 0:
+            logger.warning('{:d} of {:d} images in {:s} have no {:s} / {:s} companion and are left out{:s}'.format(
+                dropped, images, img_dir, post_fix[0], post_fix[1], '' if make else ' (--make-weight-maps writes missing weight maps)'))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(add_help=False)
     ap.add_argument('--synthetic', type=int, default=0, help='number of synthetic batches per epoch (0 = read the dataset folders)')
@@ -66,6 +88,8 @@ def main(argv=None):
     ap.add_argument('--trusted-pickle', action='store_true', help='resume from a legacy checkpoint that needs full unpickling (trusted source only)')
     ap.add_argument('--device-augment', action='store_true',
                     help="run the reference's whole training augmentation recipe on the device (cdnet_amd/augment.py)")
+    ap.add_argument('--make-weight-maps', action='store_true',
+                    help='write every missing <weight_map_dir>/<split>/<stem>_weight.png from the label directory before the data is read')
     ap.add_argument('--elastic-alpha', type=float, default=1.0, help='random_elastic displacement scale (with --device-augment)')
     ap.add_argument('--elastic-sigma', type=float, default=50.0, help='random_elastic displacement smoothing (with --device-augment)')
     ap.add_argument('--elastic-alpha-affine', type=float, default=50.0, help='random_elastic affine point offsets (with --device-augment)')
@@ -104,6 +128,7 @@ def main(argv=None):
         # train.py:262-290 without validation split: <img_dir>/train, <weight_map_dir>/train, <label_dir>/train
         from .data_folder import DataFolder, TileBatches
         dir_list, post_fix = _dataset_layout(opt, 'train', logger)
+        _prepare_weight_maps(dir_list, post_fix, own.make_weight_maps, rank, world, dev, logger)
         dset = DataFolder(dir_list, post_fix, [3, 1, 3])
         elastic = dict(elastic_alpha=own.elastic_alpha, elastic_sigma=own.elastic_sigma, elastic_alpha_affine=own.elastic_alpha_affine)
         loader = TileBatches(dset, opt.transform['train'], B, dev, seed=opt.train['seed'] + 1000 * rank, logger=logger,
@@ -117,6 +142,8 @@ def main(argv=None):
         else:
             from .data_folder import DataFolder, TileBatches
             vdirs, vfix = _dataset_layout(opt, 'val', logger)
+            if os.path.isdir(vdirs[0]):
+                _prepare_weight_maps(vdirs, vfix, own.make_weight_maps, rank, world, dev, logger)
             if all(os.path.isdir(d) for d in vdirs):
                 vset = DataFolder(vdirs, vfix, [3, 1, 3])
                 # options.py:358: the validation transform is {label_encoding, to_tensor, normalize} - no crop: every epoch scores the same

@@ -842,6 +842,22 @@ int cdnet_hausdorff_pairs(const int32_t *true_lab, const int32_t *true_tab, cons
                           int cap, const int32_t *pairs, int M, const int32_t *items, int n_items, int32_t *d2, int32_t *err_flag,
                           void *stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Border weight maps from instance labels: the `<stem>_weight.png` of every training sample, which the losses read as png / 20
+ * (train_util_dam.py:102,171,230,242).  The reference has no generator for them; the map is U-Net's,
+ *   w = 1 + w0 * exp(-(d1 + d2)^2 / (2 sigma^2)) on background pixels, 1 on the pixels of an instance,  weight u8 = floor(20 * w),
+ * d1 <= d2 the Euclidean distances (pixel centres) to the nearest and the second-nearest distinct instance; a pixel without two
+ * instances in reach gets 20.
+ *
+ * cdnet_weight_map_radius: R = ceil(sigma * sqrt(2 ln(20 w0))), the distance beyond which no instance changes a stored byte (17 for the
+ *   defaults w0 = 10, sigma = 5); 0 when w0 <= 0, sigma <= 0 or 20 * (1 + w0) > 255.
+ * cdnet_weight_map: instances i32 [H][W] (ids <= 0 are background, positive ids arbitrary) -> weight u8 [H][W], any H, W >= 1, one launch.
+ *   Refused before any HIP call: a null pointer, w0 <= 0, sigma <= 0, 20 * (1 + w0) > 255 (the byte would wrap) and R > 64 (the LDS
+ *   window of a 32 x 32 tile, (32 + 2 R)^2 * 4 B, must fit the CU's 160 KB).
+ * ---------------------------------------------------------------------------------------------------- */
+int cdnet_weight_map_radius(double w0, double sigma);
+int cdnet_weight_map(const int32_t *instances, int H, int W, double w0, double sigma, uint8_t *weight, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
