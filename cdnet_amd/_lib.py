@@ -53,6 +53,12 @@ SIGNATURES = {
     'cdnet_watershed_workspace_bytes': (_sz, [_i, _i, _i]),
     'cdnet_watershed_process': (_i, [_vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
     'cdnet_fill_label_process': (_i, [_vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    'cdnet_label_process': (_i, [_vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    'cdnet_instance_redilate_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'cdnet_instance_redilate': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
+    'cdnet_instance_redilate_lds_rows': (_i, []),
+    'cdnet_instance_redilate_lds_cols': (_i, []),
+    'cdnet_label_count': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'cdnet_tile_postproc_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'cdnet_tile_postproc': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _sz] + [_vp] * 10),
     'cdnet_cc_workspace_bytes': (_sz, [_i, _i, _i]),

@@ -1197,3 +1197,31 @@ extern "C" int cdnet_fill_label_process(const uint8_t *pred, int N, int H, int W
     ws_drop_small_kernel<<<gl, 256, 0, st>>>(labels, hb, plane, min_size);
     return check_launch("cdnet_fill_label_process");
 }
+
+// postproc_other.process, 'dcan' branch before its re-dilation (postproc_other.py:79-80): measurements.label -> remove_small_objects, no
+// hole filling.  cdnet_fill_label_process without its fill stage; same workspace.
+extern "C" int cdnet_label_process(const uint8_t *pred, int N, int H, int W, int min_size, void *workspace, size_t workspace_bytes,
+                                   int32_t *labels, void *stream) {
+    CDNET_REQUIRE(pred && labels && workspace, "cdnet_label_process: null pointer");
+    CDNET_REQUIRE(N > 0 && H > 0 && W > 0 && (size_t)H * W < (1u << 30), "cdnet_label_process: bad size");
+    size_t o[10];
+    const size_t need = ws_layout(N, H, W, o);
+    if (workspace_bytes < need) { set_error("cdnet_label_process: workspace %zu < %zu bytes", workspace_bytes, need); return CDNET_E_WORKSPACE; }
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    int *L2 = (int *)(ws + o[1]), *aux = (int *)(ws + o[2]), *hb = (int *)(ws + o[3]), *chunk = (int *)(ws + o[9]);
+    uint8_t *m = (uint8_t *)(ws + o[7]);
+    const int plane = H * W, nchunk = cdiv(plane, CHUNK);
+    const size_t P = (size_t)N * plane;
+    const dim3 gl(lin_grid(plane, 2048), N);
+    ws_binarize_kernel<<<gl, 256, 0, st>>>(pred, plane, m);                           // non-zero -> 1
+    label4_roots(m, N, H, W, L2, st);
+    cc_count_roots_kernel<<<dim3(nchunk, N), 256, 0, st>>>(L2, plane, nchunk, chunk);
+    cc_scan_chunks_kernel<<<N, 256, 0, st>>>(nchunk, chunk, nullptr);
+    cc_rank_roots_kernel<<<dim3(nchunk, N), 256, 0, st>>>(L2, plane, nchunk, chunk, aux);
+    cc_relabel_kernel<<<gl, 256, 0, st>>>(L2, aux, plane, labels);
+    if (hipMemsetAsync(hb, 0, P * 4, st) != hipSuccess) return check_launch("memset");
+    ws_hist_kernel<<<gl, 256, 0, st>>>(labels, plane, hb);
+    ws_drop_small_kernel<<<gl, 256, 0, st>>>(labels, hb, plane, min_size);
+    return check_launch("cdnet_label_process");
+}

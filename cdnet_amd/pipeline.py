@@ -81,22 +81,29 @@ def check_tiles(r):
 
 @torch.no_grad()
 def infer_image(model, image, opt=None, tta=True, all_img_test=1, patch_size=256, overlap=40, classes=9, min_area=20,
-                radius=2, want_stages=False, defer=False):
+                radius=2, want_stages=False, defer=False, postproc=0, model_mode='Unet_rev1'):
     """The reference's per-image inference (test_dam.py:297-563) for one image tensor [3,H,W] float32 on the GPU
     (already ToTensor'd / normalised): the eight dihedral views (TTA) through the network - whole image
     (all_img_test == 1, options.py:35) or 256/40 sliding windows (utils.split_forward_dam) - softmax / gated direction
     argmax per view (get_probmaps), per-view direction-difference maps, their mean, the point-guided boundary boost, argmax,
     fill holes, remove small objects, label, dilate.  Returns dict(final int32 [H,W], count, pred, ...).
+    `postproc=1` (opt.post['postproc'], --postproc 1; test_dam.py:558-563): after the boost and arg-max `final` is
+    dilate_labels(postproc_other.process(pred == 1, model_mode, min_size=10), radius) with model_mode = opt.model['modelName'] - the raw
+    prediction and postproc_other's default min_size 10, not min_area, because test_dam.py:559 passes none - and `counts` the number of
+    distinct non-zero ids of `final`; `postproc_err` (device int32) is checked here unless `defer`; a deferring caller may
+    read it with postproc.check_postproc_err (test_dam.main does not: the ids come from this package's own labelling and the flood's pass bound
+    cannot be reached, so the flag cannot be raised there).  postproc=0: the chain above, unchanged.
     `defer=True`: nothing is read back - no host synchronisation; instead of `count` the device tensor `counts` stays in the result and the
     reference's constant-DDM assertion is left to the caller (postproc.check_views on `minmax`) - the form test_dam.main pipelines images with."""
-    from . import utils
+    from . import postproc as postproc_mod, utils                         # (`postproc` is the reference's option name here)
     if opt is not None:
         tta, all_img_test = opt.test['tta'], opt.all_img_test
         patch_size, overlap = opt.test['patch_size'], opt.test['overlap']
         classes, min_area, radius = opt.direction_classes, opt.post['min_area'], opt.post['radius']
+        postproc, model_mode = int(opt.post['postproc']), opt.model['modelName']
     assert not model.training and image.dim() == 3
     _, H, W = image.shape
-    xforms = list(postproc.TTA_XFORMS) if tta else [0]
+    xforms = list(postproc_mod.TTA_XFORMS) if tta else [0]
     V = len(xforms)
     plane = H * W
     dev = image.device
@@ -113,9 +120,9 @@ def infer_image(model, image, opt=None, tta=True, all_img_test=1, patch_size=256
         utils.split_forward_views(model, image, max(H, W), 0, xforms, classes, out=bufs)
     else:
         utils.split_forward_views(model, image, patch_size, overlap, xforms, classes, out=bufs)
-    postproc.probmaps(mask_all.view(V, 3, 1, plane), dir_all.view(V, classes, 1, plane), prob_out=probs, dcm_out=dcms)
-    r = postproc.postprocess_views(probs, points, dcms, xforms=xforms, H=H, W=W, classes=classes, min_area=min_area,
-                                   radius=radius, want_stages=want_stages, check=not defer)
+    postproc_mod.probmaps(mask_all.view(V, 3, 1, plane), dir_all.view(V, classes, 1, plane), prob_out=probs, dcm_out=dcms)
+    r = postproc_mod.postprocess_views(probs, points, dcms, xforms=xforms, H=H, W=W, classes=classes, min_area=min_area,
+                                   radius=radius, want_stages=want_stages, check=not defer, postproc=int(postproc), model_mode=model_mode)
     out = {k: (v[0] if torch.is_tensor(v) and v.dim() > 0 and v.shape[0] == 1 else v) for k, v in r.items()}
     if not defer:
         out['count'] = int(r['counts'][0])

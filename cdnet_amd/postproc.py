@@ -248,9 +248,36 @@ def dilate_labels(lab, radius):
     return out
 
 
+def label_count(lab, cap):
+    """the number of distinct non-zero ids (all of them in 1..cap) of int32 label maps [N,H,W] -> (counts int32 [N], err int32 [1]), both on
+    the device (cdnet_label_count): the instance count of a label map whose ids have gaps, without a host synchronisation"""
+    assert lab.dtype == torch.int32 and lab.dim() == 3
+    lab = lab.contiguous()
+    N, H, W = lab.shape
+    seen = torch.empty((N, int(cap)), dtype=torch.int32, device=lab.device)
+    counts = torch.empty((N,), dtype=torch.int32, device=lab.device)
+    err = torch.empty((1,), dtype=torch.int32, device=lab.device)
+    _lib.call('cdnet_label_count', _lib.ptr(lab), N, H * W, int(cap), _lib.ptr(seen), _lib.ptr(counts), _lib.ptr(err), _lib.stream_ptr())
+    return counts, err
+
+
+def other_chain(pred, model_mode, radius=2):
+    """The `--postproc 1` branch of test_dam.py:558-563 for pred u8 [N,H,W]: final = dilation(postproc_other.process(pred == 1, model_mode),
+    disk(radius)).  test_dam.py:559 passes no min_size, so postproc_other's default 10 holds here - NOT opt.post['min_area'] - and the
+    prediction goes in raw, before fill-holes and remove-small.  Returns dict(final int32 [N,H,W], counts int32 [N] = the distinct non-zero
+    ids of final, postproc_err int32 [1]: non-zero when a device chain raised its error flag); nothing is read back."""
+    from . import postproc_other
+    lab, err = postproc_other.process_device((pred == 1).to(torch.uint8), model_mode, min_size=10)
+    final = dilate_labels(lab, radius)
+    counts, cerr = label_count(final, (final.shape[1] * final.shape[2] + 1) // 2)      # (ids of a 4-connected labelling: at most a checkerboard's)
+    return dict(final=final, counts=counts, postproc_err=cerr if err is None else torch.maximum(err, cerr))
+
+
 def postprocess_views(probs, points, dcms, xforms=None, H=None, W=None, classes=9, min_area=20, radius=2,
-                      want_stages=False, check=True):
+                      want_stages=False, check=True, postproc=0, model_mode='Unet_rev1'):
     """Everything after get_probmaps for I images with V views each (test_dam.py:445-563).
+    postproc=1 (test_dam.py:558-559, --postproc 1): `final` and `counts` come from `other_chain(pred, model_mode, radius)` instead of the
+    connected-component chain (min_size 10, the raw prediction: see there); postproc=0 is the chain of :546-563.
     probs f32 [I,V,3,H,W], points f32 [I,V,H,W] (or [I,V,1,H,W]), dcms u8 [I,V,H,W] (or [I,V,1,H,W]); views in
     their own frame.  Raises AssertionError (like test_dam.py:535) if a view's DDM is constant (0/0 = NaN) - `check=False` leaves that test
     to the caller (`check_views(r)` on the returned dict): the assertion reads the codes' (min, max) back, a device-to-host synchronisation a
@@ -288,12 +315,24 @@ def postprocess_views(probs, points, dcms, xforms=None, H=None, W=None, classes=
             minmax[:, idx] = mm.reshape(I, len(vs), 2)
     r = tta_boost_argmax(probs.reshape(I, V, 3 * plane), points.reshape(I, V, plane), codes, minmax, xforms, H, W,
                          want_stages=want_stages)
-    cc = cc_chain(r['pred'], 1, min_area, radius, want_stages=want_stages)
+    if int(postproc) == 1:
+        cc = other_chain(r['pred'], model_mode, radius)
+    else:
+        cc = cc_chain(r['pred'], 1, min_area, radius, want_stages=want_stages)
     r.update(cc)
     r['codes'], r['minmax'] = codes, minmax
     if check:
         check_views(r)
+        if 'postproc_err' in r:
+            check_postproc_err(r['postproc_err'])
     return r
+
+
+def check_postproc_err(err):
+    """raise when the error flag of an `other_chain` result (device tensor or its host copy) is set"""
+    e = int(err.reshape(-1)[0])
+    if e:
+        raise RuntimeError('--postproc 1: device error flag %d in postproc_other.process or the instance count' % e)
 
 
 def check_views(r, minmax_host=None):

@@ -140,6 +140,33 @@ int cdnet_watershed_process(const uint8_t *pred, int N, int H, int W, int min_si
  *   labels i32 [N][H][W]; workspace: cdnet_watershed_workspace_bytes(N, H, W) bytes. */
 int cdnet_fill_label_process(const uint8_t *pred, int N, int H, int W, int min_size, void *workspace, size_t workspace_bytes,
                              int32_t *labels, void *stream);
+/* The 'dcan' branch before its re-dilation (postproc_other.py:79-80): measurements.label (4-connected, ids in raster order) ->
+ *   remove_small_objects, no hole filling.  Arguments and workspace as for cdnet_fill_label_process. */
+int cdnet_label_process(const uint8_t *pred, int N, int H, int W, int min_size, void *workspace, size_t workspace_bytes,
+                        int32_t *labels, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Per-instance re-dilation.   Replaces the closing loops of postproc_other.process: 'micronet' postproc_other.py:56-68 (cv2.dilate with
+ * the 3 x 3 cross, r = 1) and 'dcan' :81-97 (k_disk, r = 3); both kernels are the diamond |dx| + |dy| <= r.  For every id k, ascending:
+ *   inst = cv2.dilate(label == k, diamond(r)) (outside the image is background) -> binary_fill_holes(inst) -> canvas[inst] = k,
+ * that is out(p) = the largest k whose dilated and filled instance covers p, 0 where none does.  Exact; the result does not depend on
+ * the order the instances are worked in.
+ *
+ * cdnet_instance_redilate: label / out i32 [N][H][W] (out must not overlap label), r in 1..3, ids in 1..cap (0 = background), N * cap <= 2^28.
+ *   workspace: cdnet_instance_redilate_workspace_bytes(N, H, W, cap) bytes (0 for sizes the entry refuses), 8-byte aligned.
+ *   err_flag (1 int): 1 = an id outside 0..cap, 2 = the flood of an instance did not end within its pass bound (rows x columns of its
+ *   window + 1, which it cannot exceed); out is unspecified then.  Instances whose window (bounding box grown by r, clipped) is at most
+ *   cdnet_instance_redilate_lds_rows() x cdnet_instance_redilate_lds_cols() run in LDS, one wave each; larger ones on bit planes in the
+ *   workspace, one after the other per image.
+ * cdnet_label_count: counts[N] = the number of distinct ids in 1..cap of lab i32 [N][plane] (the instance count of a label map whose ids
+ *   have gaps, kept on the device); seen i32 [N][cap] scratch; err_flag 1 = an id outside 0..cap.
+ * ---------------------------------------------------------------------------------------------------- */
+size_t cdnet_instance_redilate_workspace_bytes(int N, int H, int W, int cap);
+int cdnet_instance_redilate(const int32_t *label, int N, int H, int W, int r, int cap, void *workspace, size_t workspace_bytes,
+                            int32_t *out, int32_t *err_flag, void *stream);
+int cdnet_instance_redilate_lds_rows(void);
+int cdnet_instance_redilate_lds_cols(void);
+int cdnet_label_count(const int32_t *lab, int N, int plane, int cap, int32_t *seen, int32_t *counts, int32_t *err_flag, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Connected-component chain.   Replaces test_dam.py:546-563:
