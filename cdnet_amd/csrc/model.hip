@@ -1002,6 +1002,9 @@ extern "C" int cdnet_window_stitch(const float *tiles, int K, int tile_h, int ti
     CDNET_REQUIRE(K > 0 && tile_h > 0 && tile_w > 0 && stride > 0 && ny > 0 && nx > 0 && Hv > 0 && Wv > 0 && overlap >= 0,
                   "cdnet_window_stitch: bad arguments");
     CDNET_REQUIRE((ny - 1) * stride + tile_h >= Hv && (nx - 1) * stride + tile_w >= Wv, "cdnet_window_stitch: windows do not cover the view");
+    // a window that is not the last keeps rows up to stride + overlap / 2 - 1 of its tile: a shorter tile would be read past its end
+    CDNET_REQUIRE((ny == 1 || tile_h >= stride + overlap / 2) && (nx == 1 || tile_w >= stride + overlap / 2),
+                  "cdnet_window_stitch: tile %d x %d is smaller than stride + overlap / 2 = %d", tile_h, tile_w, stride + overlap / 2);
     window_stitch_kernel<<<lin_grid((size_t)K * Hv * Wv, 4096), 256, 0, (hipStream_t)stream>>>(tiles, K, tile_h, tile_w, stride, overlap / 2,
                                                                                          ny, nx, Hv, Wv, out);
     return check_launch("cdnet_window_stitch");

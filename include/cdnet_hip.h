@@ -675,6 +675,8 @@ int cdnet_sgd_step(float *param, const float *grad, float *momentum_buffer, size
  *   beyond the view are the zero padding of utils.py:665-676.
  * cdnet_window_stitch: window outputs f32 [ny*nx][K][tile_h][tile_w] -> out f32 [K][Hv][Wv], keeping for every pixel
  *   the last window whose interior (overlap/2 trimmed, except at the image border) contains it (utils.py:683-712).
+ *   With more than one window along an axis the tile must hold that interior: tile >= stride + overlap/2 (CDNET_E_ARG
+ *   otherwise; every geometry of utils.window_grid has tile = stride + overlap there).
  * ---------------------------------------------------------------------------------------------------- */
 int cdnet_window_pack(const float *img, int C, int H, int W, int view_xform, int tile_h, int tile_w, int stride, int ny,
                       int nx, void *out_bf16_nhwc16, void *stream);

@@ -63,7 +63,11 @@ def test_tta_views_are_pil_transforms():
         stride, th, tw, ny, nx = utils.window_grid(hv, wv, 24, 8)
         t = torch.empty((ny * nx, th, tw, 16), dtype=torch.bfloat16, device='cuda')
         _lib.call('cdnet_window_pack', _lib.ptr(x), 3, H, W, xf, th, tw, stride, ny, nx, _lib.ptr(t), _lib.stream_ptr())
+        # the fp32-precision twin: the same windows (the image is bf16-exact), equal bits
+        t32 = torch.full((ny * nx, th, tw, 16), float('nan'), dtype=torch.float32, device='cuda')
+        _lib.call('cdnet_window_pack_f32', _lib.ptr(x), 3, H, W, xf, th, tw, stride, ny, nx, _lib.ptr(t32), _lib.stream_ptr())
         got = t.float().cpu().numpy()
+        got32 = t32.cpu().numpy()
         pad = np.zeros((3, (ny - 1) * stride + th, (nx - 1) * stride + tw), np.float32)
         pad[:, :hv, :wv] = v
         for ky in range(ny):
@@ -71,6 +75,8 @@ def test_tta_views_are_pil_transforms():
                 want = pad[:, ky * stride:ky * stride + th, kx * stride:kx * stride + tw].transpose(1, 2, 0)
                 assert np.array_equal(got[ky * nx + kx, :, :, :3], want), (xf, ky, kx)
                 assert not got[ky * nx + kx, :, :, 3:].any()
+                assert np.array_equal(got32[ky * nx + kx, :, :, :3].view(np.uint32), np.ascontiguousarray(want).view(np.uint32)), (xf, ky, kx)
+                assert not got32[ky * nx + kx, :, :, 3:].view(np.uint32).any()
 
 
 def test_infer_image_pipeline_tta_windows_vs_whole_and_oracle():
