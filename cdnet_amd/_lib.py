@@ -15,6 +15,11 @@ class WgradReduceDesc(C.Structure):          # cdnet_wgrad_reduce_desc (include/
     _fields_ = [('slab', C.c_void_p), ('dw', C.c_void_p)] + [(n, C.c_int) for n in (
         'ksplit', 'npar', 'ci_blocks', 'co_blocks', 'taps', 'CI', 'CO', 'Csrc_real', 'Cin_real', 'src_coff', 'Cout', 'mode', 'block0', 'blocks')]
 
+class DilatedConvArgs(C.Structure):          # cdnet_dilated_conv_args
+    _fields_ = [(n, C.c_void_p) for n in ('in_', 'w', 'scale', 'shift', 'out')] + [(n, C.c_int) for n in (
+        'N', 'H', 'W', 'Cin', 'in_cstride', 'Cout', 'out_cstride', 'out_coff', 'taps', 'dilation', 'leaky')] + [
+        ('slope', C.c_float), ('f32', C.c_int), ('out_nchw', C.c_int)]
+
 
 # name -> (restype, argtypes); must list every symbol include/cdnet_hip.h declares (tests/test_abi.py checks)
 SIGNATURES = {
@@ -73,6 +78,9 @@ SIGNATURES = {
     'cdnet_pack_batch_table_bytes': (_sz, [_i]),
     'cdnet_pack_conv_weights_batch': (_i, [_vp, _i, _vp, _sz, _i, _vp]),
     'cdnet_conv_forward': (_i, [_vp, _vp]),
+    'cdnet_dilated_packed_weight_elems': (_sz, [_i, _i, _i, _i]),
+    'cdnet_dilated_pack_weights': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    'cdnet_dilated_conv_forward': (_i, [_vp, _vp]),
     'cdnet_src_materialize': (_i, [_vp, _i, _i, _i, _vp, _vp]),
     'cdnet_input_pack': (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     'cdnet_input_pack_f32': (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),

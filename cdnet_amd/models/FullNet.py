@@ -1,0 +1,219 @@
+"""`FullNet` - the dense dilated network of the reference (models/FullNet.py:90-138, Hui Qu), inference on the MI355X.
+
+Same constructor, same module tree (so `state_dict()` has the reference's 301 keys and shapes at the defaults: conv1.conv.weight, conv1.bn.*,
+blocks.block{i}.denselayer{j}.conv.conv.weight, blocks.trans{i}.conv.weight, ..., conv2.weight) and the same initialisation.  The nn modules
+are parameter containers; the forward runs on cdnet_dilated_conv_forward (csrc/dilated.hip):
+
+  * every ConvLayer (Conv2d -> LeakyReLU -> BatchNorm2d, :14-21) is one launch, the eval-mode BatchNorm as the scale / shift after the LeakyReLU;
+  * a dense block lives in ONE NHWC buffer of in + n_layers * growth channels (stride rounded up to 8) in the reference's concatenated order,
+    unpadded; every layer reads channels [0, Cin) and appends its growth_rate channels in place - torch.cat([x, out], 1) (:36, :52) is never a copy;
+  * a transition reads the whole buffer and writes the base channels of the next block's buffer;
+  * conv2 (no activation, no BatchNorm, no bias) stores the fp32 [N, K, H, W] logits directly (the entry's out_nchw store).
+
+Inference only: dropout does nothing in eval mode, a forward in training mode raises.
+"""
+import ctypes as C
+import math
+
+import torch
+import torch.nn as nn
+
+from .. import _lib, runtime
+
+LEAKY_SLOPE = 0.01                    # nn.LeakyReLU's default (:20)
+WORKSPACE_BYTES = 4 << 30             # forward_packed runs sub-batches whose block buffers stay under this many bytes
+
+# hybrid dilations of one dense block, by layers per block and the block's nominal dilation (the table of :67-76)
+HYBRID_DILATIONS = {
+    4: {1: (1, 1, 1, 1), 2: (1, 2, 3, 2), 4: (1, 2, 5, 9), 8: (3, 7, 10, 13), 16: (13, 15, 17, 19)},
+    6: {1: (1, 1, 1, 1, 1, 1), 2: (1, 2, 3, 1, 2, 3), 4: (1, 2, 3, 5, 6, 7), 8: (2, 5, 7, 9, 11, 14), 16: (10, 13, 16, 17, 19, 21)},
+}
+
+
+def block_dilations(n_layers, schedule, is_hybrid):
+    """per block the dilation of each of its layers (KeyError for a (n_layers, dilation) pair the hybrid table lacks, as in the reference)"""
+    if is_hybrid:
+        return [tuple(HYBRID_DILATIONS[n_layers][int(d)]) for d in schedule]
+    return [(int(d),) * n_layers for d in schedule]
+
+
+class ConvLayer(nn.Sequential):            # :14-21
+    def __init__(self, in_channels, out_channels, kernel_size, padding=0, dilation=1):
+        super().__init__()
+        self.add_module('conv', nn.Conv2d(in_channels, out_channels, kernel_size=kernel_size, padding=padding, dilation=dilation, bias=False))
+        self.add_module('relu', nn.LeakyReLU(inplace=True))
+        self.add_module('bn', nn.BatchNorm2d(out_channels))
+
+
+class BasicLayer(nn.Sequential):           # :25-36
+    def __init__(self, in_channels, growth_rate, drop_rate, dilation=1):
+        super().__init__()
+        self.conv = ConvLayer(in_channels, growth_rate, 3, padding=dilation, dilation=dilation)
+        self.drop_rate = drop_rate
+
+    def convs(self):
+        return [self.conv]
+
+
+class BottleneckLayer(nn.Sequential):      # :39-52
+    def __init__(self, in_channels, growth_rate, drop_rate, dilation=1):
+        super().__init__()
+        self.conv1 = ConvLayer(in_channels, 4 * growth_rate, 1)
+        self.conv2 = ConvLayer(4 * growth_rate, growth_rate, 3, padding=dilation, dilation=dilation)
+        self.drop_rate = drop_rate
+
+    def convs(self):
+        return [self.conv1, self.conv2]
+
+
+class DenseBlock(nn.Sequential):           # :56-61
+    def __init__(self, in_channels, growth_rate, drop_rate, layer_type, dilations):
+        super().__init__()
+        for i, d in enumerate(dilations):
+            self.add_module('denselayer%d' % (i + 1), layer_type(in_channels + i * growth_rate, growth_rate, drop_rate, int(d)))
+
+
+def _round8(c):
+    return (c + 7) // 8 * 8
+
+
+class _Conv:
+    """one launch: the Conv2d, its optional BatchNorm, the packed weights and the folded scale / shift of the current precision"""
+
+    def __init__(self, conv, bn, leaky):
+        self.conv, self.bn, self.leaky = conv, bn, leaky
+        self.Cout, self.Cin = conv.weight.shape[:2]
+        self.taps = conv.kernel_size[0] * conv.kernel_size[1]
+        self.dilation = int(conv.dilation[0])
+        self.key = self.wp = self.scale = self.shift = None
+
+    def prepare(self, device):
+        f32 = runtime.PRECISION == 'fp32'
+        ts = [self.conv.weight] + ([] if self.bn is None else [self.bn.weight, self.bn.bias, self.bn.running_mean, self.bn.running_var])
+        key = (f32, str(device)) + tuple((t.data_ptr(), t._version) for t in ts)
+        if key == self.key:
+            return
+        w = self.conv.weight.detach().to(device=device, dtype=torch.float32).contiguous()
+        n = _lib.load().cdnet_dilated_packed_weight_elems(self.Cin, self.Cout, self.taps, int(f32))
+        self.wp = torch.empty(n, dtype=torch.bfloat16, device=device)
+        _lib.call('cdnet_dilated_pack_weights', _lib.ptr(w), _lib.ptr(self.wp), self.Cin, self.Cout, self.taps, int(f32), _lib.stream_ptr())
+        if self.bn is not None:                   # eval-mode BatchNorm: y = (x - mean) / sqrt(var + eps) * weight + bias
+            bn = self.bn
+            sc = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+            sh = bn.bias.detach().double() - bn.running_mean.detach().double() * sc
+            self.scale, self.shift = sc.float().to(device).contiguous(), sh.float().to(device).contiguous()
+        self.key = key
+
+    def run(self, src, src_stride, dst, dst_stride, dst_coff, N, H, W, nchw=False):
+        a = _lib.DilatedConvArgs()
+        a.in_, a.w, a.out = src.data_ptr(), self.wp.data_ptr(), dst.data_ptr()
+        a.scale = None if self.scale is None else self.scale.data_ptr()
+        a.shift = None if self.shift is None else self.shift.data_ptr()
+        a.N, a.H, a.W = N, H, W
+        a.Cin, a.in_cstride = self.Cin, src_stride
+        a.Cout, a.out_cstride, a.out_coff = self.Cout, dst_stride, dst_coff
+        a.taps, a.dilation = self.taps, self.dilation
+        a.leaky, a.slope = int(self.leaky), LEAKY_SLOPE
+        a.f32, a.out_nchw = int(runtime.PRECISION == 'fp32'), int(nchw)
+        _lib.call('cdnet_dilated_conv_forward', C.byref(a), _lib.stream_ptr())
+
+
+class FullNet(nn.Module):
+    def __init__(self, color_channels, output_channels=2, n_layers=6, growth_rate=24, compress_ratio=0.5,
+                 drop_rate=0.1, dilations=(1, 2, 4, 8, 16, 4, 1), is_hybrid=True, layer_type='basic'):
+        super().__init__()
+        layer = BasicLayer if layer_type == 'basic' else BottleneckLayer
+        width = 24
+        self.conv1 = ConvLayer(color_channels, width, 3, padding=1)
+        self.blocks = nn.Sequential()
+        for i, ds in enumerate(block_dilations(n_layers, dilations, is_hybrid)):
+            self.blocks.add_module('block%d' % (i + 1), DenseBlock(width, growth_rate, drop_rate, layer, ds))
+            total = width + n_layers * growth_rate
+            width = int(math.floor(total * compress_ratio))
+            self.blocks.add_module('trans%d' % (i + 1), ConvLayer(total, width, 1))
+        self.conv2 = nn.Conv2d(width, output_channels, kernel_size=3, stride=1, padding=1, bias=False)
+        for m in self.modules():                                               # :124-132
+            if isinstance(m, nn.Conv2d):
+                m.weight.data.normal_(0, math.sqrt(2. / (m.kernel_size[0] * m.kernel_size[1] * m.out_channels)))
+            elif isinstance(m, nn.BatchNorm2d):
+                m.weight.data.fill_(1)
+                m.bias.data.zero_()
+        self.color_channels, self.output_channels = color_channels, output_channels
+        self.n_blocks, self.growth_rate = len(dilations), growth_rate
+        self._rt = None
+
+    @property
+    def final_conv(self):
+        """the classifier under the name pipeline.mask_channels asks a one-output network for (a property: no extra state_dict key)"""
+        return self.conv2
+
+    def _build_runtime(self):
+        def cl(m):
+            return _Conv(m.conv, m.bn, True)
+        blocks = []
+        for i in range(self.n_blocks):
+            block = getattr(self.blocks, 'block%d' % (i + 1))
+            blocks.append(([[cl(c) for c in layer.convs()] for layer in block], cl(getattr(self.blocks, 'trans%d' % (i + 1)))))
+        self._rt = (cl(self.conv1), blocks, _Conv(self.conv2, None, False))
+
+    def _convs(self):
+        stem, blocks, final = self._rt
+        return [stem] + [c for layers, trans in blocks for layer in layers for c in layer] + [trans for _, trans in blocks] + [final]
+
+    def _channels_per_pixel(self):
+        """channels of the two widest live buffers (a block and its successor) plus the bottleneck's intermediate"""
+        stem, blocks, final = self._rt
+        widths = [_round8(trans.Cin) for _, trans in blocks] + [_round8(final.Cin)]
+        inter = max(_round8(layer[0].Cout) if len(layer) == 2 else 0 for layers, _ in blocks for layer in layers)
+        return max(a + b for a, b in zip(widths, widths[1:])) + inter
+
+    def forward(self, x):
+        if not x.is_cuda:
+            raise RuntimeError('cdnet_amd.models.FullNet.FullNet runs on the MI355X only (no CPU fallback)')
+        return self.forward_packed(runtime.input_pack(x.float()))[0]
+
+    def forward_packed(self, x16):
+        """forward on packed NHWC windows [N,H,W,16] (color_channels real channels; bf16, or fp32 in the fp32 precision mode).  Returns `(logits,)`
+        with logits f32 [N,K,H,W].  The batch runs in sub-batches whose block buffers stay under WORKSPACE_BYTES; a window's result does not
+        depend on the batch it ran in."""
+        if self.training:
+            raise RuntimeError('FullNet is inference only here: call model.eval() first (training FullNet is not implemented)')
+        if not x16.is_cuda:
+            raise RuntimeError('cdnet_amd.models.FullNet.FullNet runs on the MI355X only (no CPU fallback)')
+        assert x16.dim() == 4 and x16.shape[3] == 16 and x16.dtype == runtime.act_dtype() and x16.is_contiguous(), 'packed NHWC [N,H,W,16] windows'
+        assert self.color_channels <= 16
+        if self._rt is None:
+            self._build_runtime()
+        for c in self._convs():
+            c.prepare(x16.device)
+        N, H, W, _ = x16.shape
+        out = torch.empty((N, self.output_channels, H, W), dtype=torch.float32, device=x16.device)
+        per_window = self._channels_per_pixel() * H * W * x16.element_size()
+        sub = max(1, min(N, WORKSPACE_BYTES // per_window))
+        sub = -(-N // -(-N // sub))                                            # equal-sized sub-batches (64 windows: 32 + 32, not 56 + 8)
+        for s in range(0, N, sub):
+            self._forward_nhwc(x16[s:s + sub], out[s:s + sub])
+        return (out,)
+
+    def _forward_nhwc(self, x16, out):
+        stem, blocks, final = self._rt
+        N, H, W, _ = x16.shape
+        dt, dev = x16.dtype, x16.device
+
+        def buf(c):
+            return torch.empty((N, H, W, _round8(c)), dtype=dt, device=dev)
+        cur = buf(blocks[0][1].Cin)
+        stem.run(x16, 16, cur, cur.shape[3], 0, N, H, W)
+        for i, (layers, trans) in enumerate(blocks):
+            cs = cur.shape[3]
+            for layer in layers:
+                if len(layer) == 1:                                    # BasicLayer: append in place
+                    layer[0].run(cur, cs, cur, cs, layer[0].Cin, N, H, W)
+                else:                                                  # BottleneckLayer: 1x1 to 4 * growth, then the dilated 3x3 appends
+                    mid = buf(layer[0].Cout)
+                    layer[0].run(cur, cs, mid, mid.shape[3], 0, N, H, W)
+                    layer[1].run(mid, mid.shape[3], cur, cs, layer[0].Cin, N, H, W)
+            nxt = buf(blocks[i + 1][1].Cin if i + 1 < len(blocks) else final.Cin)
+            trans.run(cur, cs, nxt, nxt.shape[3], 0, N, H, W)
+            cur = nxt
+        final.run(cur, cur.shape[3], out, 0, 0, N, H, W, nchw=True)

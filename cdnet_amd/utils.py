@@ -29,7 +29,13 @@ def chooseModel(opt):
     if name == 'HRNet18_rev1':                       # utils.py:880-882
         from .models.dam.seg_hrnet_rev1 import HighResolutionNet
         return HighResolutionNet(opt)
-    raise NotImplementedError('model {} is outside the CDNet hot path (SURVEY.md section 8: UNet, UNet2RevA1_vgg16, model_unet_MandD*, HRNet18_rev1)'.format(name))
+    if name == 'FullNet':                            # utils.py:833-838 (whose `dilations` entry options.py leaves commented out: the class default)
+        from .models.FullNet import FullNet
+        m = opt.model
+        return FullNet(m['in_c'], m['out_c'], n_layers=m['n_layers'], growth_rate=m['growth_rate'], drop_rate=m['drop_rate'],
+                       dilations=m.get('dilations', [1, 2, 4, 8, 16, 4, 1]), is_hybrid=m['is_hybrid'], compress_ratio=m['compress_ratio'],
+                       layer_type=m['layer_type'])
+    raise NotImplementedError('model {} is outside the CDNet hot path (SURVEY.md section 8: UNet, UNet2RevA1_vgg16, model_unet_MandD*, HRNet18_rev1, FullNet)'.format(name))
 
 
 def window_grid(h0, w0, size, overlap):

@@ -343,6 +343,47 @@ int cdnet_pack_conv_weights_batch(const cdnet_pack_job *jobs, int n_jobs, void *
 int cdnet_conv_forward(const cdnet_conv_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Dilated dense-block convolution (dilated.hip): FullNet's ConvLayer (models/FullNet.py:14-36: Conv2d(dilation, bias=False) ->
+ * LeakyReLU -> BatchNorm2d, then torch.cat([x, out], 1)) and its stem / transition / final convolutions (:90-138), eval mode.  NHWC:
+ *
+ *   out[n][y][x][out_coff + co] = post( sum_{ky,kx,ci<Cin} w[co][ci][ky][kx] * in[n][y + (ky-1) d][x + (kx-1) d][ci] )    zero outside the image
+ *   post(v) = (leaky ? (v >= 0 ? v : slope v) : v) * scale[co] + shift[co]        (the LeakyReLU BEFORE the affine; scale NULL = 1, shift NULL = 0)
+ *
+ * taps = 9 (3x3, padding = dilation) or 1 (1x1, dilation ignored but >= 1); dilation >= 1 without an upper bound (it may exceed H and W:
+ * a tap that no pixel of a wave's strip can reach costs no load and no MFMA).  Cin >= 1 is any count, in_cstride >= Cin the channel
+ * stride of `in`, a multiple of 8 elements; the kernel loads up to round_up(Cin, 8) channels of a pixel and masks (selects, never
+ * multiplies) those >= Cin, so NaN there is harmless.  Cout >= 1 is any count: exactly channels [out_coff, out_coff + Cout) of `out`
+ * (channel stride out_cstride >= out_coff + Cout, no alignment asked of out_coff) are written, nothing else.
+ * `in` and `out` may be the same tensor (then in_cstride == out_cstride) when [0, Cin) and [out_coff, out_coff + Cout) are disjoint: a
+ * dense layer appends its growth_rate channels in place, the concatenation is never a copy.  Overlapping ranges are an argument error.
+ * f32 = 0: in / out bf16, `w` the one-image pack, one bf16 MFMA per product, fp32 accumulation.
+ * f32 = 1: in / out fp32, `w` the split pack, every product as a_lo b_hi + a_hi b_lo + a_hi b_hi like conv32.hip.
+ * out_nchw = 1: `out` is fp32 [N][Cout][H][W] whatever f32 says (the logits cdnet_window_stitch and the soft-max read); out_coff = 0,
+ * out_cstride is ignored and `out` must not be `in`.
+ * Argument errors (CDNET_E_ARG: a null in / w / out, taps not 1 or 9, dilation < 1, a count < 1, a stride below its channel count or an
+ * in_cstride that is no multiple of 8, overlapping in-place ranges) are found before any HIP call. */
+typedef struct cdnet_dilated_conv_args {
+    const void *in;          /* [N][H][W][in_cstride] bf16 / fp32 */
+    const void *w;           /* cdnet_dilated_pack_weights */
+    const float *scale;      /* [Cout] or NULL */
+    const float *shift;      /* [Cout] or NULL */
+    void *out;
+    int N, H, W;
+    int Cin, in_cstride;
+    int Cout, out_cstride, out_coff;
+    int taps, dilation;
+    int leaky;
+    float slope;
+    int f32, out_nchw;
+} cdnet_dilated_conv_args;
+/* bf16 elements of the pack of one layer (f32 = 1: the hi and the lo image, twice as many) */
+size_t cdnet_dilated_packed_weight_elems(int Cin, int Cout, int taps, int f32);
+/* fp32 Conv2d weights [Cout][Cin][3][3] / [Cout][Cin][1][1] (device) -> the MFMA-fragment pack, once per layer: per (tap, 16-channel
+ * K step, 32-wide output tile) the 64 lanes' 8 bf16 values in load order (f32 = 1: followed by the bf16(w - bf16(w)) image). */
+int cdnet_dilated_pack_weights(const float *w, void *packed, int Cin, int Cout, int taps, int f32, void *stream);
+int cdnet_dilated_conv_forward(const cdnet_dilated_conv_args *args, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * Model-path streaming kernels (not convolutions).
  * cdnet_input_pack: f32 NCHW [N][C<=16][H][W] (the ToTensor output, my_transforms_direction.py:945) -> bf16 NHWC
  *   [N][H][W][16] with zero-padded channels.
