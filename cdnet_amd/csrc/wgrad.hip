@@ -1438,9 +1438,17 @@ __global__ __launch_bounds__(256) void wgrad_reduce_batch_kernel(const ReduceDes
                       d.mode, d.dw, b - (unsigned)d.block0, s_part);
 }
 
+// which instantiation the last launch of this thread took (cdnet_conv_backward_weight_last_form; host only, packed as
+// CDNET_WGRAD_FORM_* of cdnet_hip.h): the tests assert the dispatch instead of assuming it
+thread_local int g_last_form = 0;
+constexpr int wgrad_form(int family, int ci_t, int co_t, int taps, bool res, int xf, int qm) {
+    return family | (ci_t << 4) | (co_t << 8) | (taps << 12) | ((res ? 1 : 0) << 16) | (xf << 17) | (qm << 19);
+}
+
 template <int CI_T, int CO_T, int TAPS, bool RES, int XF>
 int launch_wgrad_ws(const WgradArgs &A, hipStream_t st) {
     constexpr int CI = CI_T * 32, CO = CO_T * 32;
+    g_last_form = wgrad_form(CDNET_WGRAD_FAMILY_WS, CI_T, CO_T, TAPS, RES, XF, 0);
     constexpr int smem = 2 * (NPIX_A * pstride(CI) + NPIX_G * pstride(CO));
     dim3 grid(cdiv(A.src.C, CI) * cdiv(A.Cout, CO), A.npar, A.ksplit);
     return launch_lds<wgrad_ws_kernel<CI_T, CO_T, TAPS, RES, XF>>(grid, NT, smem, smem, st, "hipFuncSetAttribute(wgrad_ws)", "wgrad_ws_kernel", A);
@@ -1452,6 +1460,7 @@ int launch_wgrad_gen(const WgradArgs &A, hipStream_t st) {
     constexpr int stage_bytes = NPIX_A * pstride(CI) + NPIX_G * pstride(CO);
     constexpr int fold_bytes = 4 * TAPS * 16 * 64 * 4;
     constexpr int smem = 2 * stage_bytes > fold_bytes ? 2 * stage_bytes : fold_bytes;
+    g_last_form = wgrad_form(CDNET_WGRAD_FAMILY_GEN, CI_T, CO_T, TAPS, RES, XF_GEN, 0);
     dim3 grid(cdiv(A.src.C, CI) * cdiv(A.Cout, CO), A.npar, A.ksplit);
     return launch_lds<wgrad_kernel<CI_T, CO_T, TAPS, RES>>(grid, NT, smem, smem, st, "hipFuncSetAttribute(wgrad)", "wgrad_kernel", A);
 }
@@ -1466,6 +1475,7 @@ int launch_wgrad_ws32(const WgradArgs &A, hipStream_t st) {
         constexpr int smem = QM == 1 ? 2 * (2 * (8 + 2) * HALO_W * pstride(32) + 2 * 8 * TW * pstride(32))
                                      : 2 * (2 * NPIX_A32 * pstride(64) + 2 * NPIX_G32 * pstride(64));
         dim3 grid(cdiv(A.src.C, 64) * cdiv(A.Cout, 64), A.npar, A.ksplit);
+        g_last_form = wgrad_form(CDNET_WGRAD_FAMILY_WS32, 2, 2, TAPS, false, XF, QM);
         return launch_lds<wgrad_ws32_kernel<XF, TAPS, QM>>(grid, 512, smem, smem, st, "hipFuncSetAttribute(wgrad_ws32)", "wgrad_ws32_kernel", A);
     };
     // quadrants of zero padding are not multiplied (QM): at most 32 channels on the input side, the output side, or both
@@ -1487,6 +1497,7 @@ int launch_wgrad_f32(const WgradArgs &A, hipStream_t st) {
     auto go = [&](auto qm_c) -> int {
         constexpr int QM = decltype(qm_c)::value;
         dim3 grid(cdiv(A.src.C, CI) * cdiv(A.Cout, CO), A.npar, A.ksplit);
+        g_last_form = wgrad_form(CDNET_WGRAD_FAMILY_F32, CI_T, CO_T, TAPS, false, 0, QM);
         return launch_lds<wgrad_f32_kernel<CI_T, CO_T, TAPS, QM>>(grid, NT32, smem, smem, st, "hipFuncSetAttribute(wgrad_f32)", "wgrad_f32_kernel", A);
     };
     if constexpr (CI_T == 2 && CO_T == 2 && TAPS != 9) {
@@ -1576,6 +1587,8 @@ extern "C" int cdnet_conv_backward_weight(const cdnet_conv_src *src, int src_cof
                                                 mode, dw);
     return check_launch("wgrad_reduce_kernel");
 }
+
+extern "C" int cdnet_conv_backward_weight_last_form(void) { return g_last_form; }
 
 extern "C" int cdnet_wgrad_reduce_desc_fill(int C_src, int src_coff, int Csrc_real, int Cin_real, int Cout, int taps, int npar,
                                             int ci_tiles, int ksplit, const float *slab, float *dw, int mode, int block0,

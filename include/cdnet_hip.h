@@ -469,6 +469,17 @@ int cdnet_conv_backward_weight(const cdnet_conv_src *src, int src_coff, int Csrc
                                const uint16_t *grad_out, int Cout, int N, int H, int W, int taps, int npar,
                                int ostride, int ci_tiles, int ksplit, float *slab, float *dw, int mode, void *stream);
 
+/* The kernel instantiation the calling thread's last cdnet_conv_backward_weight launched (host-side record, thread-local like
+ * cdnet_last_error; 0 before the first launch).  For tests, which assert the dispatch form of every case.  Bit layout:
+ *   bits 0-3 family (CDNET_WGRAD_FAMILY_*), 4-7 CI_T, 8-11 CO_T (32-channel tiles of the workgroup's dW block), 12-15 TAPS,
+ *   bit 16 RES (residual template form), bits 17-18 XF (0 plain, 1 fast, 2 generic; the fp32 kernel applies transforms at run time: 0),
+ *   bits 19-21 QM (quadrant mode of the fp32 kernels; 0 for the 16-bit ones). */
+#define CDNET_WGRAD_FAMILY_GEN  1   /* wgrad_kernel */
+#define CDNET_WGRAD_FAMILY_WS   2   /* wgrad_ws_kernel */
+#define CDNET_WGRAD_FAMILY_F32  3   /* wgrad_f32_kernel */
+#define CDNET_WGRAD_FAMILY_WS32 4   /* wgrad_ws32_kernel */
+int cdnet_conv_backward_weight_last_form(void);
+
 /* Deferred split-K reduction: `mode | CDNET_WGRAD_DEFER_REDUCE` makes cdnet_conv_backward_weight stop after the slabs (which then
  * must stay untouched - one slab buffer per call); cdnet_wgrad_reduce_batch sums the slabs of any number of such calls and scatters
  * into their dw in ONE launch, bit-identical to the per-call reduction (same fixed order).  The table lives in device memory:
