@@ -20,6 +20,24 @@ class DilatedConvArgs(C.Structure):          # cdnet_dilated_conv_args
         'N', 'H', 'W', 'Cin', 'in_cstride', 'Cout', 'out_cstride', 'out_coff', 'taps', 'dilation', 'leaky')] + [
         ('slope', C.c_float), ('f32', C.c_int), ('out_nchw', C.c_int)]
 
+class DilatedBwdDataArgs(C.Structure):       # cdnet_dilated_bwd_data_args
+    _fields_ = [(n, C.c_void_p) for n in ('g', 'w', 'dx')] + [(n, C.c_int) for n in (
+        'N', 'H', 'W', 'Cout', 'g_cstride', 'Cin', 'dx_cstride', 'dx_coff', 'taps', 'dilation', 'accumulate', 'f32')]
+
+class DilatedWgradArgs(C.Structure):         # cdnet_dilated_wgrad_args
+    _fields_ = [(n, C.c_void_p) for n in ('x', 'g', 'dw', 'ws')] + [('ws_bytes', C.c_size_t)] + [(n, C.c_int) for n in (
+        'N', 'H', 'W', 'Cin', 'x_cstride', 'Cout', 'g_cstride', 'taps', 'dilation')]
+
+class SliceBnFwdArgs(C.Structure):           # cdnet_slice_bn_fwd_args
+    _fields_ = [(n, C.c_void_p) for n in ('z', 'out', 'gamma', 'beta', 'running_mean', 'running_var', 'mean', 'invstd', 'ws')] + [
+        ('ws_floats', C.c_size_t), ('P', C.c_longlong)] + [(n, C.c_int) for n in ('C', 'z_cstride', 'out_cstride', 'out_coff')] + [
+        (n, C.c_float) for n in ('eps', 'momentum', 'p_drop')] + [('layer', C.c_int), ('key', C.c_ulonglong)]
+
+class SliceBnBwdArgs(C.Structure):           # cdnet_slice_bn_bwd_args
+    _fields_ = [(n, C.c_void_p) for n in ('dy', 'z', 'mean', 'invstd', 'gamma', 'dgamma', 'dbeta', 'g', 'ws')] + [
+        ('ws_floats', C.c_size_t), ('P', C.c_longlong)] + [(n, C.c_int) for n in ('C', 'z_cstride', 'dy_cstride', 'dy_coff', 'g_cstride')] + [
+        (n, C.c_float) for n in ('slope', 'p_drop')] + [('layer', C.c_int), ('key', C.c_ulonglong)]
+
 
 # name -> (restype, argtypes); must list every symbol include/cdnet_hip.h declares (tests/test_abi.py checks)
 SIGNATURES = {
@@ -81,6 +99,14 @@ SIGNATURES = {
     'cdnet_dilated_packed_weight_elems': (_sz, [_i, _i, _i, _i]),
     'cdnet_dilated_pack_weights': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     'cdnet_dilated_conv_forward': (_i, [_vp, _vp]),
+    'cdnet_dilated_pack_weights_bwd': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    'cdnet_dilated_conv_backward_data': (_i, [_vp, _vp]),
+    'cdnet_dilated_wgrad_workspace_bytes': (_sz, [_i] * 6),
+    'cdnet_dilated_conv_backward_weight': (_i, [_vp, _vp]),
+    'cdnet_slice_bn_workspace_floats': (_sz, [C.c_longlong, _i]),
+    'cdnet_slice_bn_train_forward': (_i, [_vp, _vp]),
+    'cdnet_slice_bn_train_backward': (_i, [_vp, _vp]),
+    'cdnet_dropout_mask': (_i, [C.c_ulonglong, _i, _sz, _f, _vp, _vp]),
     'cdnet_src_materialize': (_i, [_vp, _i, _i, _i, _vp, _vp]),
     'cdnet_input_pack': (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     'cdnet_input_pack_f32': (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),

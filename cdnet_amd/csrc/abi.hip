@@ -20,7 +20,8 @@ extern "C" size_t cdnet_abi_sizeof(const char *name) {
 #define CDNET_SZ(T) if (!strcmp(name, #T)) return sizeof(T)
     CDNET_SZ(cdnet_conv_src); CDNET_SZ(cdnet_conv_args); CDNET_SZ(cdnet_pack_job); CDNET_SZ(cdnet_head_feat); CDNET_SZ(cdnet_wgrad_reduce_desc);
     CDNET_SZ(cdnet_grad_in); CDNET_SZ(cdnet_bn_bwd_args); CDNET_SZ(cdnet_fuse_term); CDNET_SZ(cdnet_grad_term); CDNET_SZ(cdnet_aug_sample);
-    CDNET_SZ(cdnet_aug_geo); CDNET_SZ(cdnet_dilated_conv_args);
+    CDNET_SZ(cdnet_aug_geo); CDNET_SZ(cdnet_dilated_conv_args); CDNET_SZ(cdnet_dilated_bwd_data_args); CDNET_SZ(cdnet_dilated_wgrad_args);
+    CDNET_SZ(cdnet_slice_bn_fwd_args); CDNET_SZ(cdnet_slice_bn_bwd_args);
 #undef CDNET_SZ
     return 0;
 }

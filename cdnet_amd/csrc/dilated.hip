@@ -15,6 +15,10 @@
 // 8 s + [0, 8) - the pack uses the same order, which is all that a GEMM asks of K.
 // Channels >= Cin of the last 8-channel unit and pixels outside the image are selected to zero before the MFMA (never multiplied).
 // fp32 mode: fragments split into bf16 hi / lo, three MFMAs per product in conv32.hip's order (a_lo b_hi, a_hi b_lo, a_hi b_hi).
+//
+// Training: backward-data (cdnet_dilated_conv_backward_data) is this kernel on swapped roles - its input is the gradient g of the raw
+// convolution output, GEMM-K runs over Cout x taps, GEMM-N over Cin, the pack is w'[ci][co][8 - tap] (cdnet_dilated_pack_weights_bwd) - with
+// the template parameter ACC for the store that adds into a block's gradient buffer.  The other training kernels are in dilated_train.hip.
 #include "common.h"
 
 using namespace cdnet;
@@ -78,7 +82,9 @@ __device__ __forceinline__ uint16_t to_bf16(float v) {
 }
 
 // grid: x = 32-pixel strips x row groups of WAVES * MT rows, y = groups of NT 32-wide output tiles, z = image
-template <int MT, int NT, bool F32>
+// ACC: the NHWC store adds to what `out` holds (backward-data into a gradient buffer that other layers wrote, cdnet_dilated_conv_backward_data);
+// the forward instantiations have ACC = false
+template <int MT, int NT, bool F32, bool ACC = false>
 __global__ __launch_bounds__(WAVES * 64) void dilated_conv_kernel(const cdnet_dilated_conv_args A) {
     constexpr int IMGS = F32 ? 2 : 1;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, p = lane & 31, h = lane >> 5;
@@ -171,8 +177,13 @@ __global__ __launch_bounds__(WAVES * 64) void dilated_conv_kernel(const cdnet_di
                     static_cast<float *>(A.out)[(((size_t)n * A.Cout + co) * A.H + y) * A.W + x] = v;
                 } else {
                     const size_t o = (((size_t)n * A.H + y) * A.W + x) * (size_t)A.out_cstride + A.out_coff + co;
-                    if constexpr (F32) static_cast<float *>(A.out)[o] = v;
-                    else static_cast<uint16_t *>(A.out)[o] = to_bf16(v);
+                    if constexpr (F32) {
+                        if constexpr (ACC) v += static_cast<float *>(A.out)[o];
+                        static_cast<float *>(A.out)[o] = v;
+                    } else {
+                        if constexpr (ACC) v += __builtin_bit_cast(float, (unsigned)static_cast<uint16_t *>(A.out)[o] << 16);
+                        static_cast<uint16_t *>(A.out)[o] = to_bf16(v);
+                    }
                 }
             }
         }
@@ -198,6 +209,25 @@ __global__ void dilated_pack_kernel(const float *w, uint16_t *packed, int Cin, i
     }
 }
 
+// the backward-data pack: the same fragment order for w'[ci][co][taps - 1 - tap] - GEMM-K runs over Cout, GEMM-N over Cin, taps mirrored
+__global__ void dilated_pack_bwd_kernel(const float *w, uint16_t *packed, int Cin, int Cout, int taps, int f32, size_t rows) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows) return;
+    const int NTT = (Cin + 31) / 32, KK = 2 * ((Cout + KPAIR - 1) / KPAIR);
+    const int lane = (int)(i % 64);
+    const size_t f = i / 64;
+    const int t = (int)(f % NTT), kk = (int)((f / NTT) % KK), tap = (int)(f / NTT / KK);
+    const int ci = t * 32 + (lane & 31), c0 = (kk >> 1) * KPAIR + 16 * (lane >> 5) + 8 * (kk & 1);
+    uint16_t *dst = packed + f * (size_t)(FRAG * (f32 ? 2 : 1)) + (size_t)lane * 8;
+    for (int j = 0; j < 8; ++j) {
+        const int co = c0 + j;
+        const float v = (co < Cout && ci < Cin) ? w[((size_t)co * Cin + ci) * taps + (taps - 1 - tap)] : 0.f;
+        const __bf16 hb = static_cast<__bf16>(v);
+        dst[j] = __builtin_bit_cast(uint16_t, hb);
+        if (f32) dst[FRAG + j] = to_bf16(v - static_cast<float>(hb));
+    }
+}
+
 size_t pack_rows(int Cin, int Cout, int taps) {
     return (size_t)taps * (2 * ((Cin + KPAIR - 1) / KPAIR)) * ((Cout + 31) / 32) * 64;
 }
@@ -209,6 +239,20 @@ int launch(const cdnet_dilated_conv_args &A, hipStream_t st) {
     if (A.f32) dilated_conv_kernel<MT, NT, true><<<grid, WAVES * 64, 0, st>>>(A);
     else dilated_conv_kernel<MT, NT, false><<<grid, WAVES * 64, 0, st>>>(A);
     return check_launch("cdnet_dilated_conv_forward");
+}
+
+template <int MT, int NT>
+int launch_bwd(const cdnet_dilated_conv_args &A, bool acc, hipStream_t st) {
+    const int tiles_x = cdiv(A.W, TILE_W), tiles_y = cdiv(A.H, WAVES * MT);
+    const dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)cdiv(cdiv(A.Cout, 32), NT), (unsigned)A.N);
+    if (A.f32) {
+        if (acc) dilated_conv_kernel<MT, NT, true, true><<<grid, WAVES * 64, 0, st>>>(A);
+        else dilated_conv_kernel<MT, NT, true, false><<<grid, WAVES * 64, 0, st>>>(A);
+    } else {
+        if (acc) dilated_conv_kernel<MT, NT, false, true><<<grid, WAVES * 64, 0, st>>>(A);
+        else dilated_conv_kernel<MT, NT, false, false><<<grid, WAVES * 64, 0, st>>>(A);
+    }
+    return check_launch("cdnet_dilated_conv_backward_data");
 }
 
 }  // namespace
@@ -254,4 +298,44 @@ extern "C" int cdnet_dilated_conv_forward(const cdnet_dilated_conv_args *args, v
     CDNET_REQUIRE((long long)cdiv(A.W, TILE_W) * cdiv(A.H, WAVES) < (1ll << 31), "cdnet_dilated_conv_forward: image too large");
     if (A.Cout <= 32) return launch<4, 1>(A, (hipStream_t)stream);
     return launch<2, 2>(A, (hipStream_t)stream);
+}
+
+extern "C" int cdnet_dilated_pack_weights_bwd(const float *w, void *packed, int Cin, int Cout, int taps, int f32, void *stream) {
+    CDNET_REQUIRE(w && packed, "cdnet_dilated_pack_weights_bwd: null pointer");
+    CDNET_REQUIRE(Cin >= 1 && Cout >= 1, "cdnet_dilated_pack_weights_bwd: Cin %d, Cout %d must be positive", Cin, Cout);
+    CDNET_REQUIRE(taps == 1 || taps == 9, "cdnet_dilated_pack_weights_bwd: taps %d (1 or 9)", taps);
+    const size_t rows = pack_rows(Cout, Cin, taps);
+    dilated_pack_bwd_kernel<<<(unsigned)((rows + 255) / 256), 256, 0, (hipStream_t)stream>>>(w, static_cast<uint16_t *>(packed), Cin, Cout, taps,
+                                                                                            f32 ? 1 : 0, rows);
+    return check_launch("cdnet_dilated_pack_weights_bwd");
+}
+
+// dx = conv(g, w') is the forward kernel on swapped roles: its `in` is g (Cout channels), its output tile count runs over Cin
+extern "C" int cdnet_dilated_conv_backward_data(const cdnet_dilated_bwd_data_args *args, void *stream) {
+    CDNET_REQUIRE(args, "cdnet_dilated_conv_backward_data: null args");
+    const cdnet_dilated_bwd_data_args &B = *args;
+    CDNET_REQUIRE(B.g && B.w && B.dx, "cdnet_dilated_conv_backward_data: null g / w / dx");
+    CDNET_REQUIRE(B.taps == 1 || B.taps == 9, "cdnet_dilated_conv_backward_data: taps %d (1 or 9)", B.taps);
+    CDNET_REQUIRE(B.dilation >= 1, "cdnet_dilated_conv_backward_data: dilation %d < 1", B.dilation);
+    CDNET_REQUIRE(B.N >= 1 && B.H >= 1 && B.W >= 1 && B.Cin >= 1 && B.Cout >= 1,
+                  "cdnet_dilated_conv_backward_data: N %d H %d W %d Cin %d Cout %d must be positive", B.N, B.H, B.W, B.Cin, B.Cout);
+    CDNET_REQUIRE(B.N <= 65535, "cdnet_dilated_conv_backward_data: N %d > 65535 images per launch", B.N);
+    CDNET_REQUIRE(B.g_cstride >= B.Cout && B.g_cstride % 8 == 0,
+                  "cdnet_dilated_conv_backward_data: g_cstride %d must be a multiple of 8 and >= Cout %d", B.g_cstride, B.Cout);
+    CDNET_REQUIRE(B.dx_coff >= 0 && B.dx_cstride >= 1 && (long long)B.dx_coff + B.Cin <= B.dx_cstride,
+                  "cdnet_dilated_conv_backward_data: dx_coff %d + Cin %d exceeds dx_cstride %d", B.dx_coff, B.Cin, B.dx_cstride);
+    if (B.g == B.dx) {
+        CDNET_REQUIRE(B.g_cstride == B.dx_cstride, "cdnet_dilated_conv_backward_data: in place with strides %d != %d", B.g_cstride, B.dx_cstride);
+        CDNET_REQUIRE(B.dx_coff >= B.Cout, "cdnet_dilated_conv_backward_data: in place, target channels [%d, %d) overlap the source's [0, %d)",
+                      B.dx_coff, B.dx_coff + B.Cin, B.Cout);
+    }
+    CDNET_REQUIRE((long long)cdiv(B.W, TILE_W) * cdiv(B.H, WAVES) < (1ll << 31), "cdnet_dilated_conv_backward_data: image too large");
+    cdnet_dilated_conv_args A = {};
+    A.in = B.g; A.w = B.w; A.scale = nullptr; A.shift = nullptr; A.out = B.dx;
+    A.N = B.N; A.H = B.H; A.W = B.W;
+    A.Cin = B.Cout; A.in_cstride = B.g_cstride;
+    A.Cout = B.Cin; A.out_cstride = B.dx_cstride; A.out_coff = B.dx_coff;
+    A.taps = B.taps; A.dilation = B.dilation; A.leaky = 0; A.slope = 0.f; A.f32 = B.f32 ? 1 : 0; A.out_nchw = 0;
+    if (A.Cout <= 32) return launch_bwd<4, 1>(A, B.accumulate != 0, (hipStream_t)stream);
+    return launch_bwd<2, 2>(A, B.accumulate != 0, (hipStream_t)stream);
 }

@@ -10,7 +10,12 @@ are parameter containers; the forward runs on cdnet_dilated_conv_forward (csrc/d
   * a transition reads the whole buffer and writes the base channels of the next block's buffer;
   * conv2 (no activation, no BatchNorm, no bias) stores the fp32 [N, K, H, W] logits directly (the entry's out_nchw store).
 
-Inference only: dropout does nothing in eval mode, a forward in training mode raises.
+Training (fp32 precision mode, under a trainer's tape - cdnet_amd.trainer.FullNetTrainer): every ConvLayer is the same launch with the
+LeakyReLU alone, its output z kept compact, then cdnet_slice_bn_train_forward (batch statistics, running statistics, the dense layers'
+dropout) into the slice of the block buffer; backward mirrors the in-place append: a transition's backward-data stores the whole gradient
+buffer of its block, the dense layers run in reverse order, each reading its own slice and accumulating into the channels in front of it
+(cdnet_slice_bn_train_backward, cdnet_dilated_conv_backward_weight, cdnet_dilated_conv_backward_data).  Without a tape a forward in training
+mode raises.
 """
 import ctypes as C
 import math
@@ -86,23 +91,79 @@ class _Conv:
         self.taps = conv.kernel_size[0] * conv.kernel_size[1]
         self.dilation = int(conv.dilation[0])
         self.key = self.wp = self.scale = self.shift = None
+        self.p_drop = 0.0                         # dropout behind this layer's BatchNorm (the last ConvLayer of a dense layer, training)
+        self.needs_dx = True                      # False: the stem, whose input is the image
+        self.wpb = self.wpb_key = self.mean = self.invstd = None
 
-    def prepare(self, device):
+    def prepare(self, device, fold=True):
+        """fold False (training): the pack alone, no eval-mode scale / shift"""
         f32 = runtime.PRECISION == 'fp32'
         ts = [self.conv.weight] + ([] if self.bn is None else [self.bn.weight, self.bn.bias, self.bn.running_mean, self.bn.running_var])
-        key = (f32, str(device)) + tuple((t.data_ptr(), t._version) for t in ts)
+        # (the optimiser kernels and the training forward write parameters and running statistics through raw pointers: the epoch counts them)
+        key = (f32, str(device), fold, runtime.WEIGHTS_EPOCH[0]) + tuple((t.data_ptr(), t._version) for t in ts)
         if key == self.key:
             return
         w = self.conv.weight.detach().to(device=device, dtype=torch.float32).contiguous()
         n = _lib.load().cdnet_dilated_packed_weight_elems(self.Cin, self.Cout, self.taps, int(f32))
         self.wp = torch.empty(n, dtype=torch.bfloat16, device=device)
         _lib.call('cdnet_dilated_pack_weights', _lib.ptr(w), _lib.ptr(self.wp), self.Cin, self.Cout, self.taps, int(f32), _lib.stream_ptr())
-        if self.bn is not None:                   # eval-mode BatchNorm: y = (x - mean) / sqrt(var + eps) * weight + bias
+        self.scale = self.shift = None
+        if self.bn is not None and fold:          # eval-mode BatchNorm: y = (x - mean) / sqrt(var + eps) * weight + bias
             bn = self.bn
             sc = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
             sh = bn.bias.detach().double() - bn.running_mean.detach().double() * sc
             self.scale, self.shift = sc.float().to(device).contiguous(), sh.float().to(device).contiguous()
         self.key = key
+
+    def prepare_train(self, device):
+        """the forward pack without the fold, the backward-data pack w'[ci][co][8 - tap] and the saved statistics' buffers"""
+        self.prepare(device, fold=False)
+        if self.needs_dx and self.wpb_key != self.key:
+            w = self.conv.weight.detach()
+            n = _lib.load().cdnet_dilated_packed_weight_elems(self.Cout, self.Cin, self.taps, 1)
+            if self.wpb is None or self.wpb.numel() != n or self.wpb.device != w.device:
+                self.wpb = torch.empty(n, dtype=torch.bfloat16, device=device)
+            _lib.call('cdnet_dilated_pack_weights_bwd', _lib.ptr(w), _lib.ptr(self.wpb), self.Cin, self.Cout, self.taps, 1, _lib.stream_ptr())
+            self.wpb_key = self.key
+        if self.bn is not None and (self.mean is None or self.mean.device != self.conv.weight.device):
+            self.mean = torch.empty(self.Cout, dtype=torch.float32, device=device)
+            self.invstd = torch.empty(self.Cout, dtype=torch.float32, device=device)
+
+    def bn_forward(self, z, dst, dst_stride, dst_coff, P, layer, key, ws):
+        """z -> batch statistics (saved, running statistics updated) -> BatchNorm + this layer's dropout into dst's channel slice"""
+        bn = self.bn
+        a = _lib.SliceBnFwdArgs()
+        a.z, a.out, a.gamma, a.beta = z.data_ptr(), dst.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr()
+        if bn.track_running_stats:
+            a.running_mean, a.running_var = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
+        a.mean, a.invstd, a.ws, a.ws_floats = self.mean.data_ptr(), self.invstd.data_ptr(), ws.data_ptr(), ws.numel()
+        a.P, a.C, a.z_cstride, a.out_cstride, a.out_coff = P, self.Cout, z.shape[3], dst_stride, dst_coff
+        a.eps, a.momentum, a.p_drop, a.layer, a.key = bn.eps, bn.momentum, self.p_drop, layer, key
+        _lib.call('cdnet_slice_bn_train_forward', C.byref(a), _lib.stream_ptr())
+
+    def bn_backward(self, dy, dy_stride, dy_coff, z, g, g_stride, P, layer, key, ws):
+        """gradient of the slice -> dgamma, dbeta (the parameters' views of the flat gradient buffer) and g, the gradient of the raw output"""
+        bn = self.bn
+        a = _lib.SliceBnBwdArgs()
+        a.dy, a.z, a.mean, a.invstd, a.gamma = dy.data_ptr(), z.data_ptr(), self.mean.data_ptr(), self.invstd.data_ptr(), bn.weight.data_ptr()
+        a.dgamma, a.dbeta, a.g, a.ws, a.ws_floats = bn.weight.grad.data_ptr(), bn.bias.grad.data_ptr(), g.data_ptr(), ws.data_ptr(), ws.numel()
+        a.P, a.C, a.z_cstride, a.dy_cstride, a.dy_coff, a.g_cstride = P, self.Cout, z.shape[3], dy_stride, dy_coff, g_stride
+        a.slope, a.p_drop, a.layer, a.key = LEAKY_SLOPE, self.p_drop, layer, key
+        _lib.call('cdnet_slice_bn_train_backward', C.byref(a), _lib.stream_ptr())
+
+    def weight_grad(self, x, x_stride, g, g_stride, N, H, W, ws):
+        a = _lib.DilatedWgradArgs()
+        a.x, a.g, a.dw, a.ws, a.ws_bytes = x.data_ptr(), g.data_ptr(), self.conv.weight.grad.data_ptr(), ws.data_ptr(), ws.numel() * 4
+        a.N, a.H, a.W, a.Cin, a.x_cstride, a.Cout, a.g_cstride = N, H, W, self.Cin, x_stride, self.Cout, g_stride
+        a.taps, a.dilation = self.taps, self.dilation
+        _lib.call('cdnet_dilated_conv_backward_weight', C.byref(a), _lib.stream_ptr())
+
+    def backward_data(self, g, g_stride, dx, dx_stride, N, H, W, accumulate):
+        a = _lib.DilatedBwdDataArgs()
+        a.g, a.w, a.dx = g.data_ptr(), self.wpb.data_ptr(), dx.data_ptr()
+        a.N, a.H, a.W, a.Cout, a.g_cstride, a.Cin, a.dx_cstride, a.dx_coff = N, H, W, self.Cout, g_stride, self.Cin, dx_stride, 0
+        a.taps, a.dilation, a.accumulate, a.f32 = self.taps, self.dilation, int(accumulate), 1
+        _lib.call('cdnet_dilated_conv_backward_data', C.byref(a), _lib.stream_ptr())
 
     def run(self, src, src_stride, dst, dst_stride, dst_coff, N, H, W, nchw=False):
         a = _lib.DilatedConvArgs()
@@ -154,7 +215,10 @@ class FullNet(nn.Module):
         for i in range(self.n_blocks):
             block = getattr(self.blocks, 'block%d' % (i + 1))
             blocks.append(([[cl(c) for c in layer.convs()] for layer in block], cl(getattr(self.blocks, 'trans%d' % (i + 1)))))
+            for layer, convs in zip(block, blocks[-1][0]):
+                convs[-1].p_drop = float(layer.drop_rate)              # :33-35, :49-51: dropout on the appended channels only
         self._rt = (cl(self.conv1), blocks, _Conv(self.conv2, None, False))
+        self._rt[0].needs_dx = False
 
     def _convs(self):
         stem, blocks, final = self._rt
@@ -176,7 +240,7 @@ class FullNet(nn.Module):
         """forward on packed NHWC windows [N,H,W,16] (color_channels real channels; bf16, or fp32 in the fp32 precision mode).  Returns `(logits,)`
         with logits f32 [N,K,H,W].  The batch runs in sub-batches whose block buffers stay under WORKSPACE_BYTES; a window's result does not
         depend on the batch it ran in."""
-        if self.training:
+        if self.training and runtime.TAPE is None:
             raise RuntimeError('FullNet is inference only here: call model.eval() first (training FullNet is not implemented)')
         if not x16.is_cuda:
             raise RuntimeError('cdnet_amd.models.FullNet.FullNet runs on the MI355X only (no CPU fallback)')
@@ -184,6 +248,8 @@ class FullNet(nn.Module):
         assert self.color_channels <= 16
         if self._rt is None:
             self._build_runtime()
+        if self.training:
+            return (self._train_forward(x16),)
         for c in self._convs():
             c.prepare(x16.device)
         N, H, W, _ = x16.shape
@@ -217,3 +283,116 @@ class FullNet(nn.Module):
             trans.run(cur, cs, nxt, nxt.shape[3], 0, N, H, W)
             cur = nxt
         final.run(cur, cur.shape[3], out, 0, 0, N, H, W, nchw=True)
+
+    # ------------------------------------------------------------------------------------------------
+    # training (fp32 precision mode): forward with a record for backward, and the backward walk
+    def _ws(self, name, need, device):
+        """grow-only fp32 workspace of the training kernels"""
+        wss = self.__dict__.setdefault('_train_ws', {})
+        ws = wss.get(name)
+        if ws is None or ws.numel() < need or ws.device != device:
+            ws = wss[name] = torch.empty((max(need, 1),), dtype=torch.float32, device=device)
+        return ws
+
+    def _train_forward(self, x16):
+        if runtime.PRECISION != 'fp32':
+            raise NotImplementedError('FullNet trains in the fp32 precision mode only (runtime.set_precision("fp32"))')
+        stem, blocks, final = self._rt
+        convs = self._convs()
+        index = {id(c): k for k, c in enumerate(convs)}
+        N, H, W, _ = x16.shape
+        P, dev = N * H * W, x16.device
+        lib = _lib.load()
+        for c in convs:
+            c.prepare_train(dev)
+        ws = self._ws('bn', max(lib.cdnet_slice_bn_workspace_floats(P, c.Cout) for c in convs), dev)
+        rec = TrainRecord(x16, (N, H, W), int(getattr(self, '_train_key', 0)), index)
+
+        def buf(c):
+            return torch.empty((N, H, W, _round8(c)), dtype=torch.float32, device=dev)
+
+        def conv_bn(c, src, ss, dst, ds, coff):
+            z = buf(c.Cout)
+            c.run(src, ss, z, z.shape[3], 0, N, H, W)             # (prepare_train left no scale / shift: the LeakyReLU output)
+            c.bn_forward(z, dst, ds, coff, P, index[id(c)], rec.key, ws)
+            rec.z[id(c)] = z
+            if c.p_drop > 0:
+                rec.drops.append((index[id(c)], (N, H, W, c.Cout), c.p_drop))
+        cur = buf(blocks[0][1].Cin)
+        conv_bn(stem, x16, 16, cur, cur.shape[3], 0)
+        for i, (layers, trans) in enumerate(blocks):
+            cs = cur.shape[3]
+            rec.bufs.append(cur)
+            for layer in layers:
+                if len(layer) == 1:
+                    conv_bn(layer[0], cur, cs, cur, cs, layer[0].Cin)
+                else:
+                    mid = buf(layer[0].Cout)
+                    conv_bn(layer[0], cur, cs, mid, mid.shape[3], 0)
+                    conv_bn(layer[1], mid, mid.shape[3], cur, cs, layer[0].Cin)
+                    rec.mids[id(layer[0])] = mid
+            nxt = buf(blocks[i + 1][1].Cin if i + 1 < len(blocks) else final.Cin)
+            conv_bn(trans, cur, cs, nxt, nxt.shape[3], 0)
+            cur = nxt
+        rec.bufs.append(cur)
+        out = torch.empty((N, self.output_channels, H, W), dtype=torch.float32, device=dev)
+        final.run(cur, cur.shape[3], out, 0, 0, N, H, W, nchw=True)
+        runtime.TAPE.append(rec)
+        return out
+
+    def train_backward(self, rec, dlogits):
+        """gradients of every parameter (into their views of the flat gradient buffer) from dlogits f32 [N,K,H,W]"""
+        stem, blocks, final = self._rt
+        N, H, W = rec.shape
+        P, dev, key, index = N * H * W, dlogits.device, rec.key, rec.index
+        lib = _lib.load()
+        convs = self._convs()
+        ws = self._ws('bn', max(lib.cdnet_slice_bn_workspace_floats(P, c.Cout) for c in convs), dev)
+        wws = self._ws('wgrad', max(lib.cdnet_dilated_wgrad_workspace_bytes(N, H, W, c.Cin, c.Cout, c.taps) for c in convs) // 4, dev)
+        gmax = max(_round8(c.Cout) for c in convs)
+        gflat = self._ws('g', P * gmax, dev)                      # g, the gradient of a raw convolution output: one compact scratch
+
+        def bn_back(c, dy, dy_stride, dy_coff):
+            gs = _round8(c.Cout)
+            c.bn_backward(dy, dy_stride, dy_coff, rec.z[id(c)], gflat, gs, P, index[id(c)], key, ws)
+            return gs
+        dl = runtime.input_pack(dlogits)                          # [N,H,W,16] fp32
+        last = rec.bufs[-1]
+        final.weight_grad(last, last.shape[3], dl, 16, N, H, W, wws)
+        dB = torch.empty_like(last)
+        final.backward_data(dl, 16, dB, dB.shape[3], N, H, W, False)
+        for i in reversed(range(len(blocks))):
+            layers, trans = blocks[i]
+            cur = rec.bufs[i]
+            cs = cur.shape[3]
+            gs = bn_back(trans, dB, dB.shape[3], 0)
+            trans.weight_grad(cur, cs, gflat, gs, N, H, W, wws)
+            dcur = torch.empty_like(cur)
+            trans.backward_data(gflat, gs, dcur, cs, N, H, W, False)          # stores every channel of the block's gradient buffer
+            for layer in reversed(layers):
+                coff = layer[0].Cin
+                gs = bn_back(layer[-1], dcur, cs, coff)                      # this layer's slice is complete: the later layers ran
+                if len(layer) == 1:
+                    layer[0].weight_grad(cur, cs, gflat, gs, N, H, W, wws)
+                    layer[0].backward_data(gflat, gs, dcur, cs, N, H, W, True)
+                else:
+                    mid = rec.mids[id(layer[0])]
+                    ms = mid.shape[3]
+                    layer[1].weight_grad(mid, ms, gflat, gs, N, H, W, wws)
+                    dmid = torch.empty_like(mid)
+                    layer[1].backward_data(gflat, gs, dmid, ms, N, H, W, False)
+                    gs = bn_back(layer[0], dmid, ms, 0)
+                    layer[0].weight_grad(cur, cs, gflat, gs, N, H, W, wws)
+                    layer[0].backward_data(gflat, gs, dcur, cs, N, H, W, True)
+            dB = dcur
+        gs = bn_back(stem, dB, dB.shape[3], 0)
+        stem.weight_grad(rec.x16, 16, gflat, gs, N, H, W, wws)
+
+
+class TrainRecord:
+    """what a training forward keeps for backward: the packed input, the block buffers, every z, the bottlenecks' intermediates"""
+
+    def __init__(self, x16, shape, key, index):
+        self.x16, self.shape, self.key, self.index = x16, shape, key, index
+        self.bufs, self.z, self.mids = [], {}, {}
+        self.drops = []                        # (layer index, [N,H,W,C], p) of every dropout applied: cdnet_dropout_mask regenerates its mask

@@ -109,7 +109,7 @@ def main(argv=None):
     torch.manual_seed(opt.train['seed'])                   # train.py:75-81 (same seed on every rank = same initial weights)
     np.random.seed(opt.train['seed'])
     model = utils.chooseModel(opt).to(dev)
-    plain_unet = opt.model['modelName'] == 'UNet'
+    plain_unet = opt.model['modelName'] in ('UNet', 'FullNet')        # a mask-only network: train_util's loop and scores
     trainer, scheduler = utils.get_optimizer(opt, model, world_size=world)       # train.py:191 (the plain UNet's trainer too)
     best_iou, best_loss = 0.0, float('inf')
     if opt.train['checkpoint']:                            # train.py:293-306: resume (weights, Adam moments, epoch, best values)

@@ -945,6 +945,32 @@ class UNetTrainer(Trainer):
         return self.unet_losses
 
 
+class FullNetTrainer(UNetTrainer):
+    """Train iteration of FullNet (models/FullNet.py through train_util.train): the plain UNet's loss, optimiser, all-reduce and checkpoint
+    entry around the network's own training forward and backward (models/FullNet.py: _train_forward / train_backward on csrc/dilated.hip and
+    csrc/dilated_train.hip).  fp32 precision mode only; one stream, the gradients reduced after backward (bucketed_allreduce).
+    The dropout masks are a hash of (seed, optimiser steps taken so far, layer, element): `seed` is opt.train['seed'] + rank."""
+
+    def __init__(self, model, seed=0, **kw):
+        if runtime.PRECISION != 'fp32':
+            raise NotImplementedError('FullNet trains in the fp32 precision mode only (CDNET_PRECISION=fp32 / runtime.set_precision("fp32")); '
+                                      'bf16-mode training is not built')
+        super().__init__(model, **kw)
+        self.seed = int(seed)
+
+    def dropout_key(self):
+        """the 64-bit key of this step's masks (cdnet_dropout_mask)"""
+        return ((self.seed & 0xffffffff) << 32) | (self.flat.step_count & 0xffffffff)
+
+    def forward(self, x):
+        self.model._train_key = self.dropout_key()
+        return super().forward(x)
+
+    def backward(self, dlogits):
+        self._ar = None                                    # (no overlap: allreduce_and_step reduces the whole buffer behind backward)
+        self.model.train_backward(self.tape[-1], dlogits)
+
+
 class AblationTrainer(Trainer):
     """Train iteration of the ablation heads (models/dam/model_unet_MandD.py / model_unet_MandDandP.py through
     train_util_dam.train, which unpacks the model's outputs by their number, :152-166): the same five-term loss - without the point

@@ -7,6 +7,8 @@
   adjust_learning_rate                                 utils.py:965-977
 """
 
+import os
+
 import numpy as np
 import torch
 
@@ -160,11 +162,14 @@ class AverageMeter(object):
 
 def trainer_class(model):
     """the Trainer that serves `model`: the plain UNet's (one mask output), the ablation heads' (plain classifiers instead of the gated
-    head, model_unet_MandD / model_unet_MandDandP), the DAM networks'"""
+    head, model_unet_MandD / model_unet_MandDandP), FullNet's (the UNet's loss around its own tape), the DAM networks'"""
     from .models.unet import UNet
-    from .trainer import Trainer, AblationTrainer, UNetTrainer
+    from .models.FullNet import FullNet
+    from .trainer import Trainer, AblationTrainer, FullNetTrainer, UNetTrainer
     if isinstance(model, UNet):
         return UNetTrainer
+    if isinstance(model, FullNet):
+        return FullNetTrainer
     return AblationTrainer if getattr(model, 'VARIANT', 'rev1') != 'rev1' else Trainer
 
 
@@ -212,6 +217,8 @@ def get_optimizer(args, model, world_size=1):
         raise ValueError('Optimizer {} not available'.format(args.train['optimizer']))
     trainer = trainer_class(model)(model, lr=args.train['lr'], weight_decay=args.train['weight_decay'], world_size=world_size,
                                    optimizer=name, momentum=getattr(args, 'momentum', 0.95))
+    if hasattr(trainer, 'seed'):                                  # FullNetTrainer: the dropout masks follow --seed and the rank
+        trainer.seed = int(args.train.get('seed', 0)) + int(os.environ.get('RANK', '0'))
     trainer.alpha = float(args.train.get('alpha', 0.0))           # 1: + the instance variance term (train_util_dam.py:174-180)
     trainer.boundary = boundary                                   # 1 / 2 / 3: + the boundary / focal term (train_util_dam.py:195-205)
     trainer.dice, trainer.weight_map = dice, weight_map           # --dice 0|1|2, --weight-map 0|1 (train_util.py:134-136, 183-190)

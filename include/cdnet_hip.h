@@ -384,6 +384,99 @@ int cdnet_dilated_pack_weights(const float *w, void *packed, int Cin, int Cout, 
 int cdnet_dilated_conv_forward(const cdnet_dilated_conv_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * FullNet training (dilated.hip, dilated_train.hip): the backward of a ConvLayer (models/FullNet.py:14-21 in train(): Conv2d(dilation) ->
+ * LeakyReLU(inplace) -> BatchNorm2d on batch statistics) and of the dense layers' dropout + torch.cat (:25-52), which autograd derives in
+ * the reference (train_util.py:193-195 loss.backward()).  With g the gradient of the raw convolution output c:
+ *
+ *   dx[n][y][x][dx_coff + ci] (+)= sum_{ky,kx,co<Cout} w[co][ci][ky][kx] * g[n][y - (ky-1) d][x - (kx-1) d][co]          zero outside the image
+ *   dW[co][ci][ky][kx]          = sum_{n,y,x}          g[n][y][x][co]    * x[n][y + (ky-1) d][x + (kx-1) d][ci]          zero outside the image
+ *
+ * Every entry finds its argument errors (CDNET_E_ARG: a null pointer, taps not 1 or 9, dilation < 1, a count < 1, a stride below its
+ * channel count or no multiple of 8 where a 32-byte loader reads it, an accumulate target that overlaps the source, a short workspace)
+ * before any HIP call. */
+
+/* backward-data: the forward kernel with the roles swapped (GEMM-K = Cout x taps, GEMM-N = Cin) over the pack w'[ci][co][8 - tap] of
+ * cdnet_dilated_pack_weights_bwd (cdnet_dilated_packed_weight_elems(Cout, Cin, taps, f32) elements).  accumulate = 0 stores channels
+ * [dx_coff, dx_coff + Cin) of dx, accumulate = 1 adds to them (one read-modify-write per element by one lane: deterministic); no other
+ * channel of dx is touched.  g and dx may be the same tensor only when [0, Cout) and [dx_coff, dx_coff + Cin) are disjoint and the strides
+ * are equal.  g_cstride is a multiple of 8; any Cin, Cout, dilation >= 1; f32 as in cdnet_dilated_conv_args. */
+typedef struct cdnet_dilated_bwd_data_args {
+    const void *g;           /* [N][H][W][g_cstride], channels [0, Cout) */
+    const void *w;           /* cdnet_dilated_pack_weights_bwd */
+    void *dx;                /* [N][H][W][dx_cstride] */
+    int N, H, W;
+    int Cout, g_cstride;
+    int Cin, dx_cstride, dx_coff;
+    int taps, dilation;
+    int accumulate;
+    int f32;
+} cdnet_dilated_bwd_data_args;
+int cdnet_dilated_pack_weights_bwd(const float *w, void *packed, int Cin, int Cout, int taps, int f32, void *stream);
+int cdnet_dilated_conv_backward_data(const cdnet_dilated_bwd_data_args *args, void *stream);
+
+/* weight gradient, fp32 mode: dw fp32 [Cout][Cin][taps] in torch's layout (the parameter's view of the flat gradient buffer), stored.
+ * x is read at its channel stride (the block buffer with Cin of its channels), g compact; both strides are multiples of 8 and channels
+ * >= Cin / >= Cout are selected to zero, never multiplied.  The pixels are reduced on the matrix cores (both operands split into bf16
+ * hi / lo on load, a_lo b_hi + a_hi b_lo + a_hi b_hi as in conv32.hip) into split-K slabs in `ws`, then summed in slab order by a second
+ * launch: no floating-point atomics, two runs give the same bits.  ws_bytes >= cdnet_dilated_wgrad_workspace_bytes of the same shape. */
+typedef struct cdnet_dilated_wgrad_args {
+    const float *x;          /* [N][H][W][x_cstride], channels [0, Cin) */
+    const float *g;          /* [N][H][W][g_cstride], channels [0, Cout) */
+    float *dw;               /* [Cout][Cin][taps] */
+    void *ws;
+    size_t ws_bytes;
+    int N, H, W;
+    int Cin, x_cstride;
+    int Cout, g_cstride;
+    int taps, dilation;
+} cdnet_dilated_wgrad_args;
+size_t cdnet_dilated_wgrad_workspace_bytes(int N, int H, int W, int Cin, int Cout, int taps);
+int cdnet_dilated_conv_backward_weight(const cdnet_dilated_wgrad_args *args, void *stream);
+
+/* BatchNorm2d in train() behind the LeakyReLU, plus F.dropout(training=True) of a dense layer's output (:33-35, :49-51), written into a
+ * channel slice.  z fp32 [P][z_cstride] is the stored LeakyReLU output (P = N H W pixels, C real channels).
+ *   forward:  per-tile sums [T][2][C] -> cdnet_bn_finalize_train (mean, invstd saved; running statistics with momentum and the unbiased
+ *             variance) -> out[p][out_coff + c] = ((z - mean) invstd gamma + beta) m / (1 - p_drop)
+ *   backward: dyh = dy m / (1 - p_drop); dbeta = sum dyh, dgamma = sum dyh xhat (per-tile sums, fixed tree with an fp64 top, stored);
+ *             g[p][c] = gamma invstd (dyh - dbeta / P - xhat dgamma / P) * (z > 0 ? 1 : slope), compact at g_cstride
+ * m is cdnet_dropout_mask's bit of element p * C + c of (key, layer), regenerated, never stored; p_drop = 0 skips the step exactly.
+ * ws_floats >= cdnet_slice_bn_workspace_floats(P, C).  Channels outside the slice are not touched. */
+typedef struct cdnet_slice_bn_fwd_args {
+    const float *z;
+    float *out;              /* [P][out_cstride] */
+    const float *gamma, *beta;
+    float *running_mean, *running_var;       /* [C], updated in place (both NULL: not tracked) */
+    float *mean, *invstd;    /* [C] saved for backward */
+    float *ws;
+    size_t ws_floats;
+    long long P;
+    int C, z_cstride, out_cstride, out_coff;
+    float eps, momentum, p_drop;
+    int layer;
+    unsigned long long key;
+} cdnet_slice_bn_fwd_args;
+typedef struct cdnet_slice_bn_bwd_args {
+    const float *dy;         /* [P][dy_cstride], channels [dy_coff, dy_coff + C) */
+    const float *z;
+    const float *mean, *invstd, *gamma;
+    float *dgamma, *dbeta;   /* [C] */
+    float *g;                /* [P][g_cstride] */
+    float *ws;
+    size_t ws_floats;
+    long long P;
+    int C, z_cstride, dy_cstride, dy_coff, g_cstride;
+    float slope, p_drop;
+    int layer;
+    unsigned long long key;
+} cdnet_slice_bn_bwd_args;
+size_t cdnet_slice_bn_workspace_floats(long long P, int C);
+int cdnet_slice_bn_train_forward(const cdnet_slice_bn_fwd_args *args, void *stream);
+int cdnet_slice_bn_train_backward(const cdnet_slice_bn_bwd_args *args, void *stream);
+/* mask[i] = 1 where element i of (key, layer) is kept, i < count: a counter-based hash (two rounds of splitmix64's finaliser over key,
+ * layer and i; the upper 24 bits against p_drop * 2^24), independent of the launch geometry.  0 <= p_drop < 1. */
+int cdnet_dropout_mask(unsigned long long key, int layer, size_t count, float p_drop, uint8_t *mask, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * Model-path streaming kernels (not convolutions).
  * cdnet_input_pack: f32 NCHW [N][C<=16][H][W] (the ToTensor output, my_transforms_direction.py:945) -> bf16 NHWC
  *   [N][H][W][16] with zero-padded channels.

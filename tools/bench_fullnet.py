@@ -1,6 +1,7 @@
 """FullNet inference (cdnet_amd/models/FullNet.py on csrc/dilated.hip) against the same network as plain PyTorch modules, one process, one GPU.
 
     python tools/bench_fullnet.py [--windows 64] [--size 256] [--reps 5] [--warmup 2] [--layer-reps 20] [--skip-torch] [--only-layers]
+    python tools/bench_fullnet.py --train [--batch 8] [--size 256] [--reps 5] [--warmup 2] [--skip-torch]
 
 1. Eval forward of --windows windows of --size^2 through FullNet(3, 3).forward_packed, in both precision modes (device events, median).
 2. The same network run through the model's own nn containers (Conv2d -> LeakyReLU -> BatchNorm2d, torch.cat), fp32 and bf16
@@ -8,6 +9,12 @@
 3. Single layers on --windows windows: a dense layer 168 -> 24 at d = 1 and at d = 21 (appending in place into a 168-channel buffer), the
    286 -> 143 transition; ours against F.conv2d + leaky_relu + affine on channels_last tensors.  `must_bytes` is what the layer has to
    move at least: every input channel read once, every output channel written once, the weights once; `GBps` = must_bytes / time.
+--train: one training step (forward + loss + backward + Adam) of FullNet(3, 3) on --batch tiles, fp32 precision mode, through
+trainer.FullNetTrainer against the same network as plain PyTorch modules (fp32, eager, channels_last, F.dropout, the oracle's loss,
+torch.optim.Adam) in the same process: device events, the two paths alternating run by run, medians.  Then one step with events around
+every library call: per entry point the calls, the time, its share, the bytes the calls must move at least (operands read once, results
+written once; an accumulating backward-data reads its target too; the BatchNorm passes count z and dy once although they read them twice)
+and the rate that makes.
 One JSON line per measurement."""
 import argparse
 import ctypes as C
@@ -53,6 +60,132 @@ def torch_forward(model, x):
                 y = c(y)
             out = torch.cat([out, y], 1)
     return model.conv2(out)
+
+
+def torch_train_forward(model, x):
+    """the reference's forward in train() (models/FullNet.py:25-52, :134-138): dropout on what a dense layer appends"""
+    out = model.conv1(x)
+    for name, mod in model.blocks.named_children():
+        if name.startswith('trans'):
+            out = mod(out)
+            continue
+        for layer in mod:
+            y = out
+            for c in layer.convs():
+                y = c(y)
+            if layer.drop_rate > 0:
+                y = F.dropout(y, p=layer.drop_rate, training=True)
+            out = torch.cat([out, y], 1)
+    return model.conv2(out)
+
+
+def _must_bytes(name, a):
+    """bytes a call has to move at least, from its argument struct (None: not one of the training kernels)"""
+    if name == 'cdnet_dilated_conv_forward':
+        return a.N * a.H * a.W * (a.Cin + a.Cout) * 4 + a.Cin * a.Cout * a.taps * 4
+    if name == 'cdnet_dilated_conv_backward_data':
+        return a.N * a.H * a.W * (a.Cout + a.Cin * (2 if a.accumulate else 1)) * 4 + a.Cin * a.Cout * a.taps * 4
+    if name == 'cdnet_dilated_conv_backward_weight':
+        return a.N * a.H * a.W * (a.Cin + a.Cout) * 4 + a.Cin * a.Cout * a.taps * 4
+    if name == 'cdnet_slice_bn_train_forward':
+        return a.P * a.C * 2 * 4
+    if name == 'cdnet_slice_bn_train_backward':
+        return a.P * a.C * 3 * 4
+    return None
+
+
+def kernel_table(step):
+    """one step with events around every library call: per entry point calls, time, share, must-move bytes and the rate"""
+    from cdnet_amd import _lib
+    rows, real = [], _lib.call
+
+    def timed(name, *a):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        real(name, *a)
+        e1.record()
+        rows.append((name, _must_bytes(name, getattr(a[0], '_obj', None)) if a else None, e0, e1))
+    _lib.call = timed
+    try:
+        step()
+        torch.cuda.synchronize()
+    finally:
+        _lib.call = real
+    total = sum(e0.elapsed_time(e1) for _, _, e0, e1 in rows)
+    table = {}
+    for name, must, e0, e1 in rows:
+        t = table.setdefault(name, [0, 0.0, 0])
+        t[0] += 1
+        t[1] += e0.elapsed_time(e1)
+        t[2] += must or 0
+    for name, (calls, ms, must) in sorted(table.items(), key=lambda kv: -kv[1][1]):
+        say(what='fullnet_train_kernels', entry=name, calls=calls, ms=round(ms, 3), share=round(ms / total, 3),
+            must_bytes=must or None, GBps=round(must / ms / 1e6, 1) if must else None)
+    say(what='fullnet_train_kernels', entry='all library calls', calls=len(rows), ms=round(total, 3))
+
+
+def bench_train(args):
+    import cdnet_amd
+    import _fullnet_ref as fr
+    import _fullnet_train_ref as tr
+    from oracle import train as ot
+    from cdnet_amd.models.FullNet import FullNet
+    from cdnet_amd.trainer import FullNetTrainer
+    cdnet_amd.set_precision('fp32')
+    B, S = args.batch, args.size
+    x, label, weight = (v.cuda() for v in tr.batch((B, 3, S, S), 5))
+    ours = FullNetTrainer(fr.randomize(FullNet(3, 3), 1).cuda(), seed=1)
+    step_ours = lambda: ours.train_step(x, label, weight)
+    step_torch = None
+    if not args.skip_torch:
+        m = fr.randomize(FullNet(3, 3), 1).cuda().train().to(memory_format=torch.channels_last)
+        opt = torch.optim.Adam(m.parameters(), lr=1e-3, betas=(0.9, 0.99), weight_decay=1e-4)
+        xt = x.contiguous(memory_format=torch.channels_last)
+
+        def step_torch():
+            opt.zero_grad(set_to_none=True)
+            loss = ot.unet_losses(torch_train_forward(m, xt), label, weight)['total']
+            loss.backward()
+            opt.step()
+    for _ in range(args.warmup):
+        step_ours()
+    torch.cuda.synchronize()
+    say(what='fullnet_train_step', path='hip', note='alone, before the PyTorch path is warm', ms=round(events(step_ours, args.reps, 0), 3))
+    kernel_table(step_ours)
+    if step_torch:
+        # the first PyTorch step builds MIOpen's kernels for ~150 (layer, direction) pairs: say where it is
+        from cdnet_amd.models.FullNet import ConvLayer
+
+        def progress(name):
+            def hook(_mod, _inp, out):
+                say(what='warmup', path='torch', forward=name)
+                out.register_hook(lambda _g: say(what='warmup', path='torch', backward_reaches=name))
+            return hook
+        hooks = [mod.register_forward_hook(progress(name)) for name, mod in m.named_modules() if isinstance(mod, ConvLayer)]
+        step_torch()
+        torch.cuda.synchronize()
+        for h in hooks:
+            h.remove()
+        for _ in range(1, args.warmup):
+            step_torch()
+        torch.cuda.synchronize()
+    times = {'hip': [], 'torch': []}
+    for _ in range(args.reps):                       # alternating: both paths see the same clocks and the same neighbours
+        for path, f in (('hip', step_ours), ('torch', step_torch)):
+            if f is None:
+                continue
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            f()
+            e1.record()
+            torch.cuda.synchronize()
+            times[path].append(e0.elapsed_time(e1))
+    med = {k: statistics.median(v) for k, v in times.items() if v}
+    for k, v in med.items():
+        say(what='fullnet_train_step', path=k, precision='fp32', batch=B, size=S, ms=round(v, 3), tiles_per_s=round(B / v * 1e3, 1),
+            runs=[round(t, 2) for t in times[k]])
+    if 'torch' in med:
+        say(what='fullnet_train_step', hip_over_torch_time=round(med['hip'] / med['torch'], 3))
 
 
 def bench_network(args):
@@ -142,10 +275,15 @@ def main():
     ap.add_argument('--layer-reps', type=int, default=20)
     ap.add_argument('--skip-torch', action='store_true')
     ap.add_argument('--only-layers', action='store_true')
+    ap.add_argument('--train', action='store_true', help='time one training step instead (fp32 mode)')
+    ap.add_argument('--batch', type=int, default=8)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('tools/bench_fullnet.py needs the GPU: a time measured elsewhere says nothing about it')
     say(what='device', name=torch.cuda.get_device_name(0))
+    if args.train:
+        bench_train(args)
+        return
     bench_layers(args)
     if not args.only_layers:
         bench_network(args)
