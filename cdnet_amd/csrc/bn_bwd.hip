@@ -10,6 +10,7 @@
 //
 // Replaces loss.backward() (train_util_dam.py:307) for nn.BatchNorm2d / F.relu / the residual add / nn.MaxPool2d / F.pad.
 #include "train_util.h"
+#include "bn_sums.h"
 
 using namespace cdnet;
 
@@ -385,8 +386,6 @@ __global__ __launch_bounds__(256) void bn_bwd_flat_kernel(BnBwdArgs A) {
 
 // fp32 variants of the flat kernels: 4 channels per thread (one float4 per tensor and pixel), BN_U pixels in flight, plain
 // fp32 arithmetic (no 16-bit rounding of the activation); relu == 2 reads the mask from the stored output in `res`.
-typedef float bn_f32x4 __attribute__((ext_vector_type(4)));
-
 template <int NG, bool RES, bool APPLY>
 __global__ __launch_bounds__(256) void bn_bwd_flat32_kernel(BnBwdArgs A) {
     const int VPP = A.C / 4;
@@ -404,23 +403,23 @@ __global__ __launch_bounds__(256) void bn_bwd_flat32_kernel(BnBwdArgs A) {
     const float *raw = reinterpret_cast<const float *>(A.raw), *resp = reinterpret_cast<const float *>(A.res);
     float *draw = reinterpret_cast<float *>(A.draw), *dzo = reinterpret_cast<float *>(A.dz_out);
     for (unsigned p0 = first_pixel(ppb, VPP); p0 < npix; p0 += step * BN_U) {
-        bn_f32x4 x[BN_U], r[BN_U], g[BN_U][NG];
+        f32x4 x[BN_U], r[BN_U], g[BN_U][NG];
 #pragma unroll
         for (int u = 0; u < BN_U; ++u) {
             unsigned p = p0 + u * step;
             p = p < npix ? p : npix - 1;
             if (APPLY && A.rev) p = npix - 1 - p;
-            x[u] = *reinterpret_cast<const bn_f32x4 *>(raw + (size_t)p * A.C + c0);
-            if (RES) r[u] = *reinterpret_cast<const bn_f32x4 *>(resp + (size_t)p * A.C + c0);
+            x[u] = *reinterpret_cast<const f32x4 *>(raw + (size_t)p * A.C + c0);
+            if (RES) r[u] = *reinterpret_cast<const f32x4 *>(resp + (size_t)p * A.C + c0);
 #pragma unroll
             for (int k = 0; k < NG; ++k)
-                g[u][k] = *reinterpret_cast<const bn_f32x4 *>(reinterpret_cast<const float *>(A.gin[k].g) + (size_t)p * A.gin[k].cstride + A.gin[k].coff + c0);
+                g[u][k] = *reinterpret_cast<const f32x4 *>(reinterpret_cast<const float *>(A.gin[k].g) + (size_t)p * A.gin[k].cstride + A.gin[k].coff + c0);
         }
 #pragma unroll
         for (int u = 0; u < BN_U; ++u) {
             const unsigned p = p0 + u * step;
             const bool valid = p < npix;
-            bn_f32x4 o, z;
+            f32x4 o, z;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 float v = fmaf(x[u][j], sc[j], sh[j]);
@@ -435,12 +434,12 @@ __global__ __launch_bounds__(256) void bn_bwd_flat32_kernel(BnBwdArgs A) {
             }
             if (APPLY && valid) {
                 const unsigned pw = A.rev ? npix - 1 - p : p;
-                *reinterpret_cast<bn_f32x4 *>(draw + (size_t)pw * A.C + c0) = o;
-                if (RES) *reinterpret_cast<bn_f32x4 *>(dzo + (size_t)pw * A.C + c0) = z;
+                *reinterpret_cast<f32x4 *>(draw + (size_t)pw * A.C + c0) = o;
+                if (RES) *reinterpret_cast<f32x4 *>(dzo + (size_t)pw * A.C + c0) = z;
             }
             // the sums pass of a residual unit's bn2 already leaves dz (the 1x1 branch's gradient): the second pass then reads one
             // tensor instead of the NG gradient sources and the mask again (cdnet_bn_backward)
-            if (!APPLY && RES && dzo && valid) *reinterpret_cast<bn_f32x4 *>(dzo + (size_t)p * A.C + c0) = z;
+            if (!APPLY && RES && dzo && valid) *reinterpret_cast<f32x4 *>(dzo + (size_t)p * A.C + c0) = z;
         }
     }
     if (!APPLY) bn_write_partial<4>(A.partial, A.C, VPP, s1, s2);
@@ -476,7 +475,7 @@ __global__ __launch_bounds__(256) void bn_bwd_window32_kernel(BnBwdArgs A, int k
         const unsigned w = (APPLY && A.rev) ? nwin - 1 - w0 : w0;
         const unsigned n = w / (Hp * Wp), r = w - n * Hp * Wp;
         const unsigned py = r / Wp, px = r - py * Wp;
-        bn_f32x4 x[4], g[4][NF > 0 ? NF : 1], gv;
+        f32x4 x[4], g[4][NF > 0 ? NF : 1], gv;
         unsigned pix[4];
         bool ok[4];
 #pragma unroll
@@ -486,17 +485,17 @@ __global__ __launch_bounds__(256) void bn_bwd_window32_kernel(BnBwdArgs A, int k
             yy = yy < H ? yy : H - 1;
             xx = xx < W ? xx : W - 1;
             pix[q] = (n * H + yy) * W + xx;
-            x[q] = *reinterpret_cast<const bn_f32x4 *>(raw + (size_t)pix[q] * A.C + c0);
+            x[q] = *reinterpret_cast<const f32x4 *>(raw + (size_t)pix[q] * A.C + c0);
 #pragma unroll
             for (int m = 0; m < NF; ++m)
-                g[q][m] = *reinterpret_cast<const bn_f32x4 *>(gf[m] + (size_t)pix[q] * gcs[m] + gco[m] + c0);
+                g[q][m] = *reinterpret_cast<const f32x4 *>(gf[m] + (size_t)pix[q] * gcs[m] + gco[m] + c0);
         }
         const bool pok = py < (unsigned)gp.Hg && px < (unsigned)gp.Wg;
         {
             const unsigned cy = pok ? py : 0, cx = pok ? px : 0;
-            gv = *reinterpret_cast<const bn_f32x4 *>(gpool_p + (((size_t)n * gp.Hg + cy) * gp.Wg + cx) * gp.cstride + gp.coff + c0);
+            gv = *reinterpret_cast<const f32x4 *>(gpool_p + (((size_t)n * gp.Hg + cy) * gp.Wg + cx) * gp.cstride + gp.coff + c0);
         }
-        bn_f32x4 o[4];
+        f32x4 o[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float a[4];
@@ -529,7 +528,7 @@ __global__ __launch_bounds__(256) void bn_bwd_window32_kernel(BnBwdArgs A, int k
         if (APPLY) {
 #pragma unroll
             for (int q = 0; q < 4; ++q)
-                if (ok[q]) *reinterpret_cast<bn_f32x4 *>(draw + (size_t)pix[q] * A.C + c0) = o[q];
+                if (ok[q]) *reinterpret_cast<f32x4 *>(draw + (size_t)pix[q] * A.C + c0) = o[q];
         }
     }
     if (!APPLY) bn_write_partial<4>(A.partial, A.C, VPP, s1, s2);
@@ -589,20 +588,10 @@ __global__ __launch_bounds__(256) void bn_bwd_generic_kernel(BnBwdArgs A) {
 __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float *__restrict__ partial, int nb, int C, float M, const float *gamma,
                                                               const float *invstd, float *dgamma, float *dbeta, float *k1, float *k2,
                                                               float *k3) {
-    __shared__ double s_a[256], s_b[256];
     const int c = blockIdx.x;
-    const int lane = threadIdx.x;
-    double s1 = 0.0, s2 = 0.0;
-    for (int b = lane; b < nb; b += 256) { s1 += (double)partial[((size_t)b * 2) * C + c]; s2 += (double)partial[((size_t)b * 2 + 1) * C + c]; }
-    s_a[lane] = s1; s_b[lane] = s2;
-    __syncthreads();
-#pragma unroll
-    for (int o = 128; o > 0; o >>= 1) {
-        if (lane < o) { s_a[lane] += s_a[lane + o]; s_b[lane] += s_b[lane + o]; }
-        __syncthreads();
-    }
-    s1 = s_a[0]; s2 = s_b[0];
-    if (lane == 0) {
+    double s1, s2;
+    bn_sum_partials(partial, nb, C, c, s1, s2);
+    if (threadIdx.x == 0) {
         if (dbeta) dbeta[c] = (float)s1;
         if (dgamma) dgamma[c] = (float)s2;
         k1[c] = gamma[c] * invstd[c];

@@ -6,9 +6,9 @@
 //                    loop: the in-kernel clock the chip holds under matrix load = d(memtime) / d(memrealtime) x 100 MHz
 #include "common.h"
 #include "launch.h"
+#include "vec.h"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
+using namespace cdnet;
 
 namespace {
 

@@ -25,9 +25,6 @@
 
 using namespace cdnet;
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
 namespace {
 
 __device__ int g_dbg_dummy;
@@ -156,7 +153,7 @@ __global__ void pack_weights_batch_kernel(const PackDesc *__restrict__ table, in
 __device__ __forceinline__ V16 max8(V16 a, V16 b, bool nonneg) {
     V16 o;
     if (nonneg) {                                // post-ReLU values: integer order == float order
-        o.u = __builtin_bit_cast(uint4, xf_max_nonneg_bf8(__builtin_bit_cast(xf_u32x4, a.u), __builtin_bit_cast(xf_u32x4, b.u)));
+        o.u = __builtin_bit_cast(uint4, xf_max_nonneg_bf8(__builtin_bit_cast(u32x4, a.u), __builtin_bit_cast(u32x4, b.u)));
         return o;
     }
 #pragma unroll
@@ -614,7 +611,7 @@ __global__ __launch_bounds__(256, (BN <= 64 ? (CK == 16 && TH == 16 && CDNET_CON
         auto write_tile = [&](auto f16c) {
             constexpr bool F16 = decltype(f16c)::value;
             const bool odd = (l31 & 1) != 0;
-            const xf_s16x2 lo = A.orelu ? xf_s16x2{0, 0} : xf_s16x2{(short)-32768, (short)-32768};
+            const s16x2 lo = A.orelu ? s16x2{0, 0} : s16x2{(short)-32768, (short)-32768};
 #pragma unroll
             for (int ni = 0; ni < NPW; ++ni) {
                 const int col = (wn * NPW + ni) * 32 + l31;
@@ -632,10 +629,10 @@ __global__ __launch_bounds__(256, (BN <= 64 ? (CK == 16 && TH == 16 && CDNET_CON
                         const float v0 = fmaf(acc[mi][ni][r], osc, osh), v1 = fmaf(acc[mi][ni][r + 1], osc, osh);
                         const float send = odd ? v0 : v1;
                         const float got = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, send), 0xB1, 0xF, 0xF, true));
-                        const xf_f32x2 pr = {odd ? got : v0, odd ? v1 : got};      // (even column, odd column) of row m (+1 on odd lanes)
-                        xf_s16x2 pk;
-                        if (F16) pk = __builtin_bit_cast(xf_s16x2, __builtin_convertvector(pr, xf_h16x2));
-                        else pk = __builtin_bit_cast(xf_s16x2, __builtin_convertvector(pr, xf_bf16x2));
+                        const f32x2 pr = {odd ? got : v0, odd ? v1 : got};      // (even column, odd column) of row m (+1 on odd lanes)
+                        s16x2 pk;
+                        if (F16) pk = __builtin_bit_cast(s16x2, __builtin_convertvector(pr, h16x2));
+                        else pk = __builtin_bit_cast(s16x2, __builtin_convertvector(pr, bf16x2));
                         pk = __builtin_elementwise_max(pk, lo);
                         *reinterpret_cast<unsigned *>(dst + m * OSTR) = __builtin_bit_cast(unsigned, pk);
                     }
@@ -804,9 +801,6 @@ struct WsLds {
     }
 };
 
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));      // register staging type (HIP's uint4 struct copies defeat SROA)
-typedef short ws_s16x4 __attribute__((ext_vector_type(4)));
-
 // XF: input transform of every source, decided by the launcher - 0 plain bf16, 1 fp16 raw x scale + shift -> ReLU (training-mode
 // BatchNorm source, packed math), 2 anything (run-time flags).
 // STATS: per-tile channel sums of the unrounded accumulators.
@@ -887,7 +881,7 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(ConvArgs A) {
         constexpr int VPQ = 2 * VPP, NG = 2;
         const int slot = ptid % VPQ;
         const int khalf = slot & 1, c2 = slot >> 1;
-        u32x4v pa[PF][NA];
+        u32x4 pa[PF][NA];
         unsigned eo[PF][NA];                     // byte offsets of the requests (read again for a residual operand); bit 31 = zero fill
         // per-thread constants: halo coordinates and LDS offsets of its vectors
         int hyx[NG][NA], doff[NG][NA];
@@ -910,8 +904,8 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(ConvArgs A) {
         const __amdgpu_buffer_rsrc_t rsx1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short *>(A.nsrc > 1 ? A.src[1].x : A.src[0].x), 0, (int)src_bytes1, 0x00020000);
         const __amdgpu_buffer_rsrc_t rsr0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short *>(A.src[0].res ? A.src[0].res : A.src[0].x), 0, (int)src_bytes0, 0x00020000);
         const __amdgpu_buffer_rsrc_t rsr1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short *>(A.nsrc > 1 && A.src[1].res ? A.src[1].res : A.src[0].x), 0, (int)src_bytes1, 0x00020000);
-        auto bload = [](__amdgpu_buffer_rsrc_t r, unsigned voff) -> u32x4v {
-            return __builtin_bit_cast(u32x4v, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, 0, 0));
+        auto bload = [](__amdgpu_buffer_rsrc_t r, unsigned voff) -> u32x4 {
+            return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, 0, 0));
         };
         // bits [lo, hi) clear, everything else set (lo, hi clamped to [0, 31])
         auto bad_mask = [](int lo, int hi) -> unsigned {
@@ -991,7 +985,7 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(ConvArgs A) {
             unsigned char *dst0 = lds_a + ((R & 2) + c2) * L::A_BYTES;      // (this thread's vectors belong to chunk c2 of the pair, whichever set R is)
 #pragma unroll
             for (int i = 0; i < NA; ++i) {
-                u32x4v val;
+                u32x4 val;
                 if (XF == 0) val = pa[R][i];
                 else if (XF == 1) val = xf_bnrelu_f16<false>(pa[R][i], pa[R][i], sc, sh);
                 else {
@@ -1004,26 +998,26 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(ConvArgs A) {
                     const bool relu = s.relu != 0, f16 = s.f16 != 0;
                     if (s.res) {
                         rr.u = __builtin_bit_cast(uint4, bload(si ? rsr1 : rsr0, eo[R][i]));
-                        val = __builtin_bit_cast(u32x4v, xform8(raw, &rr, t, relu, f16).u);
+                        val = __builtin_bit_cast(u32x4, xform8(raw, &rr, t, relu, f16).u);
                     } else if (!t.on && !relu && !f16) val = pa[R][i];
-                    else val = __builtin_bit_cast(u32x4v, xform8(raw, nullptr, t, relu, f16).u);
+                    else val = __builtin_bit_cast(u32x4, xform8(raw, nullptr, t, relu, f16).u);
                 }
                 if (XF != 0) {                                   // (plain sources: the zero fill arrived as zeros)
                     const unsigned keep = (int)eo[R][i] < 0 ? 0u : 0xffffffffu;
                     val &= keep;
                 }
 #ifdef CDNET_WS_STAMPS
-                if (A.debug & 1024) { if (val[0] == 0x12345678u) *reinterpret_cast<u32x4v *>(dst0 + doff[G][i]) = val; continue; }
+                if (A.debug & 1024) { if (val[0] == 0x12345678u) *reinterpret_cast<u32x4 *>(dst0 + doff[G][i]) = val; continue; }
 #endif
                 if (ptid + (G * NA + i) * 256 < NPIX * VPQ)
-                    *reinterpret_cast<u32x4v *>(dst0 + doff[G][i]) = val;
+                    *reinterpret_cast<u32x4 *>(dst0 + doff[G][i]) = val;
             }
         };
         // ---- out path: mover wave w stores the region of consumer wave w.  Piece pc = (M tile mi, pixel half ch, cout pass kk): the four
         // ---- 16-lane groups take four cout octets, lane i of a group receives pixel i of tile row 4w + 2mi + ch (transposing read:
         // ---- lane 4q+p supplies the address of cout row q, pixels 4p..4p+3) -> one 16-byte NHWC store per lane
         constexpr int KO = BN / 32, NP = 4 * KO;
-        typedef ws_s16x4 __attribute__((address_space(3))) * lptr;
+        typedef s16x4 __attribute__((address_space(3))) * lptr;
         const int pw = wave - 4;
         const int lg = lane >> 4, li = lane & 15;
         const unsigned char *s_img = lds_o + pw * L::OUT_WAVE + (li >> 2) * L::IROW + (li & 3) * 8;
@@ -1031,7 +1025,7 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(ConvArgs A) {
             // all transposing reads first, into registers of their own, then the stores: with the pair of reads, the wait for them and
             // the store piece by piece through one register quad (what the compiler makes of a single loop) every piece paid the LDS
             // latency - 1.2 us per tile in the movers' second interval, where the consumers then waited 0.9 us (stamp build)
-            ws_s16x4 t1[NP], t2[NP];
+            s16x4 t1[NP], t2[NP];
 #pragma unroll
             for (int pc = 0; pc < NP; ++pc) {
                 const int mi = pc / (2 * KO), ch = (pc / KO) % 2, kk = pc % KO;
@@ -1157,11 +1151,11 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(ConvArgs A) {
 
     // ================================ consumers ================================
     if (!STREAM) {
-        const u32x4v *src = reinterpret_cast<const u32x4v *>(A.w + (size_t)cout_tile * 4 * (L::B_CHUNK / 2));
-        u32x4v *dst = reinterpret_cast<u32x4v *>(lds_w);
+        const u32x4 *src = reinterpret_cast<const u32x4 *>(A.w + (size_t)cout_tile * 4 * (L::B_CHUNK / 2));
+        u32x4 *dst = reinterpret_cast<u32x4 *>(lds_w);
         constexpr int nv = 4 * (L::B_CHUNK / 16), NW = (nv + 255) / 256;
         // all of a thread's vectors in flight at once (one memory round trip for the 74 KB; the accumulators are not live yet)
-        u32x4v wv[NW];
+        u32x4 wv[NW];
 #pragma unroll
         for (int i = 0; i < NW; ++i) wv[i] = src[tid + i * 256 < nv ? tid + i * 256 : 0];
 #pragma unroll
@@ -1196,7 +1190,7 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(ConvArgs A) {
         e_osh[ni] = fmaf((A.bias && cok) ? A.bias[co] : 0.f, e_osc[ni], (A.oshift && cok) ? A.oshift[co] : 0.f);
     }
     const bool f16out = A.out_f16 != 0;
-    const xf_s16x2 lo_clamp = A.orelu ? xf_s16x2{0, 0} : xf_s16x2{(short)-32768, (short)-32768};
+    const s16x2 lo_clamp = A.orelu ? s16x2{0, 0} : s16x2{(short)-32768, (short)-32768};
 
     // ---- epilogue units of a finished accumulator set (full tiles only).  Statistics: registers 4g..4g+3 of block (mi, ni) into the
     // ---- lane's running sums, blocks in the order (ni, mi) - the summation order of conv_fwd_kernel.  Image: bias/scale/shift,
@@ -1220,11 +1214,11 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(ConvArgs A) {
     auto img_unit = [&](const f32x16 (&P)[MPW][NPW], int u) {
         const int mi = u / (NPW * 4), ni = (u / 4) % NPW, g = u % 4;
         const float osc = e_osc[ni], osh = e_osh[ni];
-        const xf_f32x2 p0 = {fmaf(P[mi][ni][4 * g], osc, osh), fmaf(P[mi][ni][4 * g + 1], osc, osh)};
-        const xf_f32x2 p1 = {fmaf(P[mi][ni][4 * g + 2], osc, osh), fmaf(P[mi][ni][4 * g + 3], osc, osh)};
-        const xf_s16x2 h0 = __builtin_bit_cast(xf_s16x2, __builtin_convertvector(p0, xf_h16x2)), h1 = __builtin_bit_cast(xf_s16x2, __builtin_convertvector(p1, xf_h16x2));
-        const xf_s16x2 b0 = __builtin_bit_cast(xf_s16x2, __builtin_convertvector(p0, xf_bf16x2)), b1 = __builtin_bit_cast(xf_s16x2, __builtin_convertvector(p1, xf_bf16x2));
-        const xf_s16x2 k0 = __builtin_elementwise_max(f16out ? h0 : b0, lo_clamp), k1 = __builtin_elementwise_max(f16out ? h1 : b1, lo_clamp);
+        const f32x2 p0 = {fmaf(P[mi][ni][4 * g], osc, osh), fmaf(P[mi][ni][4 * g + 1], osc, osh)};
+        const f32x2 p1 = {fmaf(P[mi][ni][4 * g + 2], osc, osh), fmaf(P[mi][ni][4 * g + 3], osc, osh)};
+        const s16x2 h0 = __builtin_bit_cast(s16x2, __builtin_convertvector(p0, h16x2)), h1 = __builtin_bit_cast(s16x2, __builtin_convertvector(p1, h16x2));
+        const s16x2 b0 = __builtin_bit_cast(s16x2, __builtin_convertvector(p0, bf16x2)), b1 = __builtin_bit_cast(s16x2, __builtin_convertvector(p1, bf16x2));
+        const s16x2 k0 = __builtin_elementwise_max(f16out ? h0 : b0, lo_clamp), k1 = __builtin_elementwise_max(f16out ? h1 : b1, lo_clamp);
         *reinterpret_cast<uint2 *>(s_out + (mi * NPW + ni) * L::IBLK + g * 16) = make_uint2(__builtin_bit_cast(unsigned, k0), __builtin_bit_cast(unsigned, k1));
     };
     // slot sl (0 .. 2 * 36 - 1) of interval A -> unit: statistics on the even slots from 0, then the image on the odd slots

@@ -41,8 +41,6 @@
 
 using namespace cdnet;
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 
 #ifdef CDNET_WS_STAMPS
 // debug build only (CDNET_HIPCC_FLAGS=-DCDNET_WS_STAMPS, tools/ws16_stamps.py): wall-clock stamps (100 MHz) of consumer wave 0 and mover wave 4
@@ -177,7 +175,7 @@ __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
         constexpr int NG = PAIR ? 2 : 1;                          // register-set groups that share one lane -> (pixel, segment) map
         const int slot = ptid % VPQ;                              // this thread's 16-byte segment (PAIR: chunk slot >> 1 of the pair, k-half slot & 1)
         const int khalf = slot & 1, c2 = slot >> 1;
-        u32x4v pa[PF][NA];
+        u32x4 pa[PF][NA];
         unsigned eo[XF != 0 ? PF : 1][NA];       // byte offsets of the requests (read again for a residual operand); bit 31 = zero fill
         int hyx[NG][NA], doff[NG][NA];
 #pragma unroll
@@ -196,8 +194,8 @@ __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
         const __amdgpu_buffer_rsrc_t rsx1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short *>(A.nsrc > 1 ? A.src[1].x : A.src[0].x), 0, (int)src_bytes1, 0x00020000);
         const __amdgpu_buffer_rsrc_t rsr0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short *>(A.src[0].res ? A.src[0].res : A.src[0].x), 0, (int)src_bytes0, 0x00020000);
         const __amdgpu_buffer_rsrc_t rsr1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short *>(A.nsrc > 1 && A.src[1].res ? A.src[1].res : A.src[0].x), 0, (int)src_bytes1, 0x00020000);
-        auto bload = [](__amdgpu_buffer_rsrc_t r, unsigned voff) -> u32x4v {
-            return __builtin_bit_cast(u32x4v, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, 0, 0));
+        auto bload = [](__amdgpu_buffer_rsrc_t r, unsigned voff) -> u32x4 {
+            return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, 0, 0));
         };
         auto bad_mask = [](int lo, int hi) -> unsigned {
             lo = lo < 0 ? 0 : (lo > 31 ? 31 : lo);
@@ -273,7 +271,7 @@ __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
             unsigned char *dst0 = lds_a + (SB >= 0 ? SB + c2 : (PAIR ? ((R & 2) + c2) : (R & 3))) * A_BYTES;
 #pragma unroll
             for (int i = 0; i < NA; ++i) {
-                u32x4v val;
+                u32x4 val;
                 if (XF == 0) val = pa[R][i];
                 else {
                     ChanXf t;
@@ -285,14 +283,14 @@ __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
                     const bool relu = s.relu != 0, f16 = s.f16 != 0;
                     if (s.res) {
                         rr.u = __builtin_bit_cast(uint4, bload(si ? rsr1 : rsr0, eo[R][i]));
-                        val = __builtin_bit_cast(u32x4v, xform8(raw, &rr, t, relu, f16).u);
+                        val = __builtin_bit_cast(u32x4, xform8(raw, &rr, t, relu, f16).u);
                     } else if (!t.on && !relu && !f16) val = pa[R][i];
-                    else val = __builtin_bit_cast(u32x4v, xform8(raw, nullptr, t, relu, f16).u);
+                    else val = __builtin_bit_cast(u32x4, xform8(raw, nullptr, t, relu, f16).u);
                     const unsigned keep = (int)eo[R][i] < 0 ? 0u : 0xffffffffu;      // outside the image / source: zeros (after the transform)
                     val &= keep;
                 }
                 if (ptid + (G * NA + i) * NMV < NPIX * VPQ)
-                    *reinterpret_cast<u32x4v *>(dst0 + doff[G][i]) = val;
+                    *reinterpret_cast<u32x4 *>(dst0 + doff[G][i]) = val;
             }
         };
         auto commit = [&](auto rc, int c_) __attribute__((always_inline)) { commit3(rc, c_, std::integral_constant<int, -1>{}); };
@@ -350,16 +348,16 @@ __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
             constexpr int PPR = 64 / SPP, NR = 32 / PPR;         // pixels per wave-instruction, instructions per block
             const int seg = lane % SPP, lp = lane / SPP;
             const unsigned char *blk = lds_o + hf * L::OHALF + bw * L::OBLK + seg * 16;
-            u32x4v v[NR];
+            u32x4 v[NR];
 #pragma unroll
-            for (int r = 0; r < NR; ++r) v[r] = *reinterpret_cast<const u32x4v *>(blk + (r * PPR + lp) * L::OROW);
+            for (int r = 0; r < NR; ++r) v[r] = *reinterpret_cast<const u32x4 *>(blk + (r * PPR + lp) * L::OROW);
             const bool ok = cout0 + seg * 8 < A.Cout && !(A.debug & 8);
             if (A.out) {
 #pragma unroll
                 for (int r = 0; r < NR; ++r) {
                     const int px = r * PPR + lp;
                     unsigned short *dstp = A.out + (((size_t)tn * A.H + ty0 + bw * 4 + hf * 2 + (px >> 4)) * A.W + tx0 + (px & 15)) * A.out_cstride + A.out_coff + cout0 + seg * 8;
-                    if (ok) *reinterpret_cast<u32x4v *>(dstp) = v[r];
+                    if (ok) *reinterpret_cast<u32x4 *>(dstp) = v[r];
                 }
             }
             if (!STREAM && A.dot_out) {
@@ -368,7 +366,7 @@ __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
 #pragma unroll
                 for (int r = 0; r < NR; ++r) {
                     XfWords m;
-                    m.u = __builtin_bit_cast(xf_u32x4, v[r]);
+                    m.u = __builtin_bit_cast(u32x4, v[r]);
                     float sd = 0.f;
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
@@ -386,20 +384,20 @@ __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
                 // nn.MaxPool2d(2, 2) of the block's two rows beside the stores (torchvision VGG 'M' layers after a ReLU: the values are
                 // non-negative, their bf16 order is their int16 order): rows r and r + NR / 2 hold the same columns; the column partner of
                 // a pixel sits SPP lanes away.  The lanes of even columns store the block's 8 pooled pixels.
-                auto max4 = [](u32x4v a, u32x4v b) -> u32x4v {       // (xf_max_nonneg_bf8: element access through a union - xform.h)
-                    return __builtin_bit_cast(u32x4v, xf_max_nonneg_bf8(__builtin_bit_cast(xf_u32x4, a), __builtin_bit_cast(xf_u32x4, b)));
+                auto max4 = [](u32x4 a, u32x4 b) -> u32x4 {       // (xf_max_nonneg_bf8: element access through a union - xform.h)
+                    return __builtin_bit_cast(u32x4, xf_max_nonneg_bf8(__builtin_bit_cast(u32x4, a), __builtin_bit_cast(u32x4, b)));
                 };
                 const int Hp = A.H >> 1, Wp = A.W >> 1;
 #pragma unroll
                 for (int r = 0; r < NR / 2; ++r) {
                     XfWords m, o;
-                    m.u = __builtin_bit_cast(xf_u32x4, max4(v[r], v[r + NR / 2]));
+                    m.u = __builtin_bit_cast(u32x4, max4(v[r], v[r + NR / 2]));
 #pragma unroll
                     for (int k = 0; k < 4; ++k) o.w[k] = (unsigned)__shfl_xor((int)m.w[k], SPP);
                     m.u = xf_max_nonneg_bf8(m.u, o.u);
                     const int px = r * PPR + lp;                 // column of this lane's pixel inside the tile
                     unsigned short *dstp = A.pool_out + (((size_t)tn * Hp + ((ty0 + bw * 4 + hf * 2) >> 1)) * Wp + ((tx0 + px) >> 1)) * A.Cout + cout0 + seg * 8;
-                    if (ok && !(lp & 1)) *reinterpret_cast<u32x4v *>(dstp) = __builtin_bit_cast(u32x4v, m.u);
+                    if (ok && !(lp & 1)) *reinterpret_cast<u32x4 *>(dstp) = __builtin_bit_cast(u32x4, m.u);
                 }
             }
             }
@@ -554,11 +552,11 @@ __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
     // ================================ consumers ================================
     if (!STREAM) {
         // the resident weights of this output-channel tile: one contiguous block of the pack
-        const u32x4v *src = reinterpret_cast<const u32x4v *>(reinterpret_cast<const unsigned char *>(A.w) + (size_t)cout_tile * wres_bytes);
-        u32x4v *dst = reinterpret_cast<u32x4v *>(lds_w);
+        const u32x4 *src = reinterpret_cast<const u32x4 *>(reinterpret_cast<const unsigned char *>(A.w) + (size_t)cout_tile * wres_bytes);
+        u32x4 *dst = reinterpret_cast<u32x4 *>(lds_w);
         const int nv = wres_bytes / 16;
         for (int v0 = 0; v0 < nv; v0 += 256 * 8) {
-            u32x4v wv[8];
+            u32x4 wv[8];
 #pragma unroll
             for (int i = 0; i < 8; ++i) wv[i] = src[v0 + tid + i * 256 < nv ? v0 + tid + i * 256 : 0];
 #pragma unroll
@@ -572,7 +570,6 @@ __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
         // A = weights (16 output channels x 32 k), B = pixels (32 k x 16 pixels of one tile row), D: lane (pixel n = lane & 15, kg = lane >> 4)
         // holds output channels 4 kg .. 4 kg + 3 of the block.  K step s of a chunk pair: this lane's 8 k = k-block kb = 4 s + kg of the 36
         // (chunk, tap, channel half) blocks - the fragment addresses differ between the four lane groups and are kept per step.
-        typedef float f32x4a __attribute__((ext_vector_type(4)));
         constexpr int NCB = BN / 16, NPB = 4;                    // wave: NCB blocks of 16 output channels x the 4 tile rows 4 wm .. 4 wm + 3
         const int wm = wave, n16 = lane & 15, kg = lane >> 4;
         int PB9[9], WB9[9], PB1, WB1;                              // (pixel-fragment offsets for even tile rows; an odd row flips the k-half swizzle: ^ 16)
@@ -587,7 +584,7 @@ __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
             PB1 = c2 * A_BYTES + ((wm * 4 + 1) * HW_ + n16 + 1) * PSTR + ((ch ^ 1) * 16);
             WB1 = c2 * L::WCH1 + ch * BN * 16 + n16 * 16;
         }
-        f32x4a accA[NCB][NPB], accB[NCB][NPB], binit[NCB];
+        f32x4 accA[NCB][NPB], accB[NCB][NPB], binit[NCB];
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
@@ -595,21 +592,21 @@ __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
                 const int co = cout0 + cb * 16 + 4 * kg + r;
                 binit[cb][r] = co < A.Cout ? (A.bias ? A.bias[co] : 0.f) + (A.oshift ? A.oshift[co] : 0.f) : 0.f;
             }
-        const xf_s16x2 lo_clamp = A.orelu ? xf_s16x2{0, 0} : xf_s16x2{(short)-32768, (short)-32768};
+        const s16x2 lo_clamp = A.orelu ? s16x2{0, 0} : s16x2{(short)-32768, (short)-32768};
         unsigned char *const o_lane = lds_o + wave * L::OBLK + n16 * L::OROW + kg * 8;
         // epilogue of a finished set: unit u = (pb, cb) - 4 consecutive output channels of this lane's pixel in tile row pb - three
         // micro-operations: convert, ReLU clamp, one 8-byte write into the out image (half pb >> 1, pixel (pb & 1) * 16 + n)
         constexpr int NMO = NPB * NCB * 3;
         unsigned e0 = 0, e1 = 0;
-        auto micro = [&](const f32x4a (&P)[NCB][NPB], int e) {
+        auto micro = [&](const f32x4 (&P)[NCB][NPB], int e) {
             const int u = e / 3, k = e % 3, pb = u / NCB, cb = u % NCB;
             if (k == 0) {
-                const xf_f32x2 a = {P[cb][pb][0], P[cb][pb][1]}, b = {P[cb][pb][2], P[cb][pb][3]};
-                e0 = __builtin_bit_cast(unsigned, __builtin_convertvector(a, xf_bf16x2));
-                e1 = __builtin_bit_cast(unsigned, __builtin_convertvector(b, xf_bf16x2));
+                const f32x2 a = {P[cb][pb][0], P[cb][pb][1]}, b = {P[cb][pb][2], P[cb][pb][3]};
+                e0 = __builtin_bit_cast(unsigned, __builtin_convertvector(a, bf16x2));
+                e1 = __builtin_bit_cast(unsigned, __builtin_convertvector(b, bf16x2));
             } else if (k == 1) {
-                e0 = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(xf_s16x2, e0), lo_clamp));
-                e1 = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(xf_s16x2, e1), lo_clamp));
+                e0 = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, e0), lo_clamp));
+                e1 = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, e1), lo_clamp));
             } else {
                 *reinterpret_cast<uint2 *>(o_lane + (pb >> 1) * L::OHALF + (pb & 1) * 16 * L::OROW + cb * 32) = make_uint2(e0, e1);
             }
@@ -617,7 +614,7 @@ __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
         // one barrier interval = a pair of run chunks on accumulator set C: NT = 9 -> nine K steps of NCB x 4 MFMAs, NT = 1 -> one.
         // The fragments of a step are requested one step ahead (two sets).  FIRST: the tile starts from the bias.  EP of 2 (HP): the interval
         // carries that half (tile rows 2 EP, 2 EP + 1 = out-image half EP) of the finished set's epilogue.
-        auto pair_step = [&](auto nt_c, auto first_c, auto ep_c, f32x4a (&C)[NCB][NPB], const f32x4a (&P)[NCB][NPB], const unsigned char *la, const unsigned char *lw) {
+        auto pair_step = [&](auto nt_c, auto first_c, auto ep_c, f32x4 (&C)[NCB][NPB], const f32x4 (&P)[NCB][NPB], const unsigned char *la, const unsigned char *lw) {
             constexpr int NT = decltype(nt_c)::value;
             constexpr bool FIRST = decltype(first_c)::value;
             constexpr int EP = decltype(ep_c)::value;              // -1: no epilogue
@@ -689,7 +686,7 @@ __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
             qs = (qs + 2) & 3;
             __syncthreads();
         };
-        auto tile_step = [&](auto has_prev, f32x4a (&C)[NCB][NPB], const f32x4a (&P)[NCB][NPB]) {
+        auto tile_step = [&](auto has_prev, f32x4 (&C)[NCB][NPB], const f32x4 (&P)[NCB][NPB]) {
             constexpr bool HP = decltype(has_prev)::value;
             if (HP) pair_step(N9{}, T_{}, E0_{}, C, P, slot_a(), slot_w(0)); else pair_step(N9{}, T_{}, EN{}, C, P, slot_a(), slot_w(0));
             after_pair();
@@ -744,7 +741,7 @@ __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
             if (co < A.Cout) b = (A.bias ? A.bias[co] : 0.f) + (A.oshift ? A.oshift[co] : 0.f);
             binit[ci][r] = b;
         }
-    const xf_s16x2 lo_clamp = A.orelu ? xf_s16x2{0, 0} : xf_s16x2{(short)-32768, (short)-32768};
+    const s16x2 lo_clamp = A.orelu ? s16x2{0, 0} : s16x2{(short)-32768, (short)-32768};
     // the finished tile's stores: pixel (row 4 wm + 2 pi + (l31 >> 4), column l31 & 15) of the tile, channels 32 ci + 16 s + 8 half .. + 8
     const unsigned pix_b = (unsigned)A.out_cstride * 2u;
     const unsigned l_off = ((unsigned)(l31 >> 4) * (unsigned)A.W + (unsigned)(l31 & 15)) * pix_b + (unsigned)half * 16u;
@@ -769,11 +766,11 @@ __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
     constexpr int UG = 2, NMO = NPI * NCI * UG * 4;
     unsigned dd[UG][4];
     auto cvt2 = [&](float a, float b) -> unsigned {              // (bf16 outputs only: the launcher sends fp16 outputs to the older kernels)
-        const xf_f32x2 p = {a, b};
-        return __builtin_bit_cast(unsigned, __builtin_convertvector(p, xf_bf16x2));
+        const f32x2 p = {a, b};
+        return __builtin_bit_cast(unsigned, __builtin_convertvector(p, bf16x2));
     };
     auto relu2 = [&](unsigned v) -> unsigned {
-        return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(xf_s16x2, v), lo_clamp));
+        return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, v), lo_clamp));
     };
     unsigned char *const o_lane = lds_o + wave * L::OBLK + l31 * L::OROW + half * 16;      // OUT: this lane's pixel in its wave's block
     auto micro = [&](const f32x16 (&P)[NCI][NPI], int e, bool direct) __attribute__((always_inline)) {
@@ -788,13 +785,13 @@ __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
         } else {
             const int s = j - 3 * UG;
             if constexpr (OUT) {                                 // (every store of the out-image form is the movers': `direct` is never set there)
-                const u32x4v val = {dd[s][0], dd[s][1], dd[s][2], dd[s][3]};
-                *reinterpret_cast<u32x4v *>(o_lane + pi * L::OHALF + ci * 64 + s * 32) = val;
+                const u32x4 val = {dd[s][0], dd[s][1], dd[s][2], dd[s][3]};
+                *reinterpret_cast<u32x4 *>(o_lane + pi * L::OHALF + ci * 64 + s * 32) = val;
             } else if (cout0 + ci * 32 + s * 16 < A.Cout && !(A.debug & 8)) {
                 char *sb = row_base[pi] + (ci * 64 + s * 32);
                 asm volatile("" : "+s"(sb));                    // (scalar base kept opaque: uniform base + one per-lane offset register = the store's saddr form)
-                const u32x4v val = {dd[s][0], dd[s][1], dd[s][2], dd[s][3]};
-                *(__attribute__((address_space(1))) u32x4v *)((__attribute__((address_space(1))) char *)sb + l_off) = val;
+                const u32x4 val = {dd[s][0], dd[s][1], dd[s][2], dd[s][3]};
+                *(__attribute__((address_space(1))) u32x4 *)((__attribute__((address_space(1))) char *)sb + l_off) = val;
             }
         }
     };

@@ -16,32 +16,12 @@
 #include "common.h"
 #include "conv_args.h"
 #include "launch.h"
+#include "split_bf16.h"
 #include <stdlib.h>
 
 using namespace cdnet;
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));     // register staging types (HIP's float4 / uint4 structs defeat SROA)
-
 namespace {
-
-// 8 fp32 values -> hi / lo bf16 vectors (packed pairs: v_cvt_pk_bf16_f32, round to nearest even)
-__device__ __forceinline__ void split8(const float *v, u32x4 &hi, u32x4 &lo) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const f32x2 x = {v[2 * k], v[2 * k + 1]};
-        const bf16x2 h = __builtin_convertvector(x, bf16x2);
-        const unsigned hb = __builtin_bit_cast(unsigned, h);
-        const f32x2 hf = {__builtin_bit_cast(float, hb << 16), __builtin_bit_cast(float, hb & 0xffff0000u)};
-        const bf16x2 l = __builtin_convertvector(x - hf, bf16x2);
-        hi[k] = hb;
-        lo[k] = __builtin_bit_cast(unsigned, l);
-    }
-}
 
 constexpr int CK = 16;
 constexpr int PSTR = CK * 2 + 16;          // padded pixel stride of one LDS plane (bank-conflict-free b128 reads)
@@ -355,10 +335,7 @@ __global__ __launch_bounds__(256, 2) void conv_f32_kernel(ConvArgs A) {
             for (int mi = 0; mi < MPW; ++mi)
 #pragma unroll
                 for (int ni = 0; ni < NPW; ++ni) {
-                    // small terms first
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[mi], bh[ni], acc[mi][ni], 0, 0, 0);
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[mi], bl[ni], acc[mi][ni], 0, 0, 0);
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[mi], bh[ni], acc[mi][ni], 0, 0, 0);
+                    acc[mi][ni] = mfma3(acc[mi][ni], ah[mi], al[mi], bh[ni], bl[ni]);
                 }
         }
     }
@@ -546,10 +523,7 @@ __global__ __launch_bounds__(256, 4) void conv1x1_f32_stream_kernel(ConvArgs A) 
             for (int ni = 0; ni < NPW; ++ni) {
                 const bf16x8 bh = *reinterpret_cast<const bf16x8 *>(lds_b + c * 2 * B_PLANE + bbase + ni * 512);
                 const bf16x8 bl = *reinterpret_cast<const bf16x8 *>(lds_b + c * 2 * B_PLANE + B_PLANE + bbase + ni * 512);
-                // small terms first
-                acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[ni], 0, 0, 0);
-                acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[ni], 0, 0, 0);
-                acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[ni], 0, 0, 0);
+                acc[ni] = mfma3(acc[ni], ah, al, bh, bl);
             }
         }
         // a lane owns one output channel and the pixels (r & 3) + 8 (r >> 2) + 4 half of the block; lanes 0..31 / 32..63 write two 128-byte

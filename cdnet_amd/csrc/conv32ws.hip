@@ -31,38 +31,13 @@
 #include "common.h"
 #include "conv_args.h"
 #include "launch.h"
+#include "split_bf16.h"
 #include <stdlib.h>
 
 using namespace cdnet;
 
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
-
-// 8 fp32 values -> hi / lo bf16 vectors (conv32.hip: split8)
-__device__ __forceinline__ void split8(const float *v, u32x4 &hi, u32x4 &lo) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const f32x2 x = {v[2 * k], v[2 * k + 1]};
-        const bf16x2 h = __builtin_convertvector(x, bf16x2);
-        const unsigned hb = __builtin_bit_cast(unsigned, h);
-        // two plain subtractions instead of the v_pk_add_f32 the compiler would make of them: a packed fp32 instruction of a mover wave
-        // is expensive beside the consumers' MFMA stream (measured on wgrad_ws32_kernel, wgrad.hip: wg_split8)
-        float d0, d1;
-        asm("v_sub_f32 %0, %1, %2" : "=v"(d0) : "v"(x[0]), "v"(__builtin_bit_cast(float, hb << 16)));
-        asm("v_sub_f32 %0, %1, %2" : "=v"(d1) : "v"(x[1]), "v"(__builtin_bit_cast(float, hb & 0xffff0000u)));
-        const f32x2 df = {d0, d1};
-        const bf16x2 l = __builtin_convertvector(df, bf16x2);
-        hi[k] = hb;
-        lo[k] = __builtin_bit_cast(unsigned, l);
-    }
-}
 
 // One LDS-DMA piece (64 lanes x 16 bytes = 1 KB): global (uniform base + this lane's byte offset) -> LDS (uniform byte address + lane * 16).
 // Inline assembly on purpose: the compiler does not count it, so (a) it puts no alias guard - s_waitcnt vmcnt(<everything up to the
@@ -280,7 +255,7 @@ __global__ __launch_bounds__(512) void conv_ws32_kernel(ConvArgs A) {
                     const float lim = __builtin_bit_cast(float, (int)eo[R][i] < 0 ? 0u : 0x7f800000u);
 #pragma unroll
                     for (int j = 0; j < 8; ++j) v[j] = __builtin_amdgcn_fmed3f(fmaf(v[j], sc[j], sh[j]), 0.f, lim);
-                    split8(v, hi, lo);
+                    split8_scalar(v, hi, lo);
                 } else {
                     if (XF != 0 && on) {
 #pragma unroll
@@ -295,7 +270,7 @@ __global__ __launch_bounds__(512) void conv_ws32_kernel(ConvArgs A) {
 #pragma unroll
                         for (int j = 0; j < 8; ++j) v[j] = fmaxf(v[j], 0.f);
                     }
-                    split8(v, hi, lo);
+                    split8_scalar(v, hi, lo);
                     if (XF != 0) {                                       // (plain sources: the zero fill arrived as zeros)
                         const unsigned keep = (int)eo[R][i] < 0 ? 0u : 0xffffffffu;      // outside the image / source: zeros (after the transform)
                         hi &= keep;
@@ -620,7 +595,7 @@ __global__ __launch_bounds__(512) void conv_ws32_kernel(ConvArgs A) {
 #pragma unroll
                 for (int ni = 0; ni < NPW; ++ni) {
                     const int m0 = (mi * NPW + ni) * 3, g0 = t * MPW * NPW * 3 + m0;
-                    // small terms first (conv_f32_kernel's order)
+                    // mfma3's order (split_bf16.h), written out: gap() puts the interval's other work between the three
                     if (FIRST && t == 0) {
                         const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
                         C[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[t & 1][mi], bh[t & 1][ni], z, 0, 0, 0);

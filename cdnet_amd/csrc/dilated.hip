@@ -14,21 +14,16 @@
 // K order inside a 32-channel step: lane half h holds channels 16 h + [0, 16); MFMA s of the step takes the half's channels
 // 8 s + [0, 8) - the pack uses the same order, which is all that a GEMM asks of K.
 // Channels >= Cin of the last 8-channel unit and pixels outside the image are selected to zero before the MFMA (never multiplied).
-// fp32 mode: fragments split into bf16 hi / lo, three MFMAs per product in conv32.hip's order (a_lo b_hi, a_hi b_lo, a_hi b_hi).
+// fp32 mode: fragments split into bf16 hi / lo, three MFMAs per product (split8 and mfma3 of split_bf16.h).
 //
 // Training: backward-data (cdnet_dilated_conv_backward_data) is this kernel on swapped roles - its input is the gradient g of the raw
 // convolution output, GEMM-K runs over Cout x taps, GEMM-N over Cin, the pack is w'[ci][co][8 - tap] (cdnet_dilated_pack_weights_bwd) - with
 // the template parameter ACC for the store that adds into a block's gradient buffer.  The other training kernels are in dilated_train.hip.
 #include "common.h"
+#include "launch.h"
+#include "split_bf16.h"
 
 using namespace cdnet;
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -36,20 +31,6 @@ constexpr int TILE_W = 32;       // pixels of a strip (MFMA M)
 constexpr int WAVES = 4;
 constexpr int KPAIR = 32;        // channels of one load step (two MFMAs of 16)
 constexpr int FRAG = 64 * 8;     // bf16 elements of one B fragment image
-
-// 8 fp32 values -> hi / lo bf16 vectors (conv32.hip's split8: v_cvt_pk_bf16_f32, round to nearest even)
-__device__ __forceinline__ void split8(const float *v, u32x4 &hi, u32x4 &lo) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const f32x2 x = {v[2 * k], v[2 * k + 1]};
-        const bf16x2 h = __builtin_convertvector(x, bf16x2);
-        const unsigned hb = __builtin_bit_cast(unsigned, h);
-        const f32x2 hf = {__builtin_bit_cast(float, hb << 16), __builtin_bit_cast(float, hb & 0xffff0000u)};
-        const bf16x2 l = __builtin_convertvector(x - hf, bf16x2);
-        hi[k] = hb;
-        lo[k] = __builtin_bit_cast(unsigned, l);
-    }
-}
 
 // the 8 channels at element offset `eoff` of `in` as MFMA operand words; rem = Cin - first channel (channels >= rem are zeroed),
 // ok = false: the whole unit is zero and nothing is loaded
@@ -142,9 +123,7 @@ __global__ __launch_bounds__(WAVES * 64) void dilated_conv_kernel(const cdnet_di
 #pragma unroll
                         for (int m = 0; m < MT; ++m) {
                             const bf16x8 a_hi = __builtin_bit_cast(bf16x8, ah[m][s]), a_lo = __builtin_bit_cast(bf16x8, al[m][s]);
-                            acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_lo, bh, acc[m][t], 0, 0, 0);
-                            acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, bl, acc[m][t], 0, 0, 0);
-                            acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, bh, acc[m][t], 0, 0, 0);
+                            acc[m][t] = mfma3(acc[m][t], a_hi, a_lo, bh, bl);
                         }
                     } else {
 #pragma unroll
@@ -190,38 +169,21 @@ __global__ __launch_bounds__(WAVES * 64) void dilated_conv_kernel(const cdnet_di
     }
 }
 
-// one thread per packed bf16x8 fragment row (lane of a (tap, K step, output tile) fragment)
+// one thread per packed bf16x8 fragment row (lane of a (tap, K step, N tile) fragment).  BWD false: GEMM-N runs over Cout, GEMM-K over Cin;
+// true, the backward-data pack: the same fragment order for w'[ci][co][taps - 1 - tap] - GEMM-N over Cin, GEMM-K over Cout, taps mirrored
+template <bool BWD>
 __global__ void dilated_pack_kernel(const float *w, uint16_t *packed, int Cin, int Cout, int taps, int f32, size_t rows) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= rows) return;
-    const int NTT = (Cout + 31) / 32, KK = 2 * ((Cin + KPAIR - 1) / KPAIR);
+    const int NTT = ((BWD ? Cin : Cout) + 31) / 32, KK = 2 * (((BWD ? Cout : Cin) + KPAIR - 1) / KPAIR);
     const int lane = (int)(i % 64);
     const size_t f = i / 64;
     const int t = (int)(f % NTT), kk = (int)((f / NTT) % KK), tap = (int)(f / NTT / KK);
-    const int co = t * 32 + (lane & 31), c0 = (kk >> 1) * KPAIR + 16 * (lane >> 5) + 8 * (kk & 1);
+    const int n = t * 32 + (lane & 31), k0 = (kk >> 1) * KPAIR + 16 * (lane >> 5) + 8 * (kk & 1);
     uint16_t *dst = packed + f * (size_t)(FRAG * (f32 ? 2 : 1)) + (size_t)lane * 8;
     for (int j = 0; j < 8; ++j) {
-        const int ci = c0 + j;
-        const float v = (co < Cout && ci < Cin) ? w[((size_t)co * Cin + ci) * taps + tap] : 0.f;
-        const __bf16 hb = static_cast<__bf16>(v);
-        dst[j] = __builtin_bit_cast(uint16_t, hb);
-        if (f32) dst[FRAG + j] = to_bf16(v - static_cast<float>(hb));
-    }
-}
-
-// the backward-data pack: the same fragment order for w'[ci][co][taps - 1 - tap] - GEMM-K runs over Cout, GEMM-N over Cin, taps mirrored
-__global__ void dilated_pack_bwd_kernel(const float *w, uint16_t *packed, int Cin, int Cout, int taps, int f32, size_t rows) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= rows) return;
-    const int NTT = (Cin + 31) / 32, KK = 2 * ((Cout + KPAIR - 1) / KPAIR);
-    const int lane = (int)(i % 64);
-    const size_t f = i / 64;
-    const int t = (int)(f % NTT), kk = (int)((f / NTT) % KK), tap = (int)(f / NTT / KK);
-    const int ci = t * 32 + (lane & 31), c0 = (kk >> 1) * KPAIR + 16 * (lane >> 5) + 8 * (kk & 1);
-    uint16_t *dst = packed + f * (size_t)(FRAG * (f32 ? 2 : 1)) + (size_t)lane * 8;
-    for (int j = 0; j < 8; ++j) {
-        const int co = c0 + j;
-        const float v = (co < Cout && ci < Cin) ? w[((size_t)co * Cin + ci) * taps + (taps - 1 - tap)] : 0.f;
+        const int co = BWD ? k0 + j : n, ci = BWD ? n : k0 + j;
+        const float v = (co < Cout && ci < Cin) ? w[((size_t)co * Cin + ci) * taps + (BWD ? taps - 1 - tap : tap)] : 0.f;
         const __bf16 hb = static_cast<__bf16>(v);
         dst[j] = __builtin_bit_cast(uint16_t, hb);
         if (f32) dst[FRAG + j] = to_bf16(v - static_cast<float>(hb));
@@ -232,27 +194,29 @@ size_t pack_rows(int Cin, int Cout, int taps) {
     return (size_t)taps * (2 * ((Cin + KPAIR - 1) / KPAIR)) * ((Cout + 31) / 32) * 64;
 }
 
-template <int MT, int NT>
-int launch(const cdnet_dilated_conv_args &A, hipStream_t st) {
-    const int tiles_x = cdiv(A.W, TILE_W), tiles_y = cdiv(A.H, WAVES * MT);
-    const dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)cdiv(cdiv(A.Cout, 32), NT), (unsigned)A.N);
-    if (A.f32) dilated_conv_kernel<MT, NT, true><<<grid, WAVES * 64, 0, st>>>(A);
-    else dilated_conv_kernel<MT, NT, false><<<grid, WAVES * 64, 0, st>>>(A);
-    return check_launch("cdnet_dilated_conv_forward");
+// both pack entries: `who` is the entry's name, BWD its kernel; GEMM-N and GEMM-K swap for the backward-data pack
+template <bool BWD>
+int pack(const char *who, const float *w, void *packed, int Cin, int Cout, int taps, int f32, void *stream) {
+    CDNET_REQUIRE(w && packed, "%s: null pointer", who);
+    CDNET_REQUIRE(Cin >= 1 && Cout >= 1, "%s: Cin %d, Cout %d must be positive", who, Cin, Cout);
+    CDNET_REQUIRE(taps == 1 || taps == 9, "%s: taps %d (1 or 9)", who, taps);
+    const size_t rows = BWD ? pack_rows(Cout, Cin, taps) : pack_rows(Cin, Cout, taps);
+    dilated_pack_kernel<BWD><<<(unsigned)((rows + 255) / 256), 256, 0, (hipStream_t)stream>>>(w, static_cast<uint16_t *>(packed), Cin, Cout, taps,
+                                                                                             f32 ? 1 : 0, rows);
+    return check_launch(who);
 }
 
+// `who`: the entry's name; acc: the store adds (backward-data only)
 template <int MT, int NT>
-int launch_bwd(const cdnet_dilated_conv_args &A, bool acc, hipStream_t st) {
+int launch(const cdnet_dilated_conv_args &A, bool acc, hipStream_t st, const char *who) {
     const int tiles_x = cdiv(A.W, TILE_W), tiles_y = cdiv(A.H, WAVES * MT);
     const dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)cdiv(cdiv(A.Cout, 32), NT), (unsigned)A.N);
-    if (A.f32) {
-        if (acc) dilated_conv_kernel<MT, NT, true, true><<<grid, WAVES * 64, 0, st>>>(A);
-        else dilated_conv_kernel<MT, NT, true, false><<<grid, WAVES * 64, 0, st>>>(A);
-    } else {
-        if (acc) dilated_conv_kernel<MT, NT, false, true><<<grid, WAVES * 64, 0, st>>>(A);
-        else dilated_conv_kernel<MT, NT, false, false><<<grid, WAVES * 64, 0, st>>>(A);
-    }
-    return check_launch("cdnet_dilated_conv_backward_data");
+    return with_bool(A.f32 != 0, [&](auto f32_c) {
+        return with_bool(acc, [&](auto acc_c) {
+            dilated_conv_kernel<MT, NT, decltype(f32_c)::value, decltype(acc_c)::value><<<grid, WAVES * 64, 0, st>>>(A);
+            return check_launch(who);
+        });
+    });
 }
 
 }  // namespace
@@ -263,13 +227,7 @@ extern "C" size_t cdnet_dilated_packed_weight_elems(int Cin, int Cout, int taps,
 }
 
 extern "C" int cdnet_dilated_pack_weights(const float *w, void *packed, int Cin, int Cout, int taps, int f32, void *stream) {
-    CDNET_REQUIRE(w && packed, "cdnet_dilated_pack_weights: null pointer");
-    CDNET_REQUIRE(Cin >= 1 && Cout >= 1, "cdnet_dilated_pack_weights: Cin %d, Cout %d must be positive", Cin, Cout);
-    CDNET_REQUIRE(taps == 1 || taps == 9, "cdnet_dilated_pack_weights: taps %d (1 or 9)", taps);
-    const size_t rows = pack_rows(Cin, Cout, taps);
-    dilated_pack_kernel<<<(unsigned)((rows + 255) / 256), 256, 0, (hipStream_t)stream>>>(w, static_cast<uint16_t *>(packed), Cin, Cout, taps,
-                                                                                        f32 ? 1 : 0, rows);
-    return check_launch("cdnet_dilated_pack_weights");
+    return pack<false>("cdnet_dilated_pack_weights", w, packed, Cin, Cout, taps, f32, stream);
 }
 
 extern "C" int cdnet_dilated_conv_forward(const cdnet_dilated_conv_args *args, void *stream) {
@@ -296,18 +254,12 @@ extern "C" int cdnet_dilated_conv_forward(const cdnet_dilated_conv_args *args, v
         }
     }
     CDNET_REQUIRE((long long)cdiv(A.W, TILE_W) * cdiv(A.H, WAVES) < (1ll << 31), "cdnet_dilated_conv_forward: image too large");
-    if (A.Cout <= 32) return launch<4, 1>(A, (hipStream_t)stream);
-    return launch<2, 2>(A, (hipStream_t)stream);
+    if (A.Cout <= 32) return launch<4, 1>(A, false, (hipStream_t)stream, "cdnet_dilated_conv_forward");
+    return launch<2, 2>(A, false, (hipStream_t)stream, "cdnet_dilated_conv_forward");
 }
 
 extern "C" int cdnet_dilated_pack_weights_bwd(const float *w, void *packed, int Cin, int Cout, int taps, int f32, void *stream) {
-    CDNET_REQUIRE(w && packed, "cdnet_dilated_pack_weights_bwd: null pointer");
-    CDNET_REQUIRE(Cin >= 1 && Cout >= 1, "cdnet_dilated_pack_weights_bwd: Cin %d, Cout %d must be positive", Cin, Cout);
-    CDNET_REQUIRE(taps == 1 || taps == 9, "cdnet_dilated_pack_weights_bwd: taps %d (1 or 9)", taps);
-    const size_t rows = pack_rows(Cout, Cin, taps);
-    dilated_pack_bwd_kernel<<<(unsigned)((rows + 255) / 256), 256, 0, (hipStream_t)stream>>>(w, static_cast<uint16_t *>(packed), Cin, Cout, taps,
-                                                                                            f32 ? 1 : 0, rows);
-    return check_launch("cdnet_dilated_pack_weights_bwd");
+    return pack<true>("cdnet_dilated_pack_weights_bwd", w, packed, Cin, Cout, taps, f32, stream);
 }
 
 // dx = conv(g, w') is the forward kernel on swapped roles: its `in` is g (Cout channels), its output tile count runs over Cin
@@ -336,6 +288,6 @@ extern "C" int cdnet_dilated_conv_backward_data(const cdnet_dilated_bwd_data_arg
     A.Cin = B.Cout; A.in_cstride = B.g_cstride;
     A.Cout = B.Cin; A.out_cstride = B.dx_cstride; A.out_coff = B.dx_coff;
     A.taps = B.taps; A.dilation = B.dilation; A.leaky = 0; A.slope = 0.f; A.f32 = B.f32 ? 1 : 0; A.out_nchw = 0;
-    if (A.Cout <= 32) return launch_bwd<4, 1>(A, B.accumulate != 0, (hipStream_t)stream);
-    return launch_bwd<2, 2>(A, B.accumulate != 0, (hipStream_t)stream);
+    if (A.Cout <= 32) return launch<4, 1>(A, B.accumulate != 0, (hipStream_t)stream, "cdnet_dilated_conv_backward_data");
+    return launch<2, 2>(A, B.accumulate != 0, (hipStream_t)stream, "cdnet_dilated_conv_backward_data");
 }

@@ -9,19 +9,15 @@
 // 32-pixel row strips.  Per strip it stages g [32 pixels][32 co] once and, per tap, every wave its own shifted x [32 pixels][32 ci] through
 // LDS with 16-byte loads, and reads both K-major: lane (channel, half h) takes pixels 16 s + 8 h + [0, 8) of MFMA step s.  A staged pixel
 // row is 36 floats: consecutive lanes read consecutive banks and the two halves' rows, 8 apart, lie 32 banks apart - no conflict.
-// Both operands are activations: each is split into bf16 hi / lo after the LDS read, three MFMAs per product in conv32.hip's order.
+// Both operands are activations: each is split into bf16 hi / lo after the LDS read, three MFMAs per product (split8, mfma3: split_bf16.h).
 // A tap that no pixel of the strip reaches is skipped (no load, no MFMA).  Every slab stores its [taps][Cout tiles][Cin tiles] sums; a
 // second launch adds the slabs in order - no atomics, the same bits on every run.
 #include "common.h"
+#include "bn_sums.h"
+#include "launch.h"
+#include "split_bf16.h"
 
 using namespace cdnet;
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -29,20 +25,6 @@ constexpr int STRIP = 32;            // pixels of a strip (two MFMA K steps of 1
 constexpr int ROW = 36;              // floats of a staged pixel row in LDS (32 channels + 4: see above)
 constexpr int WG_WAVES = 4;          // Cin tiles of a workgroup
 constexpr int WGRAD_WGS = 512;       // workgroups a launch aims at (two per CU)
-
-// 8 fp32 values -> hi / lo bf16 vectors (dilated.hip's split8)
-__device__ __forceinline__ void split8(const float *v, u32x4 &hi, u32x4 &lo) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const f32x2 x = {v[2 * k], v[2 * k + 1]};
-        const bf16x2 h = __builtin_convertvector(x, bf16x2);
-        const unsigned hb = __builtin_bit_cast(unsigned, h);
-        const f32x2 hf = {__builtin_bit_cast(float, hb << 16), __builtin_bit_cast(float, hb & 0xffff0000u)};
-        const bf16x2 l = __builtin_convertvector(x - hf, bf16x2);
-        hi[k] = hb;
-        lo[k] = __builtin_bit_cast(unsigned, l);
-    }
-}
 
 // four channels c .. c + 3 of a pixel (channels >= cend selected to zero), or zero when !ok
 __device__ __forceinline__ f32x4 load4(const float *p, bool ok, int c, int cend) {
@@ -141,9 +123,7 @@ __global__ __launch_bounds__(WG_WAVES * 64) void dilated_wgrad_kernel(const cdne
                     frag(sx, s, h, i, bh, bl);
                     const bf16x8 a_hi = __builtin_bit_cast(bf16x8, ah[s]), a_lo = __builtin_bit_cast(bf16x8, al[s]);
                     const bf16x8 b_hi = __builtin_bit_cast(bf16x8, bh), b_lo = __builtin_bit_cast(bf16x8, bl);
-                    acc[tap] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_lo, b_hi, acc[tap], 0, 0, 0);
-                    acc[tap] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, b_lo, acc[tap], 0, 0, 0);
-                    acc[tap] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, b_hi, acc[tap], 0, 0, 0);
+                    acc[tap] = mfma3(acc[tap], a_hi, a_lo, b_hi, b_lo);
                 }
             }
         }
@@ -249,25 +229,14 @@ __global__ __launch_bounds__(256) void bn_tile_sums_kernel(const float *__restri
     }
 }
 
-// one workgroup per channel: thread i adds tiles i, i + 256, ... in fp64, then a fixed LDS tree (bn_finalize_train_kernel's scheme)
+// one workgroup per channel: the fixed-order fp64 sums of bn_sums.h
 __global__ __launch_bounds__(256) void bn_bwd_final_kernel(const float *__restrict__ part, int T, int C, float *dgamma, float *dbeta) {
-    __shared__ double s_s[256], s_q[256];
-    const int c = blockIdx.x, lane = threadIdx.x;
-    double s = 0.0, q = 0.0;
-    for (int t = lane; t < T; t += 256) {
-        s += (double)part[((size_t)t * 2) * C + c];
-        q += (double)part[((size_t)t * 2 + 1) * C + c];
-    }
-    s_s[lane] = s; s_q[lane] = q;
-    __syncthreads();
-#pragma unroll
-    for (int o = 128; o > 0; o >>= 1) {
-        if (lane < o) { s_s[lane] += s_s[lane + o]; s_q[lane] += s_q[lane + o]; }
-        __syncthreads();
-    }
-    if (lane == 0) {
-        dbeta[c] = (float)s_s[0];
-        dgamma[c] = (float)s_q[0];
+    const int c = blockIdx.x;
+    double s, q;
+    bn_sum_partials(part, T, C, c, s, q);
+    if (threadIdx.x == 0) {
+        dbeta[c] = (float)s;
+        dgamma[c] = (float)q;
     }
 }
 
@@ -300,11 +269,6 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float *__restri
         const float dz = gamma[c] * invstd[c] * (d - dbeta[c] * inv_count - xhat * (dgamma[c] * inv_count));
         g[p * gs + c] = v > 0.f ? dz : slope * dz;
     }
-}
-
-unsigned lin_blocks(size_t total) {
-    const size_t b = (total + 255) / 256;
-    return (unsigned)(b < 8192 ? (b ? b : 1) : 8192);
 }
 
 }  // namespace
@@ -346,7 +310,7 @@ extern "C" int cdnet_dropout_mask(unsigned long long key, int layer, size_t coun
     CDNET_REQUIRE(count >= 1, "cdnet_dropout_mask: count must be positive");
     CDNET_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "cdnet_dropout_mask: p_drop %g outside [0, 1)", (double)p_drop);
     CDNET_REQUIRE(layer >= 0, "cdnet_dropout_mask: layer %d < 0", layer);
-    dropout_mask_kernel<<<lin_blocks(count), 256, 0, (hipStream_t)stream>>>(layer_key(key, layer), count, drop_threshold(p_drop), mask);
+    dropout_mask_kernel<<<lin_grid(count, 8192), 256, 0, (hipStream_t)stream>>>(layer_key(key, layer), count, drop_threshold(p_drop), mask);
     return check_launch("cdnet_dropout_mask");
 }
 
@@ -383,7 +347,7 @@ extern "C" int cdnet_slice_bn_train_forward(const cdnet_slice_bn_fwd_args *args,
                                  shift, A.mean, A.invstd, stream);
     if (rc) return rc;
     const size_t total = (size_t)A.P * A.C;
-    bn_fwd_apply_kernel<<<lin_blocks(total), 256, 0, st>>>(A.z, A.z_cstride, scale, shift, total, A.C, lkey, thr, ks, A.out, A.out_cstride,
+    bn_fwd_apply_kernel<<<lin_grid(total, 8192), 256, 0, st>>>(A.z, A.z_cstride, scale, shift, total, A.C, lkey, thr, ks, A.out, A.out_cstride,
                                                           A.out_coff);
     return check_launch("cdnet_slice_bn_train_forward");
 }
@@ -411,7 +375,7 @@ extern "C" int cdnet_slice_bn_train_backward(const cdnet_slice_bn_bwd_args *args
                                                                                            A.invstd, A.P, A.C, G.tile, lkey, thr, ks, A.ws);
     bn_bwd_final_kernel<<<A.C, 256, 0, st>>>(A.ws, G.T, A.C, A.dgamma, A.dbeta);
     const size_t total = (size_t)A.P * A.C;
-    bn_bwd_apply_kernel<<<lin_blocks(total), 256, 0, st>>>(A.z, A.z_cstride, A.dy, A.dy_cstride, A.dy_coff, A.mean, A.invstd, A.gamma, A.dgamma,
+    bn_bwd_apply_kernel<<<lin_grid(total, 8192), 256, 0, st>>>(A.z, A.z_cstride, A.dy, A.dy_cstride, A.dy_coff, A.mean, A.invstd, A.gamma, A.dgamma,
                                                           A.dbeta, total, A.C, 1.f / (float)A.P, A.slope, lkey, thr, ks, A.g, A.g_cstride);
     return check_launch("cdnet_slice_bn_train_backward");
 }

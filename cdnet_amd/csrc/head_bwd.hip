@@ -37,7 +37,7 @@ __device__ __forceinline__ void feat8(const HeadFeat &f, size_t pix, int c0, con
     rr.u = make_uint4(0, 0, 0, 0);
     if (f.res) rr.u = *reinterpret_cast<const uint4 *>(f.res + pix * 64 + c0);
     if (f.f16 && f.scale && f.relu) {            // training-mode feature: packed math (xform.h)
-        const xf_u32x4 a = __builtin_bit_cast(xf_u32x4, r.u), b = __builtin_bit_cast(xf_u32x4, rr.u);
+        const u32x4 a = __builtin_bit_cast(u32x4, r.u), b = __builtin_bit_cast(u32x4, rr.u);
         if (f.res) xf_bnrelu_f16_to_f32<true>(a, b, s_sc + c0, s_sh + c0, v);
         else xf_bnrelu_f16_to_f32<false>(a, a, s_sc + c0, s_sh + c0, v);
         return;
@@ -70,7 +70,7 @@ __device__ __forceinline__ void load_raw8(const HeadFeat &f, size_t pix, int c0,
 }
 template <int FM>
 __device__ __forceinline__ void feat_from_raw8(const HeadFeat &f, const FeatRaw8 &R, int c0, const float *s_sc, const float *s_sh, float *v) {
-    const xf_u32x4 a = __builtin_bit_cast(xf_u32x4, R.r), b = __builtin_bit_cast(xf_u32x4, R.s);
+    const u32x4 a = __builtin_bit_cast(u32x4, R.r), b = __builtin_bit_cast(u32x4, R.s);
     if (FM == 1) { xf_bnrelu_f16_to_f32<true>(a, b, s_sc + c0, s_sh + c0, v); return; }
     if (FM == 0) {
         V16 r0;

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include "common.h"
 #include "head_feat.h"
+#include "bn_sums.h"
 #include "launch.h"
 #include "xform.h"
 
@@ -69,25 +70,11 @@ __global__ __launch_bounds__(256) void bn_finalize_train_kernel(const float *__r
                                                                 float eps, float momentum, float *rm, float *rv,
                                                                 float *scale, float *shift, float *mean_out,
                                                                 float *invstd_out) {
-    // one workgroup per channel (C workgroups keep every CU busy; the 4-byte reads of different channels share cache
-    // lines in L2): thread i sums tiles i, i+256, ... in order, then a fixed LDS tree - deterministic
-    __shared__ double s_s[256], s_q[256];
+    // one workgroup per channel: the fixed-order fp64 sums of bn_sums.h - deterministic
     const int c = blockIdx.x;
-    const int lane = threadIdx.x;
-    double s = 0.0, q = 0.0;
-    for (int t = lane; t < T; t += 256) {
-        s += (double)stats[((size_t)t * 2) * C + c];
-        q += (double)stats[((size_t)t * 2 + 1) * C + c];
-    }
-    s_s[lane] = s; s_q[lane] = q;
-    __syncthreads();
-#pragma unroll
-    for (int o = 128; o > 0; o >>= 1) {
-        if (lane < o) { s_s[lane] += s_s[lane + o]; s_q[lane] += s_q[lane + o]; }
-        __syncthreads();
-    }
-    s = s_s[0]; q = s_q[0];
-    if (lane == 0) {
+    double s, q;
+    bn_sum_partials(stats, T, C, c, s, q);
+    if (threadIdx.x == 0) {
         double mean = s / count;
         double var = q / count - mean * mean;
         if (var < 0) var = 0;
@@ -181,11 +168,11 @@ __device__ __forceinline__ void feat_from_raw16(const HeadFeat &f, const FeatRaw
     for (int h2 = 0; h2 < 2; ++h2) {
         const uint4 r = R.r[h2], rr = R.s[h2];
         if (f.f16 && !f.scale && f.relu && has_res) {      // eval-mode residual unit output: relu(raw + res)
-            xf_addrelu_f16_to_f32(__builtin_bit_cast(xf_u32x4, r), __builtin_bit_cast(xf_u32x4, rr), v + h2 * 8);
+            xf_addrelu_f16_to_f32(__builtin_bit_cast(u32x4, r), __builtin_bit_cast(u32x4, rr), v + h2 * 8);
             continue;
         }
         if (fast) {
-            const xf_u32x4 a = __builtin_bit_cast(xf_u32x4, r), b = __builtin_bit_cast(xf_u32x4, rr);
+            const u32x4 a = __builtin_bit_cast(u32x4, r), b = __builtin_bit_cast(u32x4, rr);
             const int c0 = q * 16 + h2 * 8;
             if (has_res) xf_bnrelu_f16_to_f32<true>(a, b, s_sc + c0, s_sh + c0, v + h2 * 8);
             else xf_bnrelu_f16_to_f32<false>(a, a, s_sc + c0, s_sh + c0, v + h2 * 8);
@@ -247,7 +234,7 @@ __global__ __launch_bounds__(256, (FM == 2 ? 1 : 4)) void dam_head_fwd_kernel(He
         if (FM == 1) {
 #pragma unroll
             for (int h2 = 0; h2 < 2; ++h2)
-                xf_bnrelu_f16_to_f32<true>(__builtin_bit_cast(xf_u32x4, R.r[h2]), __builtin_bit_cast(xf_u32x4, R.s[h2]), s_sc[k] + q * 16 + h2 * 8,
+                xf_bnrelu_f16_to_f32<true>(__builtin_bit_cast(u32x4, R.r[h2]), __builtin_bit_cast(u32x4, R.s[h2]), s_sc[k] + q * 16 + h2 * 8,
                                            s_sh[k] + q * 16 + h2 * 8, v + h2 * 8);
         } else {
             feat_from_raw16(f, R, q, s_sc[k], s_sh[k], v);
@@ -320,9 +307,6 @@ __global__ __launch_bounds__(256, (FM == 2 ? 1 : 4)) void dam_head_fwd_kernel(He
 // (the LDS pipe, not HBM, set its 416 us per 64 tiles).  Lane (col, kg) then holds outputs 4 kg .. 4 kg + 3 of pixel `col`: the gates
 // (revAttention, model_unet_rev1.py:8-17) need the point logit - broadcast from the kg = 0 lane - and the 9-term sum over the direction
 // logits - a partial sum per lane, two cross-lane adds.  HAS_F3 = false: `point` is given (cdnet_conv_args.dot_out).
-typedef float hd_f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((ext_vector_type(8))) __bf16 hd_bf16x8;
-
 template <bool HAS_F3, bool F32>
 __global__ __launch_bounds__(256) void dam_head_mfma_kernel(const unsigned short *__restrict__ f1, const unsigned short *__restrict__ f2,
                                                             const unsigned short *__restrict__ f3, const HeadW *__restrict__ hw, size_t total,
@@ -333,7 +317,7 @@ __global__ __launch_bounds__(256) void dam_head_mfma_kernel(const unsigned short
     constexpr int U = F32 ? 1 : 2;                               // 16-pixel groups in flight per wave
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int col = lane & 15, kg = lane >> 4;
-    union Frag { hd_bf16x8 v; unsigned short h[8]; };
+    union Frag { bf16x8 v; unsigned short h[8]; };
     // row `col` of a classifier (zero rows beyond its outputs), channels 32 ks + 8 kg .. + 7, as hi | lo
     auto split = [&](const float *row, int ks, Frag &hi, Frag &lo) {
 #pragma unroll
@@ -361,7 +345,7 @@ __global__ __launch_bounds__(256) void dam_head_mfma_kernel(const unsigned short
 #pragma unroll
     for (int i = 0; i < 3; ++i) bm3[i] = hw->bm[i];
     const float bp = hw->bp, a1 = hw->a1;
-    const hd_f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     for (size_t g0 = ((size_t)blockIdx.x * 4 + wave) * (16 * U); g0 < total; g0 += (size_t)gridDim.x * 4 * (16 * U)) {
         Frag b1[U][2], b2[U][2], b3[U][2];                       // 16-bit features: the fragments themselves; F32: their hi parts ...
         Frag l1[F32 ? U : 1][2], l2[F32 ? U : 1][2], l3[F32 ? U : 1][2];      // ... and lo parts
@@ -372,16 +356,16 @@ __global__ __launch_bounds__(256) void dam_head_mfma_kernel(const unsigned short
             px = px < total ? px : total - 1;
             const size_t e = px * 64 + kg * 8;
             if constexpr (F32) {
-                hd_f32x4 r[3][2][2];
+                f32x4 r[3][2][2];
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
                     for (int hq = 0; hq < 2; ++hq) {
-                        if (HAS_F3) r[2][ks][hq] = *reinterpret_cast<const hd_f32x4 *>(reinterpret_cast<const float *>(f3) + e + ks * 32 + hq * 4);
-                        r[1][ks][hq] = *reinterpret_cast<const hd_f32x4 *>(reinterpret_cast<const float *>(f2) + e + ks * 32 + hq * 4);
-                        r[0][ks][hq] = *reinterpret_cast<const hd_f32x4 *>(reinterpret_cast<const float *>(f1) + e + ks * 32 + hq * 4);
+                        if (HAS_F3) r[2][ks][hq] = *reinterpret_cast<const f32x4 *>(reinterpret_cast<const float *>(f3) + e + ks * 32 + hq * 4);
+                        r[1][ks][hq] = *reinterpret_cast<const f32x4 *>(reinterpret_cast<const float *>(f2) + e + ks * 32 + hq * 4);
+                        r[0][ks][hq] = *reinterpret_cast<const f32x4 *>(reinterpret_cast<const float *>(f1) + e + ks * 32 + hq * 4);
                     }
-                auto cut = [&](const hd_f32x4 (&q)[2], Frag &hi, Frag &lo) {
+                auto cut = [&](const f32x4 (&q)[2], Frag &hi, Frag &lo) {
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
                         const float x = q[j >> 2][j & 3];
@@ -399,16 +383,16 @@ __global__ __launch_bounds__(256) void dam_head_mfma_kernel(const unsigned short
             } else {
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
-                    if (HAS_F3) b3[u][ks].v = *reinterpret_cast<const hd_bf16x8 *>(f3 + e + ks * 32);
-                    b2[u][ks].v = *reinterpret_cast<const hd_bf16x8 *>(f2 + e + ks * 32);
-                    b1[u][ks].v = *reinterpret_cast<const hd_bf16x8 *>(f1 + e + ks * 32);
+                    if (HAS_F3) b3[u][ks].v = *reinterpret_cast<const bf16x8 *>(f3 + e + ks * 32);
+                    b2[u][ks].v = *reinterpret_cast<const bf16x8 *>(f2 + e + ks * 32);
+                    b1[u][ks].v = *reinterpret_cast<const bf16x8 *>(f1 + e + ks * 32);
                 }
             }
             if (!HAS_F3) ptin[u] = point[px];
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            hd_f32x4 aP = zero, aD = zero, aM = zero;
+            f32x4 aP = zero, aD = zero, aM = zero;
             // (small terms first)
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {

@@ -2,11 +2,10 @@
 // transform of 8 channels (producer BatchNorm scale / shift, residual operand, ReLU -> bf16 MFMA operand).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "vec.h"
 #include "xform.h"
 
 namespace cdnet {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 
 static __device__ __forceinline__ float bf2f(unsigned short u) { return __uint_as_float((unsigned)u << 16); }
 static __device__ __forceinline__ float h2f(unsigned short u) { return (float)__builtin_bit_cast(_Float16, u); }
@@ -33,13 +32,13 @@ struct ChanXf {           // per-thread channel transform for its 8 channels of 
 static __device__ __forceinline__ V16 xform8(V16 raw, const V16 *res, const ChanXf &t, bool relu, bool f16) {
     V16 o;
     if (f16 && !t.on && relu && res) {           // eval-mode residual unit: relu(raw + res), packed math
-        o.u = __builtin_bit_cast(uint4, xf_addrelu_f16(__builtin_bit_cast(xf_u32x4, raw.u), __builtin_bit_cast(xf_u32x4, res->u)));
+        o.u = __builtin_bit_cast(uint4, xf_addrelu_f16(__builtin_bit_cast(u32x4, raw.u), __builtin_bit_cast(u32x4, res->u)));
         return o;
     }
     if (f16 && t.on && relu) {                   // the training-mode combination: packed math (xform.h)
-        const xf_u32x4 r = __builtin_bit_cast(xf_u32x4, raw.u);
-        const xf_u32x4 v = res ? xf_bnrelu_f16<true>(r, __builtin_bit_cast(xf_u32x4, res->u), t.sc, t.sh)
-                               : xf_bnrelu_f16<false>(r, r, t.sc, t.sh);
+        const u32x4 r = __builtin_bit_cast(u32x4, raw.u);
+        const u32x4 v = res ? xf_bnrelu_f16<true>(r, __builtin_bit_cast(u32x4, res->u), t.sc, t.sh)
+                            : xf_bnrelu_f16<false>(r, r, t.sc, t.sh);
         o.u = __builtin_bit_cast(uint4, v);
         return o;
     }

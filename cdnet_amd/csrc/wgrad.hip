@@ -16,14 +16,10 @@
 #include "common.h"
 #include "conv_args.h"
 #include "launch.h"
+#include "split_bf16.h"
 #include "xform.h"
 
 using namespace cdnet;
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 namespace {
 
@@ -58,8 +54,7 @@ struct WgradArgs {
     int debug;                // ablation bits for tools/bench_wgrad.py (env CDNET_WGRAD_DEBUG): 1 no MFMA loop, 2 no loads, 4 no LDS staging; 8, 16: WGRAD_DBG_* (conv_args.h)
 };
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));   // register staging type (HIP's uint4 struct copies defeat SROA)
-union W16 {
+union W16 {                   // (u32x4, not uint4: register staging type, vec.h)
     u32x4 u;
     unsigned short h[8];
 };
@@ -683,31 +678,9 @@ __global__ __launch_bounds__(NT) void wgrad_ws_kernel(WgradArgs A) {
 // fp32-precision variant (src.f16 == 2: input, residual and output gradient are fp32 tensors).  Both MFMA operands are
 // split into (hi, lo) bf16 planes while they are staged - [pixel][channel] LDS tiles A_hi | A_lo | G_hi | G_lo, read with
 // the same transposing loads - and every k-step runs three MFMAs per tap: a_lo*g_hi + a_hi*g_lo + a_hi*g_hi, fp32
-// accumulation (see conv32.hip for the error bound).  8 waves = 4 dW quadrants x 2 halves of the tile's k-steps; one LDS
+// accumulation (split8_scalar and the error bound: split_bf16.h).  8 waves = 4 dW quadrants x 2 halves of the tile's k-steps; one LDS
 // stage, the next tile's global loads in flight in registers during the MFMA phase.  Pooled sources are materialised first.
 // ------------------------------------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(2))) __bf16 wg_bf16x2;
-typedef __attribute__((ext_vector_type(2))) float wg_f32x2;
-typedef __attribute__((ext_vector_type(4))) float wg_f32x4;
-
-// hi = bf16(x) (RNE), lo = bf16(x - hi) for eight values.  The two subtractions of a pair are kept scalar (inline assembly): left to
-// the compiler they become one v_pk_add_f32, and a packed fp32 instruction costs a mover wave far more than two plain ones beside
-// the consumers' MFMA stream (wgrad_ws32_kernel: 257 -> 241 us on the 64 -> 64 layer at 256 x 256 x 16).
-__device__ __forceinline__ void wg_split8(const float *v, u32x4 &hi, u32x4 &lo) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const wg_f32x2 x = {v[2 * k], v[2 * k + 1]};
-        const wg_bf16x2 h = __builtin_convertvector(x, wg_bf16x2);
-        const unsigned hb = __builtin_bit_cast(unsigned, h);
-        float d0, d1;
-        asm("v_sub_f32 %0, %1, %2" : "=v"(d0) : "v"(x[0]), "v"(__builtin_bit_cast(float, hb << 16)));
-        asm("v_sub_f32 %0, %1, %2" : "=v"(d1) : "v"(x[1]), "v"(__builtin_bit_cast(float, hb & 0xffff0000u)));
-        const wg_f32x2 d = {d0, d1};
-        hi[k] = hb;
-        lo[k] = __builtin_bit_cast(unsigned, __builtin_convertvector(d, wg_bf16x2));
-    }
-}
-
 constexpr int NT32 = 256;      // 4 waves, one per SIMD (512 registers each): one dW quadrant x all k-steps of a tile per wave
 
 // QM (64 x 64 blocks, the transposed convolutions of the decoder's 32- and 16-channel blocks): as wgrad_ws32_kernel's - 1: at most 32
@@ -777,7 +750,7 @@ __global__ __launch_bounds__(NT32) void wgrad_f32_kernel(WgradArgs A) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) { sc[j] = s_xf[slot_a * 8 + j]; sh[j] = s_xf[CI + slot_a * 8 + j]; }
 
-    wg_f32x4 pa_[NA][2], pg_[NG][2];
+    f32x4 pa_[NA][2], pg_[NG][2];
     int ea[NA];                          // element offset of the thread's i-th input vector, -1 = zero fill (tensors < 2^31 elements)
     unsigned gvalid = 0;
     // what depends on the thread only - halo coordinates and in-tile offsets of its vectors - is computed once; a tile contributes one
@@ -811,7 +784,7 @@ __global__ __launch_bounds__(NT32) void wgrad_f32_kernel(WgradArgs A) {
             const bool ok = hyx[i] >= 0 && cok_a && (unsigned)y < (unsigned)A.H && (unsigned)x < (unsigned)A.W &&
                             (unsigned)ys < (unsigned)s.Hs && (unsigned)xs < (unsigned)s.Ws;
             ea[i] = ok ? abase_e + aoff[i] : -1;
-            const wg_f32x4 *pp = reinterpret_cast<const wg_f32x4 *>(sx + (ok ? ea[i] : 0));
+            const f32x4 *pp = reinterpret_cast<const f32x4 *>(sx + (ok ? ea[i] : 0));
             pa_[i][0] = pp[0];
             pa_[i][1] = pp[1];
         }
@@ -821,18 +794,18 @@ __global__ __launch_bounds__(NT32) void wgrad_f32_kernel(WgradArgs A) {
         for (int i = 0; i < NG; ++i) {
             const bool ok = cok_g && y0 + (gyx[i] >> 16) < A.H && x0 + (gyx[i] & 0xffff) < A.W;
             const size_t e = ok ? gbase_e + goff[i] : 0;
-            const wg_f32x4 *pp = reinterpret_cast<const wg_f32x4 *>(gx + e);
+            const f32x4 *pp = reinterpret_cast<const f32x4 *>(gx + e);
             pg_[i][0] = pp[0];
             pg_[i][1] = pp[1];
             gvalid |= (ok ? 1u : 0u) << i;
         }
     };
     auto commit = [&]() {
-        wg_f32x4 rr[NA][2];
+        f32x4 rr[NA][2];
         if (sr) {
 #pragma unroll
             for (int i = 0; i < NA; ++i) {
-                const wg_f32x4 *pp = reinterpret_cast<const wg_f32x4 *>(sr + (ea[i] >= 0 ? ea[i] : 0));
+                const f32x4 *pp = reinterpret_cast<const f32x4 *>(sr + (ea[i] >= 0 ? ea[i] : 0));
                 rr[i][0] = pp[0];
                 rr[i][1] = pp[1];
             }
@@ -857,7 +830,7 @@ __global__ __launch_bounds__(NT32) void wgrad_f32_kernel(WgradArgs A) {
 #pragma unroll
                     for (int j = 0; j < 8; ++j) x[j] = fmaxf(x[j], 0.f);
                 }
-                wg_split8(x, hi, lo);
+                split8_scalar(x, hi, lo);
             }
             unsigned char *d = smem + (v / VA) * PA + slot_a * 16;
             *reinterpret_cast<u32x4 *>(d) = hi;
@@ -869,7 +842,7 @@ __global__ __launch_bounds__(NT32) void wgrad_f32_kernel(WgradArgs A) {
             u32x4 hi = {0u, 0u, 0u, 0u}, lo = {0u, 0u, 0u, 0u};
             if (gvalid & (1u << i)) {
                 const float x[8] = {pg_[i][0][0], pg_[i][0][1], pg_[i][0][2], pg_[i][0][3], pg_[i][1][0], pg_[i][1][1], pg_[i][1][2], pg_[i][1][3]};
-                wg_split8(x, hi, lo);
+                split8_scalar(x, hi, lo);
             }
             unsigned char *d = smem + 2 * A_BYTES + pix * PG + slot_g * 16;
             *reinterpret_cast<u32x4 *>(d) = hi;
@@ -919,9 +892,7 @@ __global__ __launch_bounds__(NT32) void wgrad_f32_kernel(WgradArgs A) {
 #pragma unroll
                 for (int t = 0; t < TAPS; ++t) {
                     const bf16x8 ah = rh[(ky + t / 3) & 3][t % 3], al = rl[(ky + t / 3) & 3][t % 3];
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, gqh[ky & 1], acc[t], 0, 0, 0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, gql[ky & 1], acc[t], 0, 0, 0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, gqh[ky & 1], acc[t], 0, 0, 0);
+                    acc[t] = mfma3(acc[t], ah, al, gqh[ky & 1], gql[ky & 1]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -935,9 +906,7 @@ __global__ __launch_bounds__(NT32) void wgrad_f32_kernel(WgradArgs A) {
 #pragma unroll
                 for (int t = 0; t < TAPS; ++t) {
                     const bf16x8 ah = frag2(abase + tap_off(t), PA), al = frag2(abase + tap_off(t) + A_BYTES, PA);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, gh, acc[t], 0, 0, 0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, gl, acc[t], 0, 0, 0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, gh, acc[t], 0, 0, 0);
+                    acc[t] = mfma3(acc[t], ah, al, gh, gl);
                 }
             }
         }
@@ -1074,8 +1043,8 @@ __global__ __launch_bounds__(512) void wgrad_ws32_kernel(WgradArgs A) {
         const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(sx), 0, (int)((unsigned)A.N * s.Hs * rs * 4u), 0x00020000);
         const __amdgpu_buffer_rsrc_t rs_r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(sr ? sr : sx), 0, (int)((unsigned)A.N * s.Hs * rs * 4u), 0x00020000);
         const __amdgpu_buffer_rsrc_t rs_g = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(gx), 0, (int)((unsigned)A.N * A.H * A.W * A.Cout * 4u), 0x00020000);
-        auto bload = [](__amdgpu_buffer_rsrc_t r, unsigned voff) -> wg_f32x4 {
-            return __builtin_bit_cast(wg_f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, 0, 0));
+        auto bload = [](__amdgpu_buffer_rsrc_t r, unsigned voff) -> f32x4 {
+            return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, 0, 0));
         };
         // what depends on the thread only: halo coordinates (31 = a vector that never exists: the masks' bit 31 is always set), byte
         // offsets inside a tile and LDS addresses of its vectors
@@ -1116,7 +1085,7 @@ __global__ __launch_bounds__(512) void wgrad_ws32_kernel(WgradArgs A) {
             c_ty = rem / tiles_x; c_tx = rem - c_ty * tiles_x;
         }
         const int d_n = A.ksplit / tiles_img, d_rem = A.ksplit - d_n * tiles_img, d_ty = d_rem / tiles_x, d_tx = d_rem - d_ty * tiles_x;
-        wg_f32x4 pa_[2][NA][2], pg_[2][NG][2];
+        f32x4 pa_[2][NA][2], pg_[2][NG][2];
         unsigned av[2][NA];                  // byte offsets of the input vectors (read again for a residual operand), ~0 = zero fill
         auto issue = [&](auto rc) {
             constexpr int R = decltype(rc)::value;
@@ -1151,7 +1120,7 @@ __global__ __launch_bounds__(512) void wgrad_ws32_kernel(WgradArgs A) {
         auto commit = [&](auto rc, int bufi) {
             constexpr int R = decltype(rc)::value;
             unsigned char *nb = smem + bufi * STAGE;
-            wg_f32x4 rr[NA][2];
+            f32x4 rr[NA][2];
             if (has_res) {
 #pragma unroll
                 for (int i = 0; i < NA; ++i) {
@@ -1168,7 +1137,7 @@ __global__ __launch_bounds__(512) void wgrad_ws32_kernel(WgradArgs A) {
                     const float lim = __builtin_bit_cast(float, av[R][i] == ~0u ? 0u : 0x7f800000u);
 #pragma unroll
                     for (int j = 0; j < 8; ++j) x[j] = __builtin_amdgcn_fmed3f(fmaf(x[j], sc[j], sh[j]), 0.f, lim);
-                    wg_split8(x, hi, lo);
+                    split8_scalar(x, hi, lo);
                 } else {
                     if (XF != 0 && on) {
 #pragma unroll
@@ -1183,7 +1152,7 @@ __global__ __launch_bounds__(512) void wgrad_ws32_kernel(WgradArgs A) {
 #pragma unroll
                         for (int j = 0; j < 8; ++j) x[j] = fmaxf(x[j], 0.f);
                     }
-                    wg_split8(x, hi, lo);
+                    split8_scalar(x, hi, lo);
                     if (XF != 0) {                                           // (plain sources: the zero fill arrived as zeros)
                         const unsigned keep = av[R][i] == ~0u ? 0u : 0xffffffffu;
                         hi &= keep;
@@ -1199,7 +1168,7 @@ __global__ __launch_bounds__(512) void wgrad_ws32_kernel(WgradArgs A) {
             for (int i = 0; i < NG; ++i) {
                 const float x[8] = {pg_[R][i][0][0], pg_[R][i][0][1], pg_[R][i][0][2], pg_[R][i][0][3], pg_[R][i][1][0], pg_[R][i][1][1], pg_[R][i][1][2], pg_[R][i][1][3]};
                 u32x4 hi, lo;
-                wg_split8(x, hi, lo);                                        // (no mask: the range check zero-filled it)
+                split8_scalar(x, hi, lo);                                        // (no mask: the range check zero-filled it)
                 *reinterpret_cast<u32x4 *>(nb + gdst[i]) = hi;
                 *reinterpret_cast<u32x4 *>(nb + G_PLANE + gdst[i]) = lo;
             }
@@ -1282,7 +1251,7 @@ __global__ __launch_bounds__(512) void wgrad_ws32_kernel(WgradArgs A) {
 #pragma unroll
             for (int tau = 0; tau < NTAU; ++tau) {
                 const int ky = tau / TAPS, t = tau % TAPS;
-                // small terms first (wgrad_f32_kernel's order); behind every MFMA a scheduling fence and at most one fragment pair of a
+                // mfma3's order (split_bf16.h), written out: behind every MFMA a scheduling fence and at most one fragment pair of a
                 // later tap: program order is issue order
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[tau % RING], gh[ky & 1], acc[t], 0, 0, 0);
                 if (tau + PFD < NTAU) ah[(tau + PFD) % RING] = frag(a_off(tau + PFD), PA);
@@ -1342,36 +1311,34 @@ __global__ __launch_bounds__(512) void wgrad_ws32_kernel(WgradArgs A) {
 //   mode 0: Conv2d  dW[Cout][Cin][KH][KW]  (taps = KH*KW)
 //   mode 2: ConvTranspose2d k4 s2 p1  dW[Cin][Cout][4][4]   (npar 4 x taps 4)
 //   mode 3: ConvTranspose2d k2 s2     dW[Cin][Cout][2][2]   (npar 4 x taps 1)
-typedef float rf4 __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ void wgrad_reduce_body(const float *__restrict__ slab, int ksplit, int npar, int ci_blocks, int co_blocks,
                                                   int TAPS, int CI, int CO, int Csrc_real, int Cin_real, int src_coff, int Cout,
-                                                  int mode, float *__restrict__ dw, unsigned bidx, rf4 (*s_part)[64]) {
+                                                  int mode, float *__restrict__ dw, unsigned bidx, f32x4 (*s_part)[64]) {
     // block = 256 consecutive slab elements (64 threads x one 16-byte vector) x 4 interleaved k-lanes (k = kq, kq+4, ...); every thread
     // keeps eight slabs' vectors in flight (the pass is pure streaming: 256 slabs x 147 KB for a 64 x 64 layer; with one 4-byte load per
     // thread and four in flight it ran at 0.8 TB/s, 49 us per launch on the weight-gradient stream); fixed-order combine
     const size_t per_ks = (size_t)npar * ci_blocks * co_blocks * TAPS * CI * CO;      // a multiple of 1024 (CI * CO = 4096)
     const int e = threadIdx.x & 63, kq = threadIdx.x >> 6;
     const size_t i = ((size_t)bidx * 64 + e) * 4;
-    rf4 a[8];
+    f32x4 a[8];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) a[u] = rf4{0.f, 0.f, 0.f, 0.f};
+    for (int u = 0; u < 8; ++u) a[u] = f32x4{0.f, 0.f, 0.f, 0.f};
     if (i < per_ks) {
         const float *p = slab + i;
         int k = kq;
         for (; k + 28 < ksplit; k += 32) {
-            rf4 v[8];
+            f32x4 v[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const rf4 *>(p + (size_t)(k + 4 * u) * per_ks);
+            for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const f32x4 *>(p + (size_t)(k + 4 * u) * per_ks);
 #pragma unroll
             for (int u = 0; u < 8; ++u) a[u] += v[u];
         }
-        for (; k < ksplit; k += 4) a[0] += *reinterpret_cast<const rf4 *>(p + (size_t)k * per_ks);
+        for (; k < ksplit; k += 4) a[0] += *reinterpret_cast<const f32x4 *>(p + (size_t)k * per_ks);
     }
     s_part[kq][e] = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
     __syncthreads();
     if (kq != 0 || i >= per_ks) return;
-    const rf4 sv = (s_part[0][e] + s_part[1][e]) + (s_part[2][e] + s_part[3][e]);
+    const f32x4 sv = (s_part[0][e] + s_part[1][e]) + (s_part[2][e] + s_part[3][e]);
     size_t r = i;
     const int co_l0 = r % CO; r /= CO;                           // four consecutive output channels (CO is a multiple of 32)
     const int ci_l = r % CI; r /= CI;
@@ -1411,7 +1378,7 @@ __device__ __forceinline__ void wgrad_reduce_body(const float *__restrict__ slab
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float *__restrict__ slab, int ksplit, int npar, int ci_blocks,
                                                            int co_blocks, int TAPS, int CI, int CO, int Csrc_real, int Cin_real,
                                                            int src_coff, int Cout, int mode, float *__restrict__ dw) {
-    __shared__ rf4 s_part[4][64];
+    __shared__ f32x4 s_part[4][64];
     wgrad_reduce_body(slab, ksplit, npar, ci_blocks, co_blocks, TAPS, CI, CO, Csrc_real, Cin_real, src_coff, Cout, mode, dw, blockIdx.x, s_part);
 }
 
@@ -1426,7 +1393,7 @@ struct ReduceDesc {
 static_assert(sizeof(ReduceDesc) == sizeof(cdnet_wgrad_reduce_desc), "cdnet_wgrad_reduce_desc layout");
 
 __global__ __launch_bounds__(256) void wgrad_reduce_batch_kernel(const ReduceDesc *__restrict__ tab, int n) {
-    __shared__ rf4 s_part[4][64];
+    __shared__ f32x4 s_part[4][64];
     const unsigned b = blockIdx.x;
     int lo = 0, hi = n - 1;
     while (lo < hi) {

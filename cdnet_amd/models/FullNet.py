@@ -82,6 +82,11 @@ def _round8(c):
     return (c + 7) // 8 * 8
 
 
+def _buf(x16, c):
+    """an NHWC buffer of c channels (stride rounded up to 8) for the windows x16, in x16's precision"""
+    return torch.empty(x16.shape[:3] + (_round8(c),), dtype=x16.dtype, device=x16.device)
+
+
 class _Conv:
     """one launch: the Conv2d, its optional BatchNorm, the packed weights and the folded scale / shift of the current precision"""
 
@@ -241,7 +246,8 @@ class FullNet(nn.Module):
         with logits f32 [N,K,H,W].  The batch runs in sub-batches whose block buffers stay under WORKSPACE_BYTES; a window's result does not
         depend on the batch it ran in."""
         if self.training and runtime.TAPE is None:
-            raise RuntimeError('FullNet is inference only here: call model.eval() first (training FullNet is not implemented)')
+            raise RuntimeError('FullNet is inference only outside a trainer: call model.eval() first (a training forward needs the tape of '
+                               'cdnet_amd.trainer.FullNetTrainer)')
         if not x16.is_cuda:
             raise RuntimeError('cdnet_amd.models.FullNet.FullNet runs on the MI355X only (no CPU fallback)')
         assert x16.dim() == 4 and x16.shape[3] == 16 and x16.dtype == runtime.act_dtype() and x16.is_contiguous(), 'packed NHWC [N,H,W,16] windows'
@@ -261,28 +267,37 @@ class FullNet(nn.Module):
             self._forward_nhwc(x16[s:s + sub], out[s:s + sub])
         return (out,)
 
-    def _forward_nhwc(self, x16, out):
+    def _walk(self, x16, out, step, rec=None):
+        """the network once, for both modes: stem, the dense layers' in-place appends (a bottleneck through its intermediate), the
+        transitions, conv2 into `out`.  step(c, src, src_stride, dst, dst_stride, dst_coff) runs one ConvLayer; rec, a TrainRecord, keeps
+        the block buffers and the bottlenecks' intermediates."""
         stem, blocks, final = self._rt
         N, H, W, _ = x16.shape
-        dt, dev = x16.dtype, x16.device
-
-        def buf(c):
-            return torch.empty((N, H, W, _round8(c)), dtype=dt, device=dev)
-        cur = buf(blocks[0][1].Cin)
-        stem.run(x16, 16, cur, cur.shape[3], 0, N, H, W)
+        cur = _buf(x16, blocks[0][1].Cin)
+        step(stem, x16, 16, cur, cur.shape[3], 0)
         for i, (layers, trans) in enumerate(blocks):
             cs = cur.shape[3]
+            if rec is not None:
+                rec.bufs.append(cur)
             for layer in layers:
                 if len(layer) == 1:                                    # BasicLayer: append in place
-                    layer[0].run(cur, cs, cur, cs, layer[0].Cin, N, H, W)
+                    step(layer[0], cur, cs, cur, cs, layer[0].Cin)
                 else:                                                  # BottleneckLayer: 1x1 to 4 * growth, then the dilated 3x3 appends
-                    mid = buf(layer[0].Cout)
-                    layer[0].run(cur, cs, mid, mid.shape[3], 0, N, H, W)
-                    layer[1].run(mid, mid.shape[3], cur, cs, layer[0].Cin, N, H, W)
-            nxt = buf(blocks[i + 1][1].Cin if i + 1 < len(blocks) else final.Cin)
-            trans.run(cur, cs, nxt, nxt.shape[3], 0, N, H, W)
+                    mid = _buf(x16, layer[0].Cout)
+                    step(layer[0], cur, cs, mid, mid.shape[3], 0)
+                    step(layer[1], mid, mid.shape[3], cur, cs, layer[0].Cin)
+                    if rec is not None:
+                        rec.mids[id(layer[0])] = mid
+            nxt = _buf(x16, blocks[i + 1][1].Cin if i + 1 < len(blocks) else final.Cin)
+            step(trans, cur, cs, nxt, nxt.shape[3], 0)
             cur = nxt
+        if rec is not None:
+            rec.bufs.append(cur)
         final.run(cur, cur.shape[3], out, 0, 0, N, H, W, nchw=True)
+
+    def _forward_nhwc(self, x16, out):
+        N, H, W, _ = x16.shape
+        self._walk(x16, out, lambda c, src, ss, dst, ds, coff: c.run(src, ss, dst, ds, coff, N, H, W))
 
     # ------------------------------------------------------------------------------------------------
     # training (fp32 precision mode): forward with a record for backward, and the backward walk
@@ -297,7 +312,6 @@ class FullNet(nn.Module):
     def _train_forward(self, x16):
         if runtime.PRECISION != 'fp32':
             raise NotImplementedError('FullNet trains in the fp32 precision mode only (runtime.set_precision("fp32"))')
-        stem, blocks, final = self._rt
         convs = self._convs()
         index = {id(c): k for k, c in enumerate(convs)}
         N, H, W, _ = x16.shape
@@ -308,35 +322,15 @@ class FullNet(nn.Module):
         ws = self._ws('bn', max(lib.cdnet_slice_bn_workspace_floats(P, c.Cout) for c in convs), dev)
         rec = TrainRecord(x16, (N, H, W), int(getattr(self, '_train_key', 0)), index)
 
-        def buf(c):
-            return torch.empty((N, H, W, _round8(c)), dtype=torch.float32, device=dev)
-
         def conv_bn(c, src, ss, dst, ds, coff):
-            z = buf(c.Cout)
+            z = _buf(x16, c.Cout)
             c.run(src, ss, z, z.shape[3], 0, N, H, W)             # (prepare_train left no scale / shift: the LeakyReLU output)
             c.bn_forward(z, dst, ds, coff, P, index[id(c)], rec.key, ws)
             rec.z[id(c)] = z
             if c.p_drop > 0:
                 rec.drops.append((index[id(c)], (N, H, W, c.Cout), c.p_drop))
-        cur = buf(blocks[0][1].Cin)
-        conv_bn(stem, x16, 16, cur, cur.shape[3], 0)
-        for i, (layers, trans) in enumerate(blocks):
-            cs = cur.shape[3]
-            rec.bufs.append(cur)
-            for layer in layers:
-                if len(layer) == 1:
-                    conv_bn(layer[0], cur, cs, cur, cs, layer[0].Cin)
-                else:
-                    mid = buf(layer[0].Cout)
-                    conv_bn(layer[0], cur, cs, mid, mid.shape[3], 0)
-                    conv_bn(layer[1], mid, mid.shape[3], cur, cs, layer[0].Cin)
-                    rec.mids[id(layer[0])] = mid
-            nxt = buf(blocks[i + 1][1].Cin if i + 1 < len(blocks) else final.Cin)
-            conv_bn(trans, cur, cs, nxt, nxt.shape[3], 0)
-            cur = nxt
-        rec.bufs.append(cur)
         out = torch.empty((N, self.output_channels, H, W), dtype=torch.float32, device=dev)
-        final.run(cur, cur.shape[3], out, 0, 0, N, H, W, nchw=True)
+        self._walk(x16, out, conv_bn, rec)
         runtime.TAPE.append(rec)
         return out
 

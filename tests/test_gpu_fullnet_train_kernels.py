@@ -92,6 +92,29 @@ def test_backward_data(case, accumulate):
     assert not bool((err > tol).any()), '%d elements out of tolerance, max err %g' % (int((err > tol).sum()), float(err.max()))
 
 
+@pytest.mark.parametrize('f32', [0, 1], ids=['bf16', 'fp32'])
+@pytest.mark.parametrize('case', [(24, 40, 9), (143, 286, 1), (3, 24, 9)], ids=lambda c: '%dto%d-t%d' % c)
+def test_backward_pack_is_forward_pack_of_swapped_mirrored_weights(case, f32):
+    """cdnet_dilated_pack_weights_bwd(w) == cdnet_dilated_pack_weights(w'), w'[ci][co][tap] = w[co][ci][taps - 1 - tap], bit for bit over the
+    whole buffer (the two entries' index expressions; the zero padding of the ragged tiles on both sides included).  The buffers start
+    from different fills, so an element that either entry leaves unwritten differs."""
+    import torch
+    from cdnet_amd import _lib
+    Cout, Cin, taps = case
+    k = 3 if taps == 9 else 1
+    w = torch.randn((Cout, Cin, k, k), generator=torch.Generator().manual_seed(400 + Cout)).cuda()
+    wt = w.permute(1, 0, 2, 3).flip(2, 3).contiguous()
+    n = _lib.load().cdnet_dilated_packed_weight_elems(Cout, Cin, taps, f32)       # GEMM-K over Cout, GEMM-N over Cin
+    assert n > 0
+    bwd = torch.full((n,), 0x1111, dtype=torch.int16, device='cuda')
+    fwd = torch.full((n,), 0x2222, dtype=torch.int16, device='cuda')
+    _lib.call('cdnet_dilated_pack_weights_bwd', _lib.ptr(w), _lib.ptr(bwd), Cin, Cout, taps, f32, _lib.stream_ptr())
+    _lib.call('cdnet_dilated_pack_weights', _lib.ptr(wt), _lib.ptr(fwd), Cout, Cin, taps, f32, _lib.stream_ptr())
+    torch.cuda.synchronize()
+    assert torch.equal(bwd, fwd), '%d of %d packed elements differ' % (int((bwd != fwd).sum()), n)
+    assert bool((bwd == 0).any()) and bool((bwd != 0).any())           # ragged tiles: the padding is there, and so are the weights
+
+
 def _wgrad(x, g, Cin, Cout, taps, d, xs, gs, dw=None):
     """x [N,H,W,xs], g [N,H,W,gs] device tensors -> dW [Cout,Cin,k,k] from the device"""
     import torch
