@@ -122,6 +122,7 @@ SIGNATURES = {
     'cdnet_conv_wgrad_slab_floats': (_sz, [_i] * 6),
     'cdnet_conv_backward_weight': (_i, [_vp, _i, _i, _i, _vp] + [_i] * 9 + [_vp, _vp, _i, _vp]),
     'cdnet_conv_backward_weight_last_form': (_i, []),
+    'cdnet_conv_forward_last_form': (_i, []),
     'cdnet_wgrad_reduce_desc_fill': (_i, [_i] * 9 + [_vp, _vp, _i, _i, _vp]),
     'cdnet_wgrad_reduce_batch': (_i, [_vp, _i, _i, _vp]),
     'cdnet_bn_backward_workspace_floats': (_sz, [_i]),

@@ -742,6 +742,7 @@ int launch_conv(const ConvArgs &A, hipStream_t st) {
     const int total_tiles = cdiv(A.W, TW) * cdiv(A.H, TH) * A.N * A.npar;
     const int ctiles = cdiv(A.Cout, BN);
     dim3 grid(total_tiles, ctiles, 1);
+    g_conv_last_form = conv_form(CDNET_CONV_FAMILY_FWD, BN, TAPS, 0, false, false, false, 0, 0, TH, CK);
     return launch_lds<conv_fwd_kernel<TH, TW, CK, BN, WM, WN, TAPS>>(grid, 256, LDS::bytes(XF_MAX), smem, st, "hipFuncSetAttribute(conv)", "conv_fwd_kernel", A);
 }
 
@@ -1389,6 +1390,7 @@ int try_launch_conv_ws(const ConvArgs &A, hipStream_t st, bool dry_run = false) 
     return with_bool(A.stats != nullptr, [&](auto st_c) {
         return with_int<0, 1, 2>(xf, [&](auto xf_c) {
             return with_bool(stream, [&](auto sm_c) {
+                g_conv_last_form = conv_form(CDNET_CONV_FAMILY_WS, BN, TAPS, decltype(xf_c)::value, decltype(st_c)::value, decltype(sm_c)::value);
                 return launch_lds<conv_ws_kernel<BN, TAPS, decltype(xf_c)::value, decltype(st_c)::value, decltype(sm_c)::value>>(
                     grid, 512, 160 * 1024, smem, st, "hipFuncSetAttribute(conv_ws)", "conv_ws_kernel", A);
             });
@@ -1549,6 +1551,12 @@ extern "C" int cdnet_pack_conv_weights_batch(const cdnet_pack_job *jobs, int n_j
     pack_weights_batch_kernel<<<blocks, 256, 0, st>>>((const PackDesc *)table, (int)host.size());
     return check_launch("cdnet_pack_conv_weights_batch");
 }
+
+// the launchers' record of the instantiation taken (conv_args.h; dry runs of cdnet_conv_ws_eligible and refused calls do not write it)
+namespace cdnet {
+thread_local int g_conv_last_form = 0;
+}
+extern "C" int cdnet_conv_forward_last_form(void) { return g_conv_last_form; }
 
 extern "C" int cdnet_conv_forward(const cdnet_conv_args *args, void *stream) {
     CDNET_REQUIRE(args, "cdnet_conv_forward: null args");

@@ -993,6 +993,7 @@ static int try_launch_ws16(const ConvArgs &A, hipStream_t st, bool dry_run) {
                 // bound by power and does not gain (round 5, without spills and with pair requests: 74.0 vs 72.5 us at 16 tiles, 298 vs 297.5 us at
                 // 64 - profiles/HISTORY.md); the one-tap form spilled.
                 if constexpr (STREAM_) {
+                    g_conv_last_form = conv_form(CDNET_CONV_FAMILY_WS16, BN, 9, XF, false, STREAM_, MIX_, 0, 3);
                     return launch_lds<conv_ws16_kernel<BN, XF, STREAM_, MIX_, 0, 4, decltype(pf_c)::value, true, true, PAIR_>>(
                         grid, 512, 160 * 1024, smem, st, "hipFuncSetAttribute(conv_ws16 k32)", "conv_ws16_kernel(k32)", A);
                 }
@@ -1005,9 +1006,11 @@ static int try_launch_ws16(const ConvArgs &A, hipStream_t st, bool dry_run) {
                 // tiles, where the L2 / Infinity Cache keep the line between its two pairs anyway, the pair form is 1-2 % faster and stays
                 const long long io_bytes = 2LL * A.N * A.H * A.W * (ctot + A.Cout);
                 if constexpr (!STREAM_ && PAIR_ && CDNET_WS16_QUAD_DEFAULT != 0) if (!(n0 & 3) && !(n1 & 3) && (io_bytes >= (512LL << 20) || (A.debug & CONV_DBG_WS16_QUAD))) {      // (tests: the quad form on small launches)
+                    g_conv_last_form = conv_form(CDNET_CONV_FAMILY_WS16, BN, 9, XF, false, STREAM_, MIX_, 0, 2);
                     return launch_lds<conv_ws16_kernel<BN, XF, STREAM_, MIX_, 0, 4, decltype(pf_c)::value, true, false, true, true>>(
                         grid, 512, 160 * 1024, smem, st, "hipFuncSetAttribute(conv_ws16 quad)", "conv_ws16_kernel(quad)", A);
                 }
+                g_conv_last_form = conv_form(CDNET_CONV_FAMILY_WS16, BN, 9, XF, false, STREAM_, MIX_, 0, 1);
                 return launch_lds<conv_ws16_kernel<BN, XF, STREAM_, MIX_, 0, 4, decltype(pf_c)::value, true, false, PAIR_>>(
                     grid, 512, 160 * 1024, smem, st, "hipFuncSetAttribute(conv_ws16 out)", "conv_ws16_kernel(out)", A);
             }
@@ -1017,6 +1020,7 @@ static int try_launch_ws16(const ConvArgs &A, hipStream_t st, bool dry_run) {
         constexpr int NCS = decltype(ncs_c)::value;
         constexpr int PFD = decltype(pf_c)::value;
         constexpr int NS = 4;
+        g_conv_last_form = conv_form(CDNET_CONV_FAMILY_WS16, BN, 9, XF, false, STREAM, MIX, NCS, 0);
         return launch_lds<conv_ws16_kernel<BN, XF, STREAM, MIX, NCS, NS, PFD, false>>(grid, 512, 160 * 1024, smem, st, "hipFuncSetAttribute(conv_ws16)", "conv_ws16_kernel", A);
     };
     using C0 = std::integral_constant<int, 0>;

@@ -398,6 +398,7 @@ int launch_conv32(const ConvArgs &A, hipStream_t st) {
     for (int i = 0; i < A.nsrc; ++i) ctot += A.src[i].C;
     const int smem = L::bytes(ctot);
     dim3 grid(cdiv(A.W, TW) * cdiv(A.H, TH) * A.N * A.npar, cdiv(A.Cout, BN), 1);
+    g_conv_last_form = conv_form(CDNET_CONV_FAMILY_F32, BN, TAPS, 0, false, false, false, 0, 0, TH);
     return launch_lds<conv_f32_kernel<TH, TW, BN, WM, WN, TAPS>>(grid, 256, L::bytes(XF_MAX), smem, st, "hipFuncSetAttribute(conv32)", "conv_f32_kernel", A);
 }
 
@@ -592,6 +593,7 @@ int launch_conv1x1_stream(const ConvArgs &A, hipStream_t st) {
     dim3 grid((unsigned)G, ctiles, 1);
     return with_bool(A.src[0].scale != nullptr, [&](auto xf_c) {
         return with_bool(A.eres != nullptr, [&](auto er_c) {
+            g_conv_last_form = conv_form(CDNET_CONV_FAMILY_STREAM, BN, 1, decltype(xf_c)::value ? 1 : 0, false, false, false, 0, 0, 16, 16, NCH, decltype(er_c)::value);
             conv1x1_f32_stream_kernel<BN, NCH, decltype(xf_c)::value, decltype(er_c)::value><<<grid, 256, 0, st>>>(A);
             return check_launch("conv1x1_f32_stream_kernel");
         });

@@ -760,6 +760,7 @@ static int try_launch_ws32(const ConvArgs &A, hipStream_t st, bool dry_run) {
         constexpr int XF = decltype(xf_c)::value;
         constexpr bool STATS = decltype(st_c)::value;
         constexpr int NCS = decltype(ncs_c)::value;
+        g_conv_last_form = conv_form(CDNET_CONV_FAMILY_WS32, BN, 9, XF, STATS, false, false, NCS, 0);
         return launch_lds<conv_ws32_kernel<BN, XF, STATS, false, NCS>>(grid, 512, 160 * 1024, smem, st, "hipFuncSetAttribute(conv_ws32)", "conv_ws32_kernel", A);
     };
     auto launch = [&](auto xf_c, auto st_c) -> int {
@@ -781,6 +782,7 @@ static int try_launch_ws32(const ConvArgs &A, hipStream_t st, bool dry_run) {
     if (bns) {
         if constexpr (BN == 64) {
             return with_int<0, 1, 2>(xf, [&](auto xf_c) {
+                g_conv_last_form = conv_form(CDNET_CONV_FAMILY_WS32, 64, 9, decltype(xf_c)::value, false, false, false, 0, 1);
                 return launch_lds<conv_ws32_kernel<64, decltype(xf_c)::value, false, true>>(grid, 512, 160 * 1024, smem, st, "hipFuncSetAttribute(conv_ws32 bns)", "conv_ws32_kernel(bns)", A);
             });
         }
@@ -789,11 +791,13 @@ static int try_launch_ws32(const ConvArgs &A, hipStream_t st, bool dry_run) {
     if (mix) {
         // (the one-tap second source exists for the plain and the generic transform only: the fast one runs as generic)
         return with_int<0, 2>(xf == 1 ? 2 : xf, [&](auto xf_c) {
+            g_conv_last_form = conv_form(CDNET_CONV_FAMILY_WS32, BN, 9, decltype(xf_c)::value, false, false, true, 0, 2);
             return launch_lds<conv_ws32_kernel<BN, decltype(xf_c)::value, false, false, 0, true>>(grid, 512, 160 * 1024, smem, st, "hipFuncSetAttribute(conv_ws32 mix)", "conv_ws32_kernel(mix)", A);
         });
     }
     if (!pool) return with_bool(A.stats != nullptr, [&](auto st_c) { return with_int<0, 1, 2>(xf, [&](auto xf_c) { return launch(xf_c, st_c); }); });
     if constexpr (BN == 64) {
+        g_conv_last_form = conv_form(CDNET_CONV_FAMILY_WS32, 64, 9, 0, false, false, false, 0, 3);
         return launch_lds<conv_ws32_kernel<64, 0, false, false, 0, false, true>>(grid, 512, 160 * 1024, smem, st, "hipFuncSetAttribute(conv_ws32 pool)", "conv_ws32_kernel(pool)", A);
     }
     return -1;

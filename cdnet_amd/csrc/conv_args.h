@@ -74,6 +74,15 @@ static_assert(sizeof(ConvSrc) == sizeof(cdnet_conv_src), "ConvSrc layout");
 static_assert(sizeof(ConvArgs) == sizeof(cdnet_conv_args), "ConvArgs layout");
 
 namespace cdnet {
+// which instantiation the last launch of this thread took (cdnet_conv_forward_last_form; host only, bit layout in cdnet_hip.h): every
+// launcher of conv.hip / conv16ws.hip / conv32.hip / conv32ws.hip writes it just before its launch, the tests assert it
+extern thread_local int g_conv_last_form;
+constexpr int conv_form(int family, int bn, int taps, int xf = 0, bool stats = false, bool stream = false, bool mix = false, int ncs = 0,
+                        int site = 0, int tile = 16, int ck = 16, int nch = 0, bool eres = false) {
+    return family | ((bn == 128 ? 2 : (bn == 64 ? 1 : 0)) << 4) | (taps << 6) | (xf << 10) | ((stats ? 1 : 0) << 12) | ((stream ? 1 : 0) << 13) |
+           ((mix ? 1 : 0) << 14) | (ncs << 15) | (site << 17) | ((tile == 8 ? 1 : 0) << 20) | ((ck == 64 ? 2 : (ck == 32 ? 1 : 0)) << 21) |
+           (nch << 23) | ((eres ? 1 : 0) << 26);
+}
 // conv32.hip: the fp32-storage / split-bf16x3 variant
 int conv_forward_f32(const ConvArgs &A, hipStream_t st);
 // conv32ws.hip: its wave-specialised persistent form (3x3, full 16x16 tiles, >= 4 chunks); -1 = not eligible

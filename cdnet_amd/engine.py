@@ -218,7 +218,7 @@ CONV_DEBUG = 0        # cdnet_conv_args.debug of every launch (tests: 32 = conv_
 
 def conv_forward(srcs, wpacked, Cout, cfg, taps=9, transposed=False, bias=None, oscale=None, oshift=None,
                  orelu=False, out=None, stats=None, H=None, W=None, out_dtype=torch.bfloat16, eres=None, query_ws=False, bns=None, taps1=0, pool_out=None, dot=None,
-                 pad_chunks=0, debug_or=0):
+                 pad_chunks=0, debug_or=0, out_coff=0):
     """Launch one convolution.  srcs: list of Src (1 or 2).  Returns (out, stats).  fp32 sources select the fp32-precision
     kernels (`wpacked` must then be the split pack and the output is fp32)."""
     tile, CK, BN = cfg[:3]
@@ -253,7 +253,7 @@ def conv_forward(srcs, wpacked, Cout, cfg, taps=9, transposed=False, bias=None, 
         stats = torch.empty((N * npar * ntiles, 2, Cout), dtype=torch.float32, device=s0.x.device)
     a.w, a.bias, a.oscale, a.oshift = _dp(wpacked), _dp(bias), _dp(oscale), _dp(oshift)
     a.orelu = int(orelu)
-    a.out, a.Cout, a.out_cstride, a.out_coff = (None if out is None else out.data_ptr()), Cout, (Cout if out is None else out.shape[3]), 0
+    a.out, a.Cout, a.out_cstride, a.out_coff = (None if out is None else out.data_ptr()), Cout, (Cout if out is None else out.shape[3]), out_coff      # (out_coff: `out` is a wider tensor, channels [out_coff, out_coff + Cout) are written)
     a.stats = _dp(stats)
     a.N, a.H, a.W = N, H, W
     # pad_chunks (two plain 16-bit sources only): that many more chunks than the second source has channels for - their packed

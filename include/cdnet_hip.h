@@ -342,6 +342,23 @@ int cdnet_pack_conv_weights_batch(const cdnet_pack_job *jobs, int n_jobs, void *
                                   void *stream);
 int cdnet_conv_forward(const cdnet_conv_args *args, void *stream);
 
+/* The kernel instantiation the calling thread's last cdnet_conv_forward launched (host-side record, thread-local like
+ * cdnet_last_error; 0 before the first launch; a refused call leaves it as it was).  For tests, which assert the dispatch form of
+ * every case.  Bit layout (a field a family has no template argument for is 0):
+ *   bits 0-3 family (CDNET_CONV_FAMILY_*), 4-5 BN (0 = 32, 1 = 64, 2 = 128), 6-9 TAPS, 10-11 XF (source transform form: 0 plain,
+ *   1 fast, 2 generic; conv1x1_f32_stream_kernel: 1 = with scale / shift), bit 12 STATS, bit 13 STREAM (weights streamed through the
+ *   LDS), bit 14 MIX (one-tap second source), bits 15-16 NCS (small-chunk-count form), bits 17-19 launch site (conv_ws16_kernel:
+ *   0 direct stores, 1 out image with pair requests, 2 out image with quad requests, 3 streamed 16x16x32; conv_ws32_kernel: 0 plain,
+ *   1 BatchNorm-backward sums, 2 mix, 3 pool), bit 20 tile (0 = 16 x 16, 1 = 8 x 8), bits 21-22 CK (0 = 16, 1 = 32, 2 = 64),
+ *   bits 23-25 NCH (chunks of conv1x1_f32_stream_kernel), bit 26 ERES (its fused residual epilogue). */
+#define CDNET_CONV_FAMILY_FWD    1   /* conv_fwd_kernel */
+#define CDNET_CONV_FAMILY_WS     2   /* conv_ws_kernel */
+#define CDNET_CONV_FAMILY_WS16   3   /* conv_ws16_kernel */
+#define CDNET_CONV_FAMILY_F32    4   /* conv_f32_kernel */
+#define CDNET_CONV_FAMILY_STREAM 5   /* conv1x1_f32_stream_kernel */
+#define CDNET_CONV_FAMILY_WS32   6   /* conv_ws32_kernel */
+int cdnet_conv_forward_last_form(void);
+
 /* ------------------------------------------------------------------------------------------------------
  * Dilated dense-block convolution (dilated.hip): FullNet's ConvLayer (models/FullNet.py:14-36: Conv2d(dilation, bias=False) ->
  * LeakyReLU -> BatchNorm2d, then torch.cat([x, out], 1)) and its stem / transition / final convolutions (:90-138), eval mode.  NHWC:
