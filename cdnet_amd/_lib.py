@@ -107,6 +107,10 @@ SIGNATURES = {
     'cdnet_slice_bn_train_forward': (_i, [_vp, _vp]),
     'cdnet_slice_bn_train_backward': (_i, [_vp, _vp]),
     'cdnet_dropout_mask': (_i, [C.c_ulonglong, _i, _sz, _f, _vp, _vp]),
+    'cdnet_maxpool2_forward': (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    'cdnet_maxpool2_backward': (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
+    'cdnet_upsample4_bilinear_forward': (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    'cdnet_upsample4_bilinear_backward': (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp]),
     'cdnet_src_materialize': (_i, [_vp, _i, _i, _i, _vp, _vp]),
     'cdnet_input_pack': (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     'cdnet_input_pack_f32': (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),

@@ -16,6 +16,9 @@ dropout) into the slice of the block buffer; backward mirrors the in-place appen
 buffer of its block, the dense layers run in reverse order, each reading its own slice and accumulating into the channels in front of it
 (cdnet_slice_bn_train_backward, cdnet_dilated_conv_backward_weight, cdnet_dilated_conv_backward_data).  Without a tape a forward in training
 mode raises.
+
+`FCN_pooling` (:141-193), a subclass, is the same network with a 2x2 max-pool behind trans1..trans4 and a 4x bilinear up-sampling behind trans5
+and trans6 (csrc/resample.hip): the walks below carry a map size per block, which for FullNet is one size throughout.
 """
 import ctypes as C
 import math
@@ -82,9 +85,10 @@ def _round8(c):
     return (c + 7) // 8 * 8
 
 
-def _buf(x16, c):
-    """an NHWC buffer of c channels (stride rounded up to 8) for the windows x16, in x16's precision"""
-    return torch.empty(x16.shape[:3] + (_round8(c),), dtype=x16.dtype, device=x16.device)
+def _buf(x16, c, hw=None):
+    """an NHWC buffer of c channels (stride rounded up to 8) for the windows x16 (hw: at another map size), in x16's precision"""
+    shape = x16.shape[:3] if hw is None else (x16.shape[0],) + tuple(hw)
+    return torch.empty(shape + (_round8(c),), dtype=x16.dtype, device=x16.device)
 
 
 class _Conv:
@@ -208,6 +212,12 @@ class FullNet(nn.Module):
         self.n_blocks, self.growth_rate = len(dilations), growth_rate
         self._rt = None
 
+    RESAMPLE = {}                              # block index -> what follows its transition, 'pool' or 'up' (FCN_pooling); FullNet: nothing
+
+    def _map_sizes(self, H, W):
+        """(h, w) of every block's buffer and, last, of conv2's input"""
+        return [(H, W)] * (self.n_blocks + 1)
+
     @property
     def final_conv(self):
         """the classifier under the name pipeline.mask_channels asks a one-output network for (a property: no extra state_dict key)"""
@@ -269,35 +279,42 @@ class FullNet(nn.Module):
 
     def _walk(self, x16, out, step, rec=None):
         """the network once, for both modes: stem, the dense layers' in-place appends (a bottleneck through its intermediate), the
-        transitions, conv2 into `out`.  step(c, src, src_stride, dst, dst_stride, dst_coff) runs one ConvLayer; rec, a TrainRecord, keeps
-        the block buffers and the bottlenecks' intermediates."""
+        transitions, conv2 into `out`.  step(c, src, src_stride, dst, dst_stride, dst_coff, hw) runs one ConvLayer on maps of hw = (h, w);
+        rec, a TrainRecord, keeps the block buffers and the bottlenecks' intermediates.  A transition with a resampling step behind it
+        (FCN_pooling) writes a compact temporary that _resample_forward resamples into the next block's base channels."""
         stem, blocks, final = self._rt
         N, H, W, _ = x16.shape
-        cur = _buf(x16, blocks[0][1].Cin)
-        step(stem, x16, 16, cur, cur.shape[3], 0)
+        sizes = self._map_sizes(H, W)
+        cur = _buf(x16, blocks[0][1].Cin, sizes[0])
+        step(stem, x16, 16, cur, cur.shape[3], 0, sizes[0])
         for i, (layers, trans) in enumerate(blocks):
-            cs = cur.shape[3]
+            cs, hw = cur.shape[3], sizes[i]
             if rec is not None:
                 rec.bufs.append(cur)
             for layer in layers:
                 if len(layer) == 1:                                    # BasicLayer: append in place
-                    step(layer[0], cur, cs, cur, cs, layer[0].Cin)
+                    step(layer[0], cur, cs, cur, cs, layer[0].Cin, hw)
                 else:                                                  # BottleneckLayer: 1x1 to 4 * growth, then the dilated 3x3 appends
-                    mid = _buf(x16, layer[0].Cout)
-                    step(layer[0], cur, cs, mid, mid.shape[3], 0)
-                    step(layer[1], mid, mid.shape[3], cur, cs, layer[0].Cin)
+                    mid = _buf(x16, layer[0].Cout, hw)
+                    step(layer[0], cur, cs, mid, mid.shape[3], 0, hw)
+                    step(layer[1], mid, mid.shape[3], cur, cs, layer[0].Cin, hw)
                     if rec is not None:
                         rec.mids[id(layer[0])] = mid
-            nxt = _buf(x16, blocks[i + 1][1].Cin if i + 1 < len(blocks) else final.Cin)
-            step(trans, cur, cs, nxt, nxt.shape[3], 0)
+            nxt = _buf(x16, blocks[i + 1][1].Cin if i + 1 < len(blocks) else final.Cin, sizes[i + 1])
+            if i not in self.RESAMPLE:
+                step(trans, cur, cs, nxt, nxt.shape[3], 0, hw)
+            else:
+                tmp = _buf(x16, trans.Cout, hw)
+                step(trans, cur, cs, tmp, tmp.shape[3], 0, hw)
+                self._resample_forward(i, tmp, nxt, trans.Cout, rec)
             cur = nxt
         if rec is not None:
             rec.bufs.append(cur)
         final.run(cur, cur.shape[3], out, 0, 0, N, H, W, nchw=True)
 
     def _forward_nhwc(self, x16, out):
-        N, H, W, _ = x16.shape
-        self._walk(x16, out, lambda c, src, ss, dst, ds, coff: c.run(src, ss, dst, ds, coff, N, H, W))
+        N = x16.shape[0]
+        self._walk(x16, out, lambda c, src, ss, dst, ds, coff, hw: c.run(src, ss, dst, ds, coff, N, hw[0], hw[1]))
 
     # ------------------------------------------------------------------------------------------------
     # training (fp32 precision mode): forward with a record for backward, and the backward walk
@@ -319,16 +336,17 @@ class FullNet(nn.Module):
         lib = _lib.load()
         for c in convs:
             c.prepare_train(dev)
-        ws = self._ws('bn', max(lib.cdnet_slice_bn_workspace_floats(P, c.Cout) for c in convs), dev)
+        ws = self._ws('bn', max(lib.cdnet_slice_bn_workspace_floats(P, c.Cout) for c in convs), dev)     # (P: the largest map's)
         rec = TrainRecord(x16, (N, H, W), int(getattr(self, '_train_key', 0)), index)
 
-        def conv_bn(c, src, ss, dst, ds, coff):
-            z = _buf(x16, c.Cout)
-            c.run(src, ss, z, z.shape[3], 0, N, H, W)             # (prepare_train left no scale / shift: the LeakyReLU output)
-            c.bn_forward(z, dst, ds, coff, P, index[id(c)], rec.key, ws)
+        def conv_bn(c, src, ss, dst, ds, coff, hw):
+            h, w = hw
+            z = _buf(x16, c.Cout, hw)
+            c.run(src, ss, z, z.shape[3], 0, N, h, w)             # (prepare_train left no scale / shift: the LeakyReLU output)
+            c.bn_forward(z, dst, ds, coff, N * h * w, index[id(c)], rec.key, ws)
             rec.z[id(c)] = z
             if c.p_drop > 0:
-                rec.drops.append((index[id(c)], (N, H, W, c.Cout), c.p_drop))
+                rec.drops.append((index[id(c)], (N, h, w, c.Cout), c.p_drop))
         out = torch.empty((N, self.output_channels, H, W), dtype=torch.float32, device=dev)
         self._walk(x16, out, conv_bn, rec)
         runtime.TAPE.append(rec)
@@ -342,13 +360,15 @@ class FullNet(nn.Module):
         lib = _lib.load()
         convs = self._convs()
         ws = self._ws('bn', max(lib.cdnet_slice_bn_workspace_floats(P, c.Cout) for c in convs), dev)
-        wws = self._ws('wgrad', max(lib.cdnet_dilated_wgrad_workspace_bytes(N, H, W, c.Cin, c.Cout, c.taps) for c in convs) // 4, dev)
+        sizes = self._map_sizes(H, W)
+        wws = self._ws('wgrad', max(lib.cdnet_dilated_wgrad_workspace_bytes(N, h, w, c.Cin, c.Cout, c.taps)
+                                    for h, w in set(sizes) for c in convs) // 4, dev)
         gmax = max(_round8(c.Cout) for c in convs)
         gflat = self._ws('g', P * gmax, dev)                      # g, the gradient of a raw convolution output: one compact scratch
 
-        def bn_back(c, dy, dy_stride, dy_coff):
+        def bn_back(c, dy, dy_stride, dy_coff, hw=(H, W)):
             gs = _round8(c.Cout)
-            c.bn_backward(dy, dy_stride, dy_coff, rec.z[id(c)], gflat, gs, P, index[id(c)], key, ws)
+            c.bn_backward(dy, dy_stride, dy_coff, rec.z[id(c)], gflat, gs, N * hw[0] * hw[1], index[id(c)], key, ws)
             return gs
         dl = runtime.input_pack(dlogits)                          # [N,H,W,16] fp32
         last = rec.bufs[-1]
@@ -358,29 +378,97 @@ class FullNet(nn.Module):
         for i in reversed(range(len(blocks))):
             layers, trans = blocks[i]
             cur = rec.bufs[i]
-            cs = cur.shape[3]
-            gs = bn_back(trans, dB, dB.shape[3], 0)
-            trans.weight_grad(cur, cs, gflat, gs, N, H, W, wws)
+            cs, hw = cur.shape[3], sizes[i]
+            h, w = hw
+            if i in self.RESAMPLE:                                 # the next block's base channels, resampled back to this map
+                dB = self._resample_backward(i, dB, trans.Cout, rec)
+            gs = bn_back(trans, dB, dB.shape[3], 0, hw)
+            trans.weight_grad(cur, cs, gflat, gs, N, h, w, wws)
             dcur = torch.empty_like(cur)
-            trans.backward_data(gflat, gs, dcur, cs, N, H, W, False)          # stores every channel of the block's gradient buffer
+            trans.backward_data(gflat, gs, dcur, cs, N, h, w, False)          # stores every channel of the block's gradient buffer
             for layer in reversed(layers):
                 coff = layer[0].Cin
-                gs = bn_back(layer[-1], dcur, cs, coff)                      # this layer's slice is complete: the later layers ran
+                gs = bn_back(layer[-1], dcur, cs, coff, hw)                  # this layer's slice is complete: the later layers ran
                 if len(layer) == 1:
-                    layer[0].weight_grad(cur, cs, gflat, gs, N, H, W, wws)
-                    layer[0].backward_data(gflat, gs, dcur, cs, N, H, W, True)
+                    layer[0].weight_grad(cur, cs, gflat, gs, N, h, w, wws)
+                    layer[0].backward_data(gflat, gs, dcur, cs, N, h, w, True)
                 else:
                     mid = rec.mids[id(layer[0])]
                     ms = mid.shape[3]
-                    layer[1].weight_grad(mid, ms, gflat, gs, N, H, W, wws)
+                    layer[1].weight_grad(mid, ms, gflat, gs, N, h, w, wws)
                     dmid = torch.empty_like(mid)
-                    layer[1].backward_data(gflat, gs, dmid, ms, N, H, W, False)
-                    gs = bn_back(layer[0], dmid, ms, 0)
-                    layer[0].weight_grad(cur, cs, gflat, gs, N, H, W, wws)
-                    layer[0].backward_data(gflat, gs, dcur, cs, N, H, W, True)
+                    layer[1].backward_data(gflat, gs, dmid, ms, N, h, w, False)
+                    gs = bn_back(layer[0], dmid, ms, 0, hw)
+                    layer[0].weight_grad(cur, cs, gflat, gs, N, h, w, wws)
+                    layer[0].backward_data(gflat, gs, dcur, cs, N, h, w, True)
             dB = dcur
         gs = bn_back(stem, dB, dB.shape[3], 0)
         stem.weight_grad(rec.x16, 16, gflat, gs, N, H, W, wws)
+
+
+class FCN_pooling(FullNet):
+    """FullNet's pooled ablation twin (reference models/FullNet.py:141-193): the same seven dense blocks and transitions with
+    nn.MaxPool2d(2, 2) behind trans1..trans4 and nn.UpsamplingBilinear2d(scale_factor=4) behind trans5 and trans6, so the blocks run on maps
+    of H, H/2, H/4, H/8, H/16, H/4 and H rows.  The six resampling modules are parameter-free children of `blocks` in the reference's
+    order; state_dict() is a seven-block FullNet's.  The resampling runs on csrc/resample.hip: a resampled transition writes a compact
+    temporary, cdnet_maxpool2_forward / cdnet_upsample4_bilinear_forward resample it into the next block's base channels; backward reads the
+    next block's gradient buffer as a slice (cdnet_maxpool2_backward with the stored arg-max bytes, cdnet_upsample4_bilinear_backward)."""
+    RESAMPLE = {0: 'pool', 1: 'pool', 2: 'pool', 3: 'pool', 4: 'up', 5: 'up'}
+
+    def __init__(self, color_channels, output_channels=2, n_layers=6, growth_rate=24, compress_ratio=0.5,
+                 drop_rate=0.1, dilations=(1, 2, 4, 8, 16, 4, 1), is_hybrid=True, layer_type='basic'):
+        dilations = tuple(dilations)
+        if len(dilations) < 7:
+            raise IndexError('FCN_pooling has seven dense blocks: %d dilations given' % len(dilations))      # (:162-163 dilation_list[i])
+        super().__init__(color_channels, output_channels, n_layers, growth_rate, compress_ratio, drop_rate, dilations[:7], is_hybrid, layer_type)
+        # the reference's children of `blocks`, in its order (:164-172); the parameters and their initial values are untouched
+        children = list(self.blocks.named_children())
+        self.blocks = nn.Sequential()
+        for name, mod in children:
+            self.blocks.add_module(name, mod)
+            if name.startswith('trans'):
+                i = int(name[5:])
+                if i <= 4:
+                    self.blocks.add_module('pool%d' % i, nn.MaxPool2d(kernel_size=2, stride=2))
+                elif i <= 6:
+                    self.blocks.add_module('upsample%d' % i, nn.UpsamplingBilinear2d(scale_factor=4))
+
+    def _map_sizes(self, H, W):
+        return [(H // d, W // d) for d in (1, 2, 4, 8, 16, 4, 1, 1)]
+
+    def _channels_per_pixel(self):
+        """FullNet's bound (taken at the full map size for every block) plus the widest transition's compact temporary"""
+        return super()._channels_per_pixel() + max(_round8(trans.Cout) for _, trans in self._rt[1])
+
+    def forward_packed(self, x16):
+        if x16.dim() == 4 and (x16.shape[1] % 16 or x16.shape[2] % 16):
+            raise ValueError('FCN_pooling needs H and W that are multiples of 16 (four 2x2 pools, then two 4x upsamplings): got %d x %d'
+                             % (x16.shape[1], x16.shape[2]))
+        return super().forward_packed(x16)
+
+    def _resample_forward(self, i, tmp, nxt, C, rec):
+        N, h, w, ts = tmp.shape
+        f32 = int(tmp.dtype == torch.float32)
+        if self.RESAMPLE[i] == 'pool':
+            idx = None
+            if rec is not None:
+                idx = rec.pool_idx[i] = torch.empty((N, h // 2, w // 2, ts), dtype=torch.uint8, device=tmp.device)
+            _lib.call('cdnet_maxpool2_forward', _lib.ptr(tmp), ts, _lib.ptr(nxt), nxt.shape[3], 0, _lib.ptr(idx), ts, N, h, w, C, f32,
+                      _lib.stream_ptr())
+        else:
+            _lib.call('cdnet_upsample4_bilinear_forward', _lib.ptr(tmp), ts, _lib.ptr(nxt), nxt.shape[3], 0, N, h, w, C, f32, _lib.stream_ptr())
+
+    def _resample_backward(self, i, dnxt, C, rec):
+        """the gradient of block i's compact transition output from channels [0, C) of the next block's gradient buffer"""
+        N, h, w, _ = rec.bufs[i].shape
+        d = torch.empty((N, h, w, _round8(C)), dtype=torch.float32, device=dnxt.device)
+        if self.RESAMPLE[i] == 'pool':
+            idx = rec.pool_idx[i]
+            _lib.call('cdnet_maxpool2_backward', _lib.ptr(dnxt), dnxt.shape[3], 0, _lib.ptr(idx), idx.shape[3], _lib.ptr(d), d.shape[3], N, h, w, C,
+                      _lib.stream_ptr())
+        else:
+            _lib.call('cdnet_upsample4_bilinear_backward', _lib.ptr(dnxt), dnxt.shape[3], 0, _lib.ptr(d), d.shape[3], N, h, w, C, _lib.stream_ptr())
+        return d
 
 
 class TrainRecord:
@@ -389,4 +477,5 @@ class TrainRecord:
     def __init__(self, x16, shape, key, index):
         self.x16, self.shape, self.key, self.index = x16, shape, key, index
         self.bufs, self.z, self.mids = [], {}, {}
+        self.pool_idx = {}                     # FCN_pooling: block index -> u8 [N,h/2,w/2,round8(C)], 2 dy + dx of every pooled element's arg-max
         self.drops = []                        # (layer index, [N,H,W,C], p) of every dropout applied: cdnet_dropout_mask regenerates its mask

@@ -494,6 +494,38 @@ int cdnet_slice_bn_train_backward(const cdnet_slice_bn_bwd_args *args, void *str
 int cdnet_dropout_mask(unsigned long long key, int layer, size_t count, float p_drop, uint8_t *mask, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * FCN_pooling's resampling steps (resample.hip): nn.MaxPool2d(kernel_size=2, stride=2) behind trans1..trans4 and
+ * nn.UpsamplingBilinear2d(scale_factor=4) behind trans5 and trans6 (models/FullNet.py:169-172, applied by nn.Sequential in :191), and
+ * their backward, which autograd derives in the reference (train_util.py:193-195 loss.backward()).  NHWC.  One side of every entry is
+ * compact (a channel stride alone), the other a channel slice [coff, coff + C) of a dense block's buffer: a transition's resampled output
+ * lands in the next block's base channels and is never copied.  C >= 1 is any count; channels outside the slice and the padding channels
+ * of either stride are not written.  Accesses are 16 bytes wide where every stride and offset is a multiple of 16 bytes and the bases are
+ * 16-byte aligned (the index bytes: 4 / 8 bytes wide), with a scalar tail; otherwise scalar.  No atomics: every output element comes
+ * from one thread in a fixed order of operations.  f32 = 1: fp32 tensors, f32 = 0: bf16.
+ * Argument errors (CDNET_E_ARG: a null pointer, a count < 1, odd H or W of the pool, a stride below coff + C, source and destination the
+ * same tensor, sizes beyond the 31-bit item index or 2^40 elements) are found before any HIP call. */
+
+/* y[n][h][w][y_coff + c] = max of x[n][2h + dy][2w + dx][c], dy, dx in {0, 1}: bit-equal to one of the four inputs (ATen's rule: a later
+ * element replaces the running maximum when it is greater or NaN).  idx (NULL: inference, not written) u8 [N][H/2][W/2][idx_cstride]
+ * gets 2 dy + dx of the window's first maximum in raster order.  H, W are the INPUT's sizes, both even. */
+int cdnet_maxpool2_forward(const void *x, int x_cstride, void *y, int y_cstride, int y_coff, uint8_t *idx, int idx_cstride, int N, int H, int W,
+                           int C, int f32, void *stream);
+/* dx[n][h][w][c] = dy[n][h/2][w/2][dy_coff + c] where idx names (h & 1, w & 1), 0 elsewhere; fp32.  Every element of channels [0, C) of dx
+ * is stored (no memset).  H, W are dx's sizes. */
+int cdnet_maxpool2_backward(const float *dy, int dy_cstride, int dy_coff, const uint8_t *idx, int idx_cstride, float *dx, int dx_cstride, int N,
+                            int H, int W, int C, void *stream);
+/* [N][Hs][Ws][C] -> [N][4 Hs][4 Ws][C], bilinear with align_corners=True.  Source coordinates in integers: q = h (Hs - 1), h0 = q / (H - 1),
+ * lambda = float(q % (H - 1)) / float(H - 1) with H = 4 Hs, h1 = min(h0 + 1, Hs - 1); columns alike; every weight is a correctly rounded
+ * quotient at any size.  y = (x00 (1 - lw) + x01 lw) (1 - lh) + (x10 (1 - lw) + x11 lw) lh in fp32 (bf16: rounded once, on the store).
+ * Hs = 1 or Ws = 1 copies along that axis.  Hs, Ws <= 8192. */
+int cdnet_upsample4_bilinear_forward(const void *x, int x_cstride, void *y, int y_cstride, int y_coff, int N, int Hs, int Ws, int C, int f32,
+                                     void *stream);
+/* the transpose in gather form, fp32: dx[n][hs][ws][c] = sum over the outputs (h, w) that read (hs, ws), in ascending (h, w) order, of
+ * (wy wx) dy[n][h][w][dy_coff + c] with the forward's weights wy, wx. */
+int cdnet_upsample4_bilinear_backward(const float *dy, int dy_cstride, int dy_coff, float *dx, int dx_cstride, int N, int Hs, int Ws, int C,
+                                      void *stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * Model-path streaming kernels (not convolutions).
  * cdnet_input_pack: f32 NCHW [N][C<=16][H][W] (the ToTensor output, my_transforms_direction.py:945) -> bf16 NHWC
  *   [N][H][W][16] with zero-padded channels.

@@ -2,6 +2,7 @@
 
     python tools/bench_fullnet.py [--windows 64] [--size 256] [--reps 5] [--warmup 2] [--layer-reps 20] [--skip-torch] [--only-layers]
     python tools/bench_fullnet.py --train [--batch 8] [--size 256] [--reps 5] [--warmup 2] [--skip-torch]
+    python tools/bench_fullnet.py --net FCN_pooling [--train] ...
 
 1. Eval forward of --windows windows of --size^2 through FullNet(3, 3).forward_packed, in both precision modes (device events, median).
 2. The same network run through the model's own nn containers (Conv2d -> LeakyReLU -> BatchNorm2d, torch.cat), fp32 and bf16
@@ -15,6 +16,9 @@ torch.optim.Adam) in the same process: device events, the two paths alternating 
 every library call: per entry point the calls, the time, its share, the bytes the calls must move at least (operands read once, results
 written once; an accumulating backward-data reads its target too; the BatchNorm passes count z and dy once although they read them twice)
 and the rate that makes.
+--net FCN_pooling: the pooled twin (FCN_pooling(3, 3), csrc/resample.hip behind six of its transitions) through the same two paths, without
+the single-layer part; the eval forward gets the per-entry table too, and every run starts with the box's float4 copy rate (cdnet_box_copy
+over 256 MiB), the figure the resampling entries' GB/s stand beside.
 One JSON line per measurement."""
 import argparse
 import ctypes as C
@@ -51,7 +55,7 @@ def torch_forward(model, x):
     """the reference's forward (models/FullNet.py:134-138) through the model's containers"""
     out = model.conv1(x)
     for name, mod in model.blocks.named_children():
-        if name.startswith('trans'):
+        if not name.startswith('block'):                    # a transition; FCN_pooling: also the pool / upsampling behind it
             out = mod(out)
             continue
         for layer in mod:
@@ -66,7 +70,7 @@ def torch_train_forward(model, x):
     """the reference's forward in train() (models/FullNet.py:25-52, :134-138): dropout on what a dense layer appends"""
     out = model.conv1(x)
     for name, mod in model.blocks.named_children():
-        if name.startswith('trans'):
+        if not name.startswith('block'):                    # a transition; FCN_pooling: also the pool / upsampling behind it
             out = mod(out)
             continue
         for layer in mod:
@@ -79,10 +83,27 @@ def torch_train_forward(model, x):
     return model.conv2(out)
 
 
-def _must_bytes(name, a):
-    """bytes a call has to move at least, from its argument struct (None: not one of the training kernels)"""
+def _must_bytes(name, args):
+    """bytes a call has to move at least, from its arguments (None: not one of the network's kernels)"""
+    if name == 'cdnet_maxpool2_forward':                      # (x, xs, y, ys, yoff, idx, is, N, H, W, C, f32, stream)
+        n, h, w, c, f32 = args[7:12]
+        es = 4 if f32 else 2
+        return n * h * w * c * es + n * (h // 2) * (w // 2) * c * (es + (0 if getattr(args[5], 'value', args[5]) is None else 1))
+    if name == 'cdnet_maxpool2_backward':                     # (dy, dys, dyoff, idx, is, dx, dxs, N, H, W, C, stream)
+        n, h, w, c = args[7:11]
+        return n * (h // 2) * (w // 2) * c * 5 + n * h * w * c * 4
+    if name == 'cdnet_upsample4_bilinear_forward':            # (x, xs, y, ys, yoff, N, Hs, Ws, C, f32, stream)
+        n, h, w, c, f32 = args[5:10]
+        return n * h * w * c * 17 * (4 if f32 else 2)
+    if name == 'cdnet_upsample4_bilinear_backward':           # (dy, dys, dyoff, dx, dxs, N, Hs, Ws, C, stream)
+        n, h, w, c = args[5:9]
+        return n * h * w * c * 17 * 4
+    a = getattr(args[0], '_obj', None) if args else None
+    if a is None:
+        return None
     if name == 'cdnet_dilated_conv_forward':
-        return a.N * a.H * a.W * (a.Cin + a.Cout) * 4 + a.Cin * a.Cout * a.taps * 4
+        es = 4 if a.f32 else 2
+        return a.N * a.H * a.W * (a.Cin * es + a.Cout * (4 if a.out_nchw else es)) + a.Cin * a.Cout * a.taps * es
     if name == 'cdnet_dilated_conv_backward_data':
         return a.N * a.H * a.W * (a.Cout + a.Cin * (2 if a.accumulate else 1)) * 4 + a.Cin * a.Cout * a.taps * 4
     if name == 'cdnet_dilated_conv_backward_weight':
@@ -94,7 +115,7 @@ def _must_bytes(name, a):
     return None
 
 
-def kernel_table(step):
+def kernel_table(step, what='fullnet_train_kernels'):
     """one step with events around every library call: per entry point calls, time, share, must-move bytes and the rate"""
     from cdnet_amd import _lib
     rows, real = [], _lib.call
@@ -104,7 +125,7 @@ def kernel_table(step):
         e0.record()
         real(name, *a)
         e1.record()
-        rows.append((name, _must_bytes(name, getattr(a[0], '_obj', None)) if a else None, e0, e1))
+        rows.append((name, _must_bytes(name, a), e0, e1))
     _lib.call = timed
     try:
         step()
@@ -119,9 +140,24 @@ def kernel_table(step):
         t[1] += e0.elapsed_time(e1)
         t[2] += must or 0
     for name, (calls, ms, must) in sorted(table.items(), key=lambda kv: -kv[1][1]):
-        say(what='fullnet_train_kernels', entry=name, calls=calls, ms=round(ms, 3), share=round(ms / total, 3),
+        say(what=what, entry=name, calls=calls, ms=round(ms, 3), share=round(ms / total, 3),
             must_bytes=must or None, GBps=round(must / ms / 1e6, 1) if must else None)
-    say(what='fullnet_train_kernels', entry='all library calls', calls=len(rows), ms=round(total, 3))
+    say(what=what, entry='all library calls', calls=len(rows), ms=round(total, 3))
+
+
+def bench_box(reps=20):
+    """the box's float4 copy rate (cdnet_box_copy, 256 MiB read + 256 MiB written per call)"""
+    from cdnet_amd import _lib
+    n = 256 << 20
+    src, dst = torch.zeros(n, dtype=torch.uint8, device='cuda'), torch.empty(n, dtype=torch.uint8, device='cuda')
+    st = _lib.stream_ptr()
+    ms = events(lambda: _lib.call('cdnet_box_copy', _lib.ptr(src), _lib.ptr(dst), n, st), reps, 3)
+    say(what='box_copy', bytes_moved=2 * n, ms=round(ms, 4), GBps=round(2 * n / ms / 1e6, 1))
+
+
+def network_class(args):
+    from cdnet_amd.models import FullNet as fn
+    return getattr(fn, args.net)
 
 
 def bench_train(args):
@@ -129,8 +165,8 @@ def bench_train(args):
     import _fullnet_ref as fr
     import _fullnet_train_ref as tr
     from oracle import train as ot
-    from cdnet_amd.models.FullNet import FullNet
     from cdnet_amd.trainer import FullNetTrainer
+    FullNet = network_class(args)
     cdnet_amd.set_precision('fp32')
     B, S = args.batch, args.size
     x, label, weight = (v.cuda() for v in tr.batch((B, 3, S, S), 5))
@@ -182,7 +218,7 @@ def bench_train(args):
             times[path].append(e0.elapsed_time(e1))
     med = {k: statistics.median(v) for k, v in times.items() if v}
     for k, v in med.items():
-        say(what='fullnet_train_step', path=k, precision='fp32', batch=B, size=S, ms=round(v, 3), tiles_per_s=round(B / v * 1e3, 1),
+        say(what='fullnet_train_step', path=k, net=args.net, precision='fp32', batch=B, size=S, ms=round(v, 3), tiles_per_s=round(B / v * 1e3, 1),
             runs=[round(t, 2) for t in times[k]])
     if 'torch' in med:
         say(what='fullnet_train_step', hip_over_torch_time=round(med['hip'] / med['torch'], 3))
@@ -192,7 +228,7 @@ def bench_network(args):
     import cdnet_amd
     import _fullnet_ref as fr
     from cdnet_amd import runtime
-    from cdnet_amd.models.FullNet import FullNet
+    FullNet = network_class(args)
     N, S = args.windows, args.size
     model = fr.randomize(FullNet(3, 3), 1).cuda().eval()
     x = fr.bf16_exact_input((N, 3, S, S), 2).cuda()
@@ -203,7 +239,9 @@ def bench_network(args):
         with torch.no_grad():
             ms = events(lambda: model.forward_packed(x16), args.reps, args.warmup)
             outs[prec] = model.forward_packed(x16)[0][:2].clone()
-        say(what='fullnet_forward', path='hip', precision=prec, windows=N, size=S, ms=round(ms, 3), ms_per_window=round(ms / N, 4))
+            if args.net != 'FullNet':
+                kernel_table(lambda: model.forward_packed(x16), what='fullnet_forward_kernels_' + prec)
+        say(what='fullnet_forward', path='hip', net=args.net, precision=prec, windows=N, size=S, ms=round(ms, 3), ms_per_window=round(ms / N, 4))
         del x16
         torch.cuda.empty_cache()
     if args.skip_torch:
@@ -215,7 +253,7 @@ def bench_network(args):
             ms = events(lambda: torch_forward(m, xt), args.reps, args.warmup)
             got = torch_forward(m, xt[:2]).float()
         err = float((got - outs[prec]).abs().max()) / float(got.abs().max())
-        say(what='fullnet_forward', path='torch', precision=prec, windows=N, size=S, ms=round(ms, 3), ms_per_window=round(ms / N, 4),
+        say(what='fullnet_forward', path='torch', net=args.net, precision=prec, windows=N, size=S, ms=round(ms, 3), ms_per_window=round(ms / N, 4),
             hip_vs_torch_rel_diff=err)
         del m, xt
         torch.cuda.empty_cache()
@@ -277,14 +315,18 @@ def main():
     ap.add_argument('--only-layers', action='store_true')
     ap.add_argument('--train', action='store_true', help='time one training step instead (fp32 mode)')
     ap.add_argument('--batch', type=int, default=8)
+    ap.add_argument('--net', choices=['FullNet', 'FCN_pooling'], default='FullNet')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('tools/bench_fullnet.py needs the GPU: a time measured elsewhere says nothing about it')
     say(what='device', name=torch.cuda.get_device_name(0))
+    if args.net != 'FullNet':
+        bench_box()
     if args.train:
         bench_train(args)
         return
-    bench_layers(args)
+    if args.net == 'FullNet':
+        bench_layers(args)
     if not args.only_layers:
         bench_network(args)
 
