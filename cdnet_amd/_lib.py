@@ -131,6 +131,8 @@ SIGNATURES = {
     'cdnet_wgrad_reduce_batch': (_i, [_vp, _i, _i, _vp]),
     'cdnet_bn_backward_workspace_floats': (_sz, [_i]),
     'cdnet_bn_backward': (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    'cdnet_bn_backward_last_plan': (_i, []),
+    'cdnet_bn_backward_last_sums_plan': (_i, []),
     'cdnet_dam_head_backward_workspace_floats': (_sz, [_i, _i, _i]),
     'cdnet_dam_head_backward': (_i, [_vp] * 7 + [_i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     'cdnet_dam_head_backward_fused_blocks': (_i, []),

@@ -621,6 +621,8 @@ static int fill_bn_args(const cdnet_bn_bwd_args *a, BnBwdArgs &A, const char *wh
         A.gin[k].oy = a->gin[k].oy; A.gin[k].ox = a->gin[k].ox; A.gin[k].pooled = a->gin[k].pooled;
         A.gin[k].coff = a->gin[k].coff; A.gin[k].cstride = a->gin[k].cstride ? a->gin[k].cstride : a->C;
         if (k < a->ngin) CDNET_REQUIRE(a->gin[k].g, "%s: null gradient input %d", who, k);
+        // (a floor-mode pool of a one-pixel-high or -wide tensor has no output: the window kernels' clamped load would read element 0 of it)
+        if (k < a->ngin) CDNET_REQUIRE(a->gin[k].Hg >= 1 && a->gin[k].Wg >= 1, "%s: empty gradient input %d (%d x %d)", who, k, a->gin[k].Hg, a->gin[k].Wg);
     }
     A.ngin = a->ngin; A.N = a->N; A.H = a->H; A.W = a->W; A.C = a->C;
     A.partial = nullptr; A.k1 = A.k2 = A.k3 = nullptr; A.draw = nullptr; A.dz_out = nullptr;
@@ -669,9 +671,24 @@ static BnPlan bn_plan(const BnBwdArgs &A, const void *draw, const void *dz_out) 
     return P;
 }
 
+// which instantiation the last launch of this thread took, per pass ([0] sums, [1] apply), and which pass came last
+// (cdnet_bn_backward_last_plan / _last_sums_plan; host only, bit layout in cdnet_hip.h)
+static thread_local int g_bn_last_plan[2] = {0, 0};
+static thread_local int g_bn_last_pass = 0;
+
+static int bn_plan_record(const BnPlan &P, const BnBwdArgs &A, bool apply, bool dz_source) {
+    const int path = P.path == BN_WINDOW ? CDNET_BN_PATH_WINDOW : P.path == BN_FLAT ? CDNET_BN_PATH_FLAT : CDNET_BN_PATH_GENERIC;
+    const int n = P.path == BN_WINDOW ? P.nflat : P.path == BN_FLAT ? A.ngin : 0;
+    const int res = P.path == BN_FLAT && A.res ? 1 : 0;
+    const int kp = P.path == BN_WINDOW ? P.kp : 0;
+    return path | (P.f32 ? 1 : 0) << 2 | n << 3 | res << 5 | kp << 6 | (apply ? 1 : 0) << 8 | (dz_source ? 1 : 0) << 9 | P.nb << 10;
+}
+
 // one pass of the plan: the only place that turns run-time source counts into kernel instantiations
 template <bool APPLY>
-static void launch(const BnPlan &P, const BnBwdArgs &A, hipStream_t st) {
+static void launch(const BnPlan &P, const BnBwdArgs &A, hipStream_t st, bool dz_source = false) {
+    g_bn_last_plan[APPLY ? 1 : 0] = bn_plan_record(P, A, APPLY, dz_source);
+    g_bn_last_pass = APPLY ? 1 : 0;
     auto window = [&](auto nf) {
         constexpr int NF = decltype(nf)::value;
         if (P.f32) bn_bwd_window32_kernel<NF, APPLY><<<P.nb, 256, 0, st>>>(A, P.kp);
@@ -757,7 +774,7 @@ extern "C" int cdnet_bn_backward(const cdnet_bn_bwd_args *a, const float *gamma,
         bn_set_coeffs(A, k);
     }
     A.dz_out = dz_out;
-    launch<true>(P, reuse ? bn_dz_as_source(A, dz_out) : A, st);
+    launch<true>(P, reuse ? bn_dz_as_source(A, dz_out) : A, st, reuse);
     return check_launch("cdnet_bn_backward");
 }
 
@@ -818,5 +835,8 @@ extern "C" int cdnet_bn_backward_apply(const cdnet_bn_bwd_args *a, const float *
     launch<true>(bn_plan_plain(A), A, (hipStream_t)stream);
     return check_launch("cdnet_bn_backward_apply");
 }
+
+extern "C" int cdnet_bn_backward_last_plan(void) { return g_bn_last_plan[g_bn_last_pass]; }
+extern "C" int cdnet_bn_backward_last_sums_plan(void) { return g_bn_last_plan[0]; }
 
 extern "C" size_t cdnet_bn_backward_workspace_floats(int C) { return (size_t)BN_MAX_BLOCKS * 2 * C + 3 * (size_t)C; }

@@ -689,6 +689,24 @@ int cdnet_bn_backward_finalize(const cdnet_bn_bwd_args *args, const float *gamma
 int cdnet_bn_backward(const cdnet_bn_bwd_args *args, const float *gamma, float *dgamma, float *dbeta, float *workspace,
                       size_t workspace_floats, uint16_t *draw, uint16_t *dz_out, void *stream);
 
+/* The launch plan of the calling thread's last BatchNorm-backward kernel launch (any of the four entries; host-side record,
+ * thread-local like cdnet_last_error; 0 before the first launch; a refused call leaves it alone).  For tests, which assert the kernel
+ * instantiation and the workgroup count of every case.  cdnet_bn_backward_last_sums_plan: the same record of the last SUMS pass (the
+ * fused entry launches sums, finalize, apply: its apply pass is what cdnet_bn_backward_last_plan then returns).  Bit layout:
+ *   bits 0-1  path (CDNET_BN_PATH_*)
+ *   bit  2    f32: the fp32 kernels (4 channels per thread on the window / flat paths)
+ *   bits 3-4  NF (window: same-size sources beside the pooled one, 0-2) or NG (flat: gradient sources, 1-3); 0 on the generic path
+ *   bit  5    RES (flat: the residual template form); 0 elsewhere
+ *   bits 6-7  kp (window: position of the pooled source among the sources); 0 elsewhere
+ *   bit  8    pass: 0 sums, 1 apply
+ *   bit  9    the apply pass ran on the dz the sums pass stored (one plain source, no mask) instead of the caller's sources
+ *   bits 10-21 nb: workgroups of the launch = partial rows of the sums pass (1 .. 2048) */
+#define CDNET_BN_PATH_WINDOW  1   /* bn_bwd_window_kernel / bn_bwd_window32_kernel */
+#define CDNET_BN_PATH_FLAT    2   /* bn_bwd_flat_kernel / bn_bwd_flat32_kernel */
+#define CDNET_BN_PATH_GENERIC 3   /* bn_bwd_generic_kernel */
+int cdnet_bn_backward_last_plan(void);
+int cdnet_bn_backward_last_sums_plan(void);
+
 /* DAM head backward (model_unet_rev1.py:258-263): gradients of the three logit maps (f32 NCHW) -> gradients of the
  * three 64-channel features (bf16 NHWC) and of the head weights (f32, CDNET_HEAD_WEIGHT_FLOATS layout). */
 size_t cdnet_dam_head_backward_workspace_floats(int N, int H, int W);
