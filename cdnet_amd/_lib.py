@@ -123,6 +123,9 @@ SIGNATURES = {
     'cdnet_bias_grad_f32': (_i, [_vp, _sz, _i, _vp, _sz, _vp, _vp]),
     'cdnet_final_conv1x1_backward_workspace_floats': (_sz, []),
     'cdnet_final_conv1x1_backward': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _vp, _vp]),
+    'cdnet_final_conv1x1_c16': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'cdnet_final_conv1x1_c16_backward_workspace_floats': (_sz, []),
+    'cdnet_final_conv1x1_c16_backward': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _vp, _vp]),
     'cdnet_conv_wgrad_slab_floats': (_sz, [_i] * 6),
     'cdnet_conv_backward_weight': (_i, [_vp, _i, _i, _i, _vp] + [_i] * 9 + [_vp, _vp, _i, _vp]),
     'cdnet_conv_backward_weight_last_form': (_i, []),

@@ -115,7 +115,8 @@ class _RU:
 
 class Unet(nn.Module):
     # head wiring: 'rev1' = the direction-aware-mask head of CDNet; the ablation models of models/dam/model_unet_MandD*.py reuse
-    # this class with VARIANT 'MandD' (mask + direction, no gates, no point branch) / 'MandDandP' (plus the point branch)
+    # this class with VARIANT 'MandD' (mask + direction, no gates, no point branch) / 'MandDandP' (plus the point branch); 'plain' is the
+    # backbone U-Net of models/model_unet.py: no head modules at all, `final_conv` on the decoder's 16-channel feature
     VARIANT = 'rev1'
     DIRECTION_OUT = 9
 
@@ -137,15 +138,16 @@ class Unet(nn.Module):
         self.replaced_conv1 = False
         self.child0 = nn.Conv2d(1, 64, kernel_size=(3, 3), stride=(1, 1), padding=(1, 1))       # never used (:220)
         self.child_conv1 = nn.Conv2d(1, 64, kernel_size=(7, 7), stride=(2, 2), padding=(3, 3), bias=False)
-        self.mask_feature = ResidualUnit(decoder_filters[-1], 64)
-        self.direction_feature = ResidualUnit(64, 64)
-        self.point_feature = ResidualUnit(64, 64)
-        self.point_conv = nn.Conv2d(64, 1, kernel_size=1)
-        self.directionAtt = revAttention(1)
-        self.direction_conv = nn.Conv2d(64, self.DIRECTION_OUT, kernel_size=1)
-        self.maskAtt = revAttention(self.DIRECTION_OUT)
-        self.mask_conv = nn.Conv2d(64, 3, kernel_size=1)
-        if self.VARIANT != 'rev1':
+        if self.VARIANT != 'plain':
+            self.mask_feature = ResidualUnit(decoder_filters[-1], 64)
+            self.direction_feature = ResidualUnit(64, 64)
+            self.point_feature = ResidualUnit(64, 64)
+            self.point_conv = nn.Conv2d(64, 1, kernel_size=1)
+            self.directionAtt = revAttention(1)
+            self.direction_conv = nn.Conv2d(64, self.DIRECTION_OUT, kernel_size=1)
+            self.maskAtt = revAttention(self.DIRECTION_OUT)
+            self.mask_conv = nn.Conv2d(64, 3, kernel_size=1)
+        if self.VARIANT not in ('rev1', 'plain'):
             self.residual = ResidualUnit(64, 64)            # model_unet_MandD.py:234
         if encoder_freeze:
             self.freeze_encoder()
@@ -175,6 +177,9 @@ class Unet(nn.Module):
         for k, b in enumerate(self.upsample_blocks):
             dec.append((ConvLayer('upsample_blocks.%d.up' % k, 'convT4', b.up.weight, None, b.bn1),
                         ConvLayer('upsample_blocks.%d.conv2' % k, 'conv3', b.conv2.weight, None, b.bn2)))
+        if self.VARIANT == 'plain':
+            self._rt = dict(enc=enc, dec=dec, ru=[])
+            return
         self._rt = dict(enc=enc, dec=dec, ru=[_RU('mask_feature', self.mask_feature),
                                                _RU('direction_feature', self.direction_feature),
                                                _RU('point_feature', self.point_feature)])
@@ -209,7 +214,8 @@ class Unet(nn.Module):
 
     def forward_features(self, x, training):
         """runs the encoder/decoder/residual units; returns the three head features as Src (eval mode, 16-bit path: the third one is a
-        runtime.PointLogit - the point feature's only reader is point_conv, its logits come with the unit's launch)"""
+        runtime.PointLogit - the point feature's only reader is point_conv, its logits come with the unit's launch); VARIANT 'plain':
+        the decoder's 16-channel feature alone"""
         if self._rt is None:
             self._build_runtime()
         if not x.is_cuda:
@@ -246,6 +252,8 @@ class Unet(nn.Module):
             u.off = pad_offsets((uh, uw), (sh, sw))                # F.pad (:126-131)
             tt = None if training else conv2.forward_eval_swapped([u, skip], H=sh, W=sw)      # (eval, 16-bit: an odd chunk count made even - runtime.py)
             t = tt if tt is not None else conv2.forward([u, skip], training, H=sh, W=sw)      # cat([x, skip]) -> conv2 -> bn2 -> relu (:133-141)
+        if self.VARIANT == 'plain':
+            return t
         f1 = self._rt['ru'][0].forward(t, training, store=True)
         f2 = self._rt['ru'][1].forward(f1, training, store=True)
         if self.VARIANT == 'rev1':

@@ -68,6 +68,18 @@ def head_feat(s):
     return f
 
 
+def head_feat16(s):
+    """the 16-channel feature of cdnet_final_conv1x1_c16 / _backward (the backbone U-Net's last decoder block): no residual operand"""
+    assert not s.pool and s.off == (0, 0) and s.C == 16 and s.res is None
+    f = HeadFeat()
+    f.raw, f.res = s.x.data_ptr(), None
+    f.scale = None if s.scale is None else s.scale.data_ptr()
+    f.shift = None if s.shift is None else s.shift.data_ptr()
+    f.relu = int(s.relu)
+    f.f16 = int(s.f16)
+    return f
+
+
 class ConvLayer:
     """One convolution (optionally followed by BatchNorm) of a network."""
 

@@ -6,7 +6,7 @@
   image_metrics(pred_labeled, gt_instances)                          test.py:316-371: the 22 numbers of one row of <img_dir>_result.txt
   main(argv=None)                                                    test.py:34-606 (command line; images from opt.test['img_dir'])
 
-Models: UNet, FullNet (inference on csrc/dilated.hip), and the model_unet_MandD / MandD4 / MandD16 ablation heads through output[0] of their (mask, direction) pair (:629-630).  A network
+Models: UNet, UNet_vgg16 (models/model_unet.py), FullNet (inference on csrc/dilated.hip), and the model_unet_MandD / MandD4 / MandD16 ablation heads through output[0] of their (mask, direction) pair (:629-630).  A network
 with three outputs (UNet2RevA1_vgg16, model_unet_MandDandP, HRNet18_rev1) is refused with a ValueError - cdnet_amd.test_dam evaluates those (the
 reference's test.py fails on them too).
 
@@ -26,7 +26,7 @@ from .options import Options
 from .test_dam import _dist_env, evaluate_labels, gather_results, ground_truth_instances, shard_names
 
 # networks whose forward has one mask output (or (mask, direction), read through output[0])
-MASK_MODELS = ('UNet', 'model_unet_MandD', 'model_unet_MandD4', 'model_unet_MandD16', 'FullNet')
+MASK_MODELS = ('UNet', 'model_unet_MandD', 'model_unet_MandD4', 'model_unet_MandD16', 'FullNet', 'UNet_vgg16')
 
 # the 22 columns of <img_dir basename>_result.txt (test.py:442-455)
 HEADER = ['pixel_acc', 'pixel_IoU', 'pixel_Recall', 'pixel_Precision', 'pixel_F1', 'recall', 'precision', 'F1', 'Dice', 'IoU', 'Hausdorff',

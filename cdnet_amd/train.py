@@ -1,5 +1,5 @@
 """Training entry point with the reference's shape (train.py:59-530, the part that is the hot path): options -> seeds ->
-`chooseModel` -> optimiser and scheduler (`utils.get_optimizer`) -> epochs of `train_util_dam.train` (the plain UNet: `train_util.train`),
+`chooseModel` -> optimiser and scheduler (`utils.get_optimizer`) -> epochs of `train_util_dam.train` (the mask-only networks UNet, UNet_vgg16 and FullNet: `train_util.train`),
 each followed by validation, the scheduler step and the checkpoint.
 
     python -m cdnet_amd.train --synthetic 64 --epochs 2              # synthetic tiles (no dataset needed)
@@ -108,8 +108,11 @@ def main(argv=None):
     logger = logging.getLogger('cdnet_amd.train')
     torch.manual_seed(opt.train['seed'])                   # train.py:75-81 (same seed on every rank = same initial weights)
     np.random.seed(opt.train['seed'])
+    if opt.model['modelName'] == 'UNet_vgg16' and opt.model['direction'] != 0:
+        raise ValueError("--model-name UNet_vgg16 has one mask output and no direction branch: pass --direction 0 (got {})".format(
+            opt.model['direction']))
     model = utils.chooseModel(opt).to(dev)
-    plain_unet = opt.model['modelName'] in ('UNet', 'FullNet')        # a mask-only network: train_util's loop and scores
+    plain_unet = opt.model['modelName'] in ('UNet', 'FullNet', 'UNet_vgg16')        # a mask-only network: train_util's loop and scores
     trainer, scheduler = utils.get_optimizer(opt, model, world_size=world)       # train.py:191 (the plain UNet's trainer too)
     best_iou, best_loss = 0.0, float('inf')
     if opt.train['checkpoint']:                            # train.py:293-306: resume (weights, Adam moments, epoch, best values)

@@ -945,6 +945,23 @@ class UNetTrainer(Trainer):
         return self.unet_losses
 
 
+class BackboneUNetTrainer(UNetTrainer):
+    """Train iteration of the backbone U-Net (models/model_unet.py through train_util.train): the plain UNet's loss, optimiser, all-reduce
+    and checkpoint entry; the classifier reads the decoder's 16-channel feature (cdnet_final_conv1x1_c16_backward), the rest is the rev1
+    tape."""
+
+    def _classifier_backward(self, key, f, conv, dl):
+        N, H, W, _ = f.x.shape
+        K = conv.out_channels
+        df = self.buf(key, (N, H, W, 16), runtime.act_dtype())
+        ws = self._ws('classifier16', _lib.load().cdnet_final_conv1x1_c16_backward_workspace_floats())
+        hf = runtime.head_feat16(f)
+        w = conv.weight.detach().reshape(K, 16)
+        _lib.call('cdnet_final_conv1x1_c16_backward', C.byref(hf), _lib.ptr(w), _lib.ptr(dl), K, N, H, W, _lib.ptr(df), _lib.ptr(ws),
+                  ws.numel(), _lib.ptr(conv.weight.grad), _lib.ptr(conv.bias.grad), _lib.stream_ptr())
+        return _G(df, H, W)
+
+
 class FullNetTrainer(UNetTrainer):
     """Train iteration of FullNet (models/FullNet.py through train_util.train): the plain UNet's loss, optimiser, all-reduce and checkpoint
     entry around the network's own training forward and backward (models/FullNet.py: _train_forward / train_backward on csrc/dilated.hip and

@@ -24,6 +24,9 @@ def chooseModel(opt):
         from .models.dam.model_unet_rev1 import Unet
         # the reference hard-codes pretrained=True (ImageNet download); weights are supplied via load_state_dict here
         return Unet(backbone_name='vgg16_bn', pretrained=False, encoder_freeze=False, classes=opt.model['out_c'])
+    if name == 'UNet_vgg16':                         # utils.py:822-824 (the ResNet backbones of :825-830 are not built)
+        from .models.model_unet import Unet
+        return Unet(backbone_name='vgg16_bn', pretrained=False, encoder_freeze=False, classes=opt.model['out_c'])
     if name in ('model_unet_MandD', 'model_unet_MandD4', 'model_unet_MandD16', 'model_unet_MandDandP'):      # utils.py:857-874
         import importlib
         mod = importlib.import_module('.models.dam.' + name, __package__)
@@ -37,7 +40,7 @@ def chooseModel(opt):
         return FullNet(m['in_c'], m['out_c'], n_layers=m['n_layers'], growth_rate=m['growth_rate'], drop_rate=m['drop_rate'],
                        dilations=m.get('dilations', [1, 2, 4, 8, 16, 4, 1]), is_hybrid=m['is_hybrid'], compress_ratio=m['compress_ratio'],
                        layer_type=m['layer_type'])
-    raise NotImplementedError('model {} is outside the CDNet hot path (SURVEY.md section 8: UNet, UNet2RevA1_vgg16, model_unet_MandD*, HRNet18_rev1, FullNet)'.format(name))
+    raise NotImplementedError('model {} is outside the CDNet hot path (SURVEY.md section 8: UNet, UNet_vgg16, UNet2RevA1_vgg16, model_unet_MandD*, HRNet18_rev1, FullNet)'.format(name))
 
 
 def window_grid(h0, w0, size, overlap):
@@ -162,12 +165,16 @@ class AverageMeter(object):
 
 def trainer_class(model):
     """the Trainer that serves `model`: the plain UNet's (one mask output), the ablation heads' (plain classifiers instead of the gated
-    head, model_unet_MandD / model_unet_MandDandP), FullNet's (the UNet's loss around its own tape), the DAM networks'"""
+    head, model_unet_MandD / model_unet_MandDandP), FullNet's (the UNet's loss around its own tape), the backbone U-Net's (the UNet's loss
+    around the rev1 tape, models/model_unet.py), the DAM networks'"""
     from .models.unet import UNet
     from .models.FullNet import FullNet
-    from .trainer import Trainer, AblationTrainer, FullNetTrainer, UNetTrainer
+    from .models.model_unet import Unet as BackboneUnet
+    from .trainer import Trainer, AblationTrainer, BackboneUNetTrainer, FullNetTrainer, UNetTrainer
     if isinstance(model, UNet):
         return UNetTrainer
+    if isinstance(model, BackboneUnet):
+        return BackboneUNetTrainer
     if isinstance(model, FullNet):
         return FullNetTrainer
     return AblationTrainer if getattr(model, 'VARIANT', 'rev1') != 'rev1' else Trainer

@@ -581,6 +581,18 @@ int cdnet_bias_grad_f32(const float *grad_out, size_t npix, int C, float *worksp
 size_t cdnet_final_conv1x1_backward_workspace_floats(void);
 int cdnet_final_conv1x1_backward(const cdnet_head_feat *f, const float *w, const float *dlogits, int K, int N, int H, int W,
                                  uint16_t *df, float *workspace, size_t workspace_floats, float *dw, float *db, void *stream);
+/* The backbone U-Net's classifier (models/model_unet.py:166,194 final_conv 16->K, 1 <= K <= 20) on the 16-channel feature of the last
+ * decoder block: a cdnet_head_feat whose raw is NHWC [N][H][W][16] (f16 = 0 / 1 / 2: bf16 / fp16 / fp32), 16-byte aligned, with the
+ * optional per-channel scale / shift (both or neither) and ReLU; res must be NULL (CDNET_E_ARG otherwise).  fp32 arithmetic behind the
+ * storage format.  Forward: f32 NCHW logits out[N][K][H][W].  Backward: dlogits f32 [N][K][H][W] -> df [N][H][W][16], the gradient of
+ * the activated feature (bf16 for f16 = 0 / 1, f32 for f16 = 2; 16-byte aligned), dw f32 [K][16], db f32 [K]; the sums go through
+ * per-workgroup partial rows in `workspace` (cdnet_final_conv1x1_c16_backward_workspace_floats() floats) and a fixed-order reduce:
+ * no atomics, two runs give the same bits. */
+int cdnet_final_conv1x1_c16(const cdnet_head_feat *f, const float *w, const float *b, int K, int N, int H, int W,
+                            float *out, void *stream);
+size_t cdnet_final_conv1x1_c16_backward_workspace_floats(void);
+int cdnet_final_conv1x1_c16_backward(const cdnet_head_feat *f, const float *w, const float *dlogits, int K, int N, int H, int W,
+                                     void *df, float *workspace, size_t workspace_floats, float *dw, float *db, void *stream);
 
 /* cdnet_src_materialize: a convolution source with its pending transform - BatchNorm scale / shift, residual add, ReLU,
  * nn.MaxPool2d(2, 2[, ceil_mode]) (model_unet_rev1.py:268-287 backbone 'M' layers, unet.py:19), F.pad offset - written out
