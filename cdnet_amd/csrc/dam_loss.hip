@@ -426,7 +426,8 @@ extern "C" int cdnet_dam_loss_terms(const float *mask, const float *point, const
                   "cdnet_dam_loss: direction_classes %d must be 5, 9 or 17 (options.py:45)", direction_classes);
     const int P = H * W;
     if (workspace_floats < cdnet_dam_loss_classes_workspace_floats(B, P, direction_classes)) { set_error("cdnet_dam_loss: workspace too small"); return CDNET_E_WORKSPACE; }
-    if (dmask) CDNET_REQUIRE(dpoint && ddir, "cdnet_dam_loss: all three gradient outputs or none");
+    CDNET_REQUIRE((dmask != nullptr) == (dpoint != nullptr) && (dmask != nullptr) == (ddir != nullptr),
+                  "cdnet_dam_loss: all three gradient outputs or none");      // (dpoint or ddir alone used to be taken as none, silently)
     LossIn L;
     L.mask = mask; L.point = point; L.dirn = dirn; L.label = label; L.dirlab = dirlab; L.point_t = point_target_f16;
     L.weight = weight_u8; L.single = nullptr; L.B = B; L.P = P; L.quirk0 = quirk_sample0; L.terms = terms;

@@ -750,7 +750,7 @@ int cdnet_dam_head_backward_fused(const cdnet_head_feat *f1, const cdnet_head_fe
  * quirk_sample0 = 1 reproduces train_util_dam.py:139 (direction one-hot masked by sample 0's foreground).
  * losses[11] = {total, direction CE, direction weighted dice, MSE, CE, dice, then the pixel-level metrics of
  * train_util_dam.py:279-293 (argmax direction class == 1 vs direction label == 1, utils.py:67-110), averaged over the batch:
- * accuracy, IoU, recall, precision, F1}.  dmask/dpoint/ddir may all be NULL.
+ * accuracy, IoU, recall, precision, F1}.  dmask/dpoint/ddir may all be NULL (values only); some but not all of them: CDNET_E_ARG.
  * Label content is validated on the device: a mask class > 2 or a direction class > 8 makes every entry of `losses` NaN
  * (indices are clamped, nothing is read or written out of bounds) - the reference's nn.NLLLoss raises on such targets.
  */
