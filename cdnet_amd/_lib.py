@@ -11,6 +11,68 @@ LIB_PATH = os.environ.get('CDNET_LIB_PATH') or os.path.join(_HERE, 'libcdnet_hip
 
 _vp, _i, _sz, _f, _u = C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_uint
 
+
+# ctypes mirrors of the argument structs of include/cdnet_hip.h: every one is defined here, once (MIRRORS below names them for tests/test_abi.py)
+class ConvSrc(C.Structure):                  # cdnet_conv_src
+    _fields_ = [('x', C.c_void_p), ('res', C.c_void_p), ('scale', C.c_void_p), ('shift', C.c_void_p),
+                ('C', C.c_int), ('Hs', C.c_int), ('Ws', C.c_int), ('pool', C.c_int), ('relu', C.c_int),
+                ('off_y', C.c_int), ('off_x', C.c_int), ('f16', C.c_int), ('row_stride', C.c_int)]
+
+
+class ConvArgs(C.Structure):                 # cdnet_conv_args
+    _fields_ = [('src', ConvSrc * 2), ('nsrc', C.c_int), ('w', C.c_void_p), ('bias', C.c_void_p),
+                ('oscale', C.c_void_p), ('oshift', C.c_void_p), ('orelu', C.c_int), ('out', C.c_void_p),
+                ('Cout', C.c_int), ('out_cstride', C.c_int), ('out_coff', C.c_int), ('stats', C.c_void_p),
+                ('N', C.c_int), ('H', C.c_int), ('W', C.c_int), ('taps', C.c_int), ('npar', C.c_int),
+                ('ostride', C.c_int), ('nchunk', C.c_int), ('tile', C.c_int), ('CK', C.c_int), ('BN', C.c_int),
+                ('out_f16', C.c_int), ('debug', C.c_int), ('ws', C.c_int), ('f32', C.c_int),
+                ('eres', C.c_void_p), ('eres_scale', C.c_void_p), ('eres_shift', C.c_void_p), ('eres_f16', C.c_int), ('eres_relu', C.c_int),
+                ('taps1', C.c_int), ('pad_', C.c_int), ('pool_out', C.c_void_p),
+                ('dot_w', C.c_void_p), ('dot_b', C.c_void_p), ('dot_out', C.c_void_p)]
+
+
+class PackJob(C.Structure):                  # cdnet_pack_job
+    _fields_ = [('w', C.c_void_p), ('packed', C.c_void_p), ('Cout', C.c_int), ('Cin', C.c_int), ('KH', C.c_int), ('KW', C.c_int),
+                ('CK', C.c_int), ('BN', C.c_int), ('mode', C.c_int), ('pad_', C.c_int)]
+
+
+class HeadFeat(C.Structure):                 # cdnet_head_feat
+    _fields_ = [('raw', C.c_void_p), ('res', C.c_void_p), ('scale', C.c_void_p), ('shift', C.c_void_p),
+                ('relu', C.c_int), ('f16', C.c_int)]
+
+
+class FuseTerm(C.Structure):                 # cdnet_fuse_term
+    _fields_ = [('x', C.c_void_p), ('Hs', C.c_int), ('Ws', C.c_int), ('scale', C.c_void_p), ('shift', C.c_void_p),
+                ('f16', C.c_int), ('pad_', C.c_int)]
+
+
+class GradTerm(C.Structure):                 # cdnet_grad_term
+    _fields_ = [('g', C.c_void_p), ('cstride', C.c_int), ('coff', C.c_int)]
+
+
+class GradIn(C.Structure):                   # cdnet_grad_in
+    _fields_ = [('g', C.c_void_p), ('Hg', C.c_int), ('Wg', C.c_int), ('oy', C.c_int), ('ox', C.c_int),
+                ('pooled', C.c_int), ('coff', C.c_int), ('cstride', C.c_int), ('pad_', C.c_int)]
+
+
+class BnBwdArgs(C.Structure):                # cdnet_bn_bwd_args
+    _fields_ = [('raw', C.c_void_p), ('res', C.c_void_p), ('scale', C.c_void_p), ('shift', C.c_void_p),
+                ('mean', C.c_void_p), ('invstd', C.c_void_p), ('gin', GradIn * 3), ('ngin', C.c_int),
+                ('f16', C.c_int), ('relu', C.c_int), ('N', C.c_int), ('H', C.c_int), ('W', C.c_int), ('C', C.c_int)]
+
+
+class AugSample(C.Structure):                # cdnet_aug_sample
+    _fields_ = [('minv', C.c_double * 6), ('img', C.c_void_p), ('weight', C.c_void_p), ('label', C.c_void_p)] + \
+        [(n, C.c_int32) for n in ('H', 'W', 'img_stride', 'weight_stride', 'label_stride', 'label_i32')] + \
+        [('color', C.c_float * 4)] + [(n, C.c_int32) for n in ('hflip', 'vflip', 'filter', 'y0', 'x0')] + \
+        [('alpha', C.c_float), ('sigma', C.c_float), ('seed', C.c_uint32)]
+
+
+class AugGeo(C.Structure):                   # cdnet_aug_geo
+    _fields_ = [('paff', C.c_double * 6), ('rinv', C.c_double * 6)] + [(n, C.c_int32) for n in ('Hr', 'Wr', 'fy0', 'fx0')] + \
+        [('flags', C.c_uint32), ('reserved', C.c_int32)]
+
+
 class WgradReduceDesc(C.Structure):          # cdnet_wgrad_reduce_desc (include/cdnet_hip.h)
     _fields_ = [('slab', C.c_void_p), ('dw', C.c_void_p)] + [(n, C.c_int) for n in (
         'ksplit', 'npar', 'ci_blocks', 'co_blocks', 'taps', 'CI', 'CO', 'Csrc_real', 'Cin_real', 'src_coff', 'Cout', 'mode', 'block0', 'blocks')]
@@ -38,6 +100,15 @@ class SliceBnBwdArgs(C.Structure):           # cdnet_slice_bn_bwd_args
         ('ws_floats', C.c_size_t), ('P', C.c_longlong)] + [(n, C.c_int) for n in ('C', 'z_cstride', 'dy_cstride', 'dy_coff', 'g_cstride')] + [
         (n, C.c_float) for n in ('slope', 'p_drop')] + [('layer', C.c_int), ('key', C.c_ulonglong)]
 
+
+# struct name of include/cdnet_hip.h -> its mirror; must list every name cdnet_abi_sizeof knows (tests/test_abi.py checks)
+MIRRORS = {
+    'cdnet_conv_src': ConvSrc, 'cdnet_conv_args': ConvArgs, 'cdnet_pack_job': PackJob, 'cdnet_head_feat': HeadFeat,
+    'cdnet_wgrad_reduce_desc': WgradReduceDesc, 'cdnet_grad_in': GradIn, 'cdnet_bn_bwd_args': BnBwdArgs, 'cdnet_fuse_term': FuseTerm,
+    'cdnet_grad_term': GradTerm, 'cdnet_aug_sample': AugSample, 'cdnet_aug_geo': AugGeo, 'cdnet_dilated_conv_args': DilatedConvArgs,
+    'cdnet_dilated_bwd_data_args': DilatedBwdDataArgs, 'cdnet_dilated_wgrad_args': DilatedWgradArgs,
+    'cdnet_slice_bn_fwd_args': SliceBnFwdArgs, 'cdnet_slice_bn_bwd_args': SliceBnBwdArgs,
+}
 
 # name -> (restype, argtypes); must list every symbol include/cdnet_hip.h declares (tests/test_abi.py checks)
 SIGNATURES = {

@@ -21,20 +21,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import AugGeo, AugSample
 
 HALO = 6                                   # the field window: crop + 6 px on every side (csrc/augment.hip)
-
-
-class AugSample(C.Structure):              # cdnet_aug_sample (include/cdnet_hip.h)
-    _fields_ = [('minv', C.c_double * 6), ('img', C.c_void_p), ('weight', C.c_void_p), ('label', C.c_void_p)] + \
-        [(n, C.c_int32) for n in ('H', 'W', 'img_stride', 'weight_stride', 'label_stride', 'label_i32')] + \
-        [('color', C.c_float * 4)] + [(n, C.c_int32) for n in ('hflip', 'vflip', 'filter', 'y0', 'x0')] + \
-        [('alpha', C.c_float), ('sigma', C.c_float), ('seed', C.c_uint32)]
-
-
-class AugGeo(C.Structure):                 # cdnet_aug_geo (include/cdnet_hip.h)
-    _fields_ = [('paff', C.c_double * 6), ('rinv', C.c_double * 6)] + [(n, C.c_int32) for n in ('Hr', 'Wr', 'fy0', 'fx0')] + \
-        [('flags', C.c_uint32), ('reserved', C.c_int32)]
 
 
 GEO_RESIZE, GEO_AFFINE, GEO_ROTATION = 1, 2, 4

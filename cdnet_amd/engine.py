@@ -1,4 +1,4 @@
-"""Host-side plumbing for the convolution stack: ctypes mirrors of the ABI structs, weight packing, per-layer
+"""Host-side plumbing for the convolution stack: weight packing, per-layer
 kernel configuration and thin call wrappers.  No compute happens here - every function ends in a C-ABI call
 into libcdnet_hip.so (torch tensors only provide device memory and the current stream).
 """
@@ -7,24 +7,7 @@ import os
 import torch
 
 from . import _lib
-
-
-class ConvSrc(C.Structure):
-    _fields_ = [('x', C.c_void_p), ('res', C.c_void_p), ('scale', C.c_void_p), ('shift', C.c_void_p),
-                ('C', C.c_int), ('Hs', C.c_int), ('Ws', C.c_int), ('pool', C.c_int), ('relu', C.c_int),
-                ('off_y', C.c_int), ('off_x', C.c_int), ('f16', C.c_int), ('row_stride', C.c_int)]
-
-
-class ConvArgs(C.Structure):
-    _fields_ = [('src', ConvSrc * 2), ('nsrc', C.c_int), ('w', C.c_void_p), ('bias', C.c_void_p),
-                ('oscale', C.c_void_p), ('oshift', C.c_void_p), ('orelu', C.c_int), ('out', C.c_void_p),
-                ('Cout', C.c_int), ('out_cstride', C.c_int), ('out_coff', C.c_int), ('stats', C.c_void_p),
-                ('N', C.c_int), ('H', C.c_int), ('W', C.c_int), ('taps', C.c_int), ('npar', C.c_int),
-                ('ostride', C.c_int), ('nchunk', C.c_int), ('tile', C.c_int), ('CK', C.c_int), ('BN', C.c_int),
-                ('out_f16', C.c_int), ('debug', C.c_int), ('ws', C.c_int), ('f32', C.c_int),
-                ('eres', C.c_void_p), ('eres_scale', C.c_void_p), ('eres_shift', C.c_void_p), ('eres_f16', C.c_int), ('eres_relu', C.c_int),
-                ('taps1', C.c_int), ('pad_', C.c_int), ('pool_out', C.c_void_p),
-                ('dot_w', C.c_void_p), ('dot_b', C.c_void_p), ('dot_out', C.c_void_p)]
+from ._lib import ConvArgs, ConvSrc, PackJob         # (the mirrors live in _lib; the names resolve here as before)
 
 
 def _dp(t):
@@ -34,13 +17,17 @@ def _dp(t):
 class Src:
     """One convolution source: a 16-bit NHWC tensor [N,Hs,Ws,C] (bf16, or fp16 for raw pre-BatchNorm outputs) plus the
     producer's lazily-applied transform.  `view=(ptr_offset_elems, Hs, Ws, C, row_stride)` describes a strided window of
-    `x` instead of the dense tensor (space-to-depth view of an upsampled gradient)."""
+    `x` instead of the dense tensor (space-to-depth view of an upsampled gradient).  `grad_to=(stored tensor, pool mode)`: backward
+    routes the gradient of this stored copy to that tensor instead (runtime.pooled, a residual unit's materialised output);
+    `is_input`: the network's input, which takes no gradient."""
+    __slots__ = ('x', 'scale', 'shift', 'relu', 'pool', 'res', 'off', 'N', 'Hs', 'Ws', 'Cc', 'ptr_off', 'row_stride', 'grad_to', 'is_input')
 
-    def __init__(self, x, scale=None, shift=None, relu=False, pool=False, res=None, off=(0, 0), view=None):
+    def __init__(self, x, scale=None, shift=None, relu=False, pool=False, res=None, off=(0, 0), view=None, grad_to=None, is_input=False):
         assert x.dtype in (torch.bfloat16, torch.float16, torch.float32) and x.is_contiguous()
         # a source keeps its residual branch in the storage type of x
         assert res is None or res.dtype == x.dtype
         self.x, self.scale, self.shift, self.relu, self.pool, self.res, self.off = x, scale, shift, relu, pool, res, off
+        self.grad_to, self.is_input = grad_to, is_input
         if view is None:
             assert x.dim() == 4
             self.N, self.Hs, self.Ws, self.Cc = x.shape
@@ -166,11 +153,6 @@ def _pack_dims(w, cfg, mode):
     taps = {2: 4, 3: 1, 4: 9, 5: 1, 6: 9, 7: 9}.get(mode, KH * KW)
     npar = 4 if mode in (2, 3) else 1
     return Cout, Cin, KH, KW, CK, BN, taps, npar
-
-
-class PackJob(C.Structure):
-    _fields_ = [('w', C.c_void_p), ('packed', C.c_void_p), ('Cout', C.c_int), ('Cin', C.c_int), ('KH', C.c_int), ('KW', C.c_int),
-                ('CK', C.c_int), ('BN', C.c_int), ('mode', C.c_int), ('pad_', C.c_int)]
 
 
 def pack_job(w, cfg, mode, out, split=False):

@@ -93,17 +93,18 @@ class _RU:
             h = self.c1.forward([x], training, relu=True)
             y = self.c2.forward([h], training, relu=False, out_dtype=runtime.raw_dtype())       # raw fp16; BatchNorm pending in training
             f = self.cr.forward([x], training, eres=Src(y.x, y.scale, y.shift, relu=relu2))
-            # backward: the consumers' gradients of f go through bn2 first (ReLU mask read from f), its dz is conv_1x1's gradient
-            self.c2.node_relu, self.c2.node_res = (2 if relu2 else 0), f.x
-            self.cr.fused_res_of = self.c2
+            if training:
+                # backward: the consumers' gradients of f go through bn2 first (ReLU mask read from f), its dz is conv_1x1's gradient
+                self.c2.rec.relu, self.c2.rec.res = (2 if relu2 else 0), f.x
+                self.cr.rec.fused_res_of = self.c2.rec
             return f
-        self.cr.fused_res_of = None
         # the pre-activation pair (bn2 output, residual) is kept in fp16: it is only ever read through the consumer's
         # add+ReLU transform, never as an MFMA operand
         r = self.cr.forward([x], training, out_dtype=runtime.raw_dtype())               # residual = conv_1x1(x)   (:162)
         h = self.c1.forward([x], training, relu=True)                             # relu1(bn1(conv1(x)))     (:163-165)
         y = self.c2.forward([h], training, relu=False, out_dtype=runtime.raw_dtype())   # bn2(conv2(.))            (:166-167)
-        self.c2.node_relu, self.c2.node_res = relu2, r.x         # how consumers (and backward) see the unit's output
+        if training:
+            self.c2.rec.relu, self.c2.rec.res = relu2, r.x       # how consumers (and backward) see the unit's output
         out = Src(y.x, y.scale, y.shift, relu=relu2, res=r.x)    # relu2(out + residual)             (:168-169)
         if store and runtime.RU_MATERIALIZE:
             # three consumers (the next unit's two convolutions and the head) would each redo BatchNorm + add + ReLU over
@@ -227,14 +228,13 @@ class Unet(nn.Module):
         """x16: bf16 NHWC [N,H,W,16] (3 real channels) - the form cdnet_input_pack / cdnet_window_pack produce"""
         if self._rt is None:
             self._build_runtime()
-        t = Src(x16)
-        t.is_input = True
+        t = Src(x16, is_input=True)
         self._rt['enc'][0][1].needs_input_grad = False
         feats = {}
         enc, tp = self._rt['enc'], None
         for idx, (kind, layer, out_name) in enumerate(enc):         # forward_backbone (:268-287)
             if kind == 'conv':
-                if not training and idx + 1 < len(enc) and enc[idx + 1][0] == 'pool' and not getattr(runtime, 'DEBUG_NORELU', False):
+                if not training and idx + 1 < len(enc) and enc[idx + 1][0] == 'pool' and not runtime.DEBUG_NORELU:
                     t, tp = layer.forward_eval_pool([t])           # eval: the max-pool that follows leaves with the convolution's stores
                 else:
                     t = layer.forward([t], training)

@@ -384,8 +384,7 @@ class HighResolutionNet(nn.Module):
         rt = self._rt
         x = x16
         assert x.shape[1] % 8 == 0 and x.shape[2] % 8 == 0, 'HRNet18_rev1 needs tile sizes divisible by 8 (three stride-2 stages)'
-        t = Src(x16)
-        t.is_input = True
+        t = Src(x16, is_input=True)
         for L in rt['stem']:                              # conv1-bn1-relu, conv2-bn2-relu (:495-500)
             t = L.forward([t], training, relu=True)
         for k, quad in enumerate(rt['layer1']):

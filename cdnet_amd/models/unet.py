@@ -95,8 +95,7 @@ class UNet(nn.Module):
         if self._rt is None:
             self._build_runtime()
         training = self.training
-        t = Src(x16)
-        t.is_input = True
+        t = Src(x16, is_input=True)
         self._rt['down'][0][0].needs_input_grad = False
         skips = []
         for c1, c2 in self._rt['down']:                               # x_i, x = down_i(x)   (:91-94)

@@ -15,6 +15,7 @@ import weakref
 import torch
 
 from . import _lib, engine
+from ._lib import FuseTerm, GradTerm, HeadFeat          # noqa: F401 (the mirrors live in _lib; the names resolve here as before)
 from .engine import Src
 
 BN_EPS = 1e-5
@@ -47,18 +48,13 @@ def raw_dtype():
 
 
 DEBUG_NORELU = False   # debug aid (tools/debug_train.py): linearised network
-TAPE = None              # set by cdnet_amd.trainer around a training forward: layers append themselves in execution order
+TAPE = None              # set by cdnet_amd.trainer around a training forward: one record per layer / fuse node, in execution order
 WEIGHTS_EPOCH = [0]      # bumped by the fused Adam step (it updates parameters behind torch's version counters)
 LAYERS = weakref.WeakSet()   # every live ConvLayer (the trainer batches their weight re-packs)
 
 
-class HeadFeat(C.Structure):
-    _fields_ = [('raw', C.c_void_p), ('res', C.c_void_p), ('scale', C.c_void_p), ('shift', C.c_void_p),
-                ('relu', C.c_int), ('f16', C.c_int)]
-
-
-def head_feat(s):
-    assert not s.pool and s.off == (0, 0) and s.C == 64
+def head_feat(s, channels=64):
+    assert not s.pool and s.off == (0, 0) and s.C == channels
     f = HeadFeat()
     f.raw, f.res = s.x.data_ptr(), (None if s.res is None else s.res.data_ptr())
     f.scale = None if s.scale is None else s.scale.data_ptr()
@@ -70,18 +66,42 @@ def head_feat(s):
 
 def head_feat16(s):
     """the 16-channel feature of cdnet_final_conv1x1_c16 / _backward (the backbone U-Net's last decoder block): no residual operand"""
-    assert not s.pool and s.off == (0, 0) and s.C == 16 and s.res is None
-    f = HeadFeat()
-    f.raw, f.res = s.x.data_ptr(), None
-    f.scale = None if s.scale is None else s.scale.data_ptr()
-    f.shift = None if s.shift is None else s.shift.data_ptr()
-    f.relu = int(s.relu)
-    f.f16 = int(s.f16)
-    return f
+    assert s.res is None
+    return head_feat(s, 16)
+
+
+class ConvRecord:
+    """One training forward of a ConvLayer, as the tape walk (cdnet_amd.trainer) reads it:
+      layer, srcs, out, H, W  the layer, its sources, the stored (raw) output and the logical size - written by the forward;
+      relu, res               how consumers see the output: ReLU False / True / 2 (mask read from `res`, the stored sum) and the residual
+                              branch - the forward, then the residual unit that ran the layer, or the walk for an HRNet residual sum;
+      res_grad_to             the tensor that takes the residual branch's gradient when that is not `res` itself (the walk; cleared when used);
+      fused_res_of            on conv_1x1 of a residual unit with the fused epilogue: conv2's record (the residual unit);
+      deferred                the record whose backward runs right behind this one's (the walk; cleared when used).
+    The layer's scale / shift / save_mean / save_invstd / stats are NOT here: those device buffers stay on the layer and its next training
+    forward rewrites them, so two live forwards of one model are not supported."""
+    __slots__ = ('layer', 'srcs', 'out', 'H', 'W', 'relu', 'res', 'res_grad_to', 'fused_res_of', 'deferred')
+
+    def __init__(self, layer, srcs, out, H, W, relu):          # (one per layer and step: kept to two statements)
+        self.layer, self.srcs, self.out, self.H, self.W, self.relu = layer, srcs, out, H, W, relu
+        self.res = self.res_grad_to = self.fused_res_of = self.deferred = None
+
+
+class FuseRecord:
+    """One training forward of a FuseNode: its terms, the tensor `out` that holds the sum in channels [coff, coff + C), relu, H, W."""
+    __slots__ = ('node', 'terms', 'out', 'relu', 'H', 'W', 'C', 'coff')
+
+    def __init__(self, node, terms, out, relu, H, W, C, coff):
+        self.node, self.terms, self.out, self.relu, self.H, self.W, self.C, self.coff = node, terms, out, relu, H, W, C, coff
 
 
 class ConvLayer:
     """One convolution (optionally followed by BatchNorm) of a network."""
+    __slots__ = ('name', 'kind', 'weight', 'bias', 'bn', 'cfg_override', 'Cout', 'Cin', 'taps', 'transposed', 'pack_mode', 'cfg', 'cfg_f32',
+                 'wp', 'wp_version', 'wp_padded', 'wpb', 'wpb_version', 'cfg_bwd', 'fold', 'fold_version', 'fold_eval',
+                 'wpe', 'wpe_version', 'wps', 'wps_version', 'ru_wr', 'ru_wr_version', 'ru_pack', 'ru_pack_version', 'ru_shift',
+                 '_swapped_eligible', '_ru_eligible', 'scale', 'shift', 'save_mean', 'save_invstd', 'stats',
+                 'rec', 'needs_input_grad', 'bias_grad_from', '__weakref__')
 
     def __init__(self, name, kind, weight, bias=None, bn=None, cfg_override=None):
         assert kind in ('conv3', 'conv1', 'convT4', 'convT2', 'conv3s2')
@@ -102,17 +122,22 @@ class ConvLayer:
         self.wp_version = None
         self.fold = None                       # eval-mode (scale, shift)
         self.fold_version = None
+        self.fold_eval = True                  # False: eval-mode BatchNorm stays an epilogue affine (seg_hrnet_rev1.py)
+        # eval-mode packs, made on first use: scale-folded (eval_pack), channel-swapped (forward_eval_swapped), a residual unit's two-launch form
+        self.wpe = self.wpe_version = self.wps = self.wps_version = None
+        self.ru_wr = self.ru_wr_version = self.ru_pack = self.ru_pack_version = self.ru_shift = None
+        self._swapped_eligible, self._ru_eligible = {}, {}
         dev = weight.device
+        self.scale = self.shift = self.save_mean = self.save_invstd = None
         if bn is not None:
             self.scale = torch.empty((self.Cout,), dtype=torch.float32, device=dev)
             self.shift = torch.empty((self.Cout,), dtype=torch.float32, device=dev)
             self.save_mean = torch.empty((self.Cout,), dtype=torch.float32, device=dev)
             self.save_invstd = torch.empty((self.Cout,), dtype=torch.float32, device=dev)
         self.stats = None
-        self.saved = None                      # (srcs, raw, H, W) of the last training forward
-        self.node_relu, self.node_res = True, None   # how consumers see this layer's output (set in forward / by the RU)
+        self.rec = None                        # the ConvRecord of the last training forward (for whoever ran it, never for the tape walk)
         self.needs_input_grad = True
-        self.bias_grad_from = None
+        self.bias_grad_from = None             # conv_1x1 of a residual unit: the layer whose dbeta is this bias's gradient
         self.wpb, self.wpb_version, self.cfg_bwd = None, None, None
         self.wp_padded = False                 # forward pack zero-extends Cin (RGB stem): not batchable
         LAYERS.add(self)
@@ -178,7 +203,7 @@ class ConvLayer:
         initial value (csrc/conv16ws.hip).  The RGB stem's zero-extended pack (3 -> 16 reduction channels) is folded like any other.  Returns
         (packed, shift) or None when the layer keeps the epilogue affine (transposed and stride-2 layers, layers without BatchNorm, fp32 mode
         unless `allow_f32`)."""
-        if not EVAL_FOLD_WEIGHTS or not getattr(self, 'fold_eval', True) or self.kind not in ('conv3', 'conv1') or self.bn is None:
+        if not EVAL_FOLD_WEIGHTS or not self.fold_eval or self.kind not in ('conv3', 'conv1') or self.bn is None:
             return None
         f32 = PRECISION == 'fp32'
         if f32 and not allow_f32:
@@ -188,8 +213,8 @@ class ConvLayer:
         pad = cin_total if cin_total != self.Cin else None       # RGB stem: 3 -> 16 zero-extended reduction channels
         sc, sh = self.eval_fold()
         ver = (self.weight._version, self.fold_version, WEIGHTS_EPOCH[0], tuple(self.cfg), f32)
-        if getattr(self, 'wpe', None) is None or self.wpe_version != ver:
-            self.wpe = engine.pack_weights(self.weight.detach(), self.cfg, 0, Cin_pad=pad, out=getattr(self, 'wpe', None), cout_scale=sc, split=f32)
+        if self.wpe is None or self.wpe_version != ver:
+            self.wpe = engine.pack_weights(self.weight.detach(), self.cfg, 0, Cin_pad=pad, out=self.wpe, cout_scale=sc, split=f32)
             self.wpe_version = ver
         return self.wpe, sh
 
@@ -199,7 +224,7 @@ class ConvLayer:
         399 us per 64 tiles for 0.8 GB).  The convolution does not care in which order its input channels arrive: the sources are passed as
         [skip, x] with the weight's input channels permuted to match, and one padding chunk of zero weights behind x makes the count even - the
         out-image form with pair requests.  Returns the output Src, or None when the launch is not that kernel's (the caller takes forward())."""
-        if PRECISION != 'bf16' or self.kind != 'conv3' or self.bn is None or len(srcs) != 2 or not EVAL_FOLD_WEIGHTS or not getattr(self, 'fold_eval', True):
+        if PRECISION != 'bf16' or self.kind != 'conv3' or self.bn is None or len(srcs) != 2 or not EVAL_FOLD_WEIGHTS or not self.fold_eval:
             return None
         a, b = srcs
         if (a.C // 16) % 2 == 0 or (b.C // 16) % 2 or a.C % 16 or b.C % 16 or a.C + b.C != self.Cin:
@@ -215,7 +240,7 @@ class ConvLayer:
             return None
         sc, sh = self.eval_fold()
         ver = (self.weight._version, self.fold_version, WEIGHTS_EPOCH[0], tuple(self.cfg), a.C)       # (a.C: the split point of the channel permutation)
-        if getattr(self, 'wps', None) is None or self.wps_version != ver:
+        if self.wps is None or self.wps_version != ver:
             w = self.weight.detach()
             wz = torch.zeros((w.shape[0], 16, w.shape[2], w.shape[3]), dtype=w.dtype, device=w.device)
             wperm = torch.cat([w[:, a.C:], w[:, :a.C], wz], 1).contiguous()          # input channels: [skip | x | padding chunk]
@@ -223,7 +248,7 @@ class ConvLayer:
             self.wps_version = ver
         kw = dict(oshift=sh, orelu=relu and not DEBUG_NORELU, H=H, W=W, pad_chunks=1)
         key = (a.N, H, W, a.C, b.C, a.off, b.off, engine.CONV_DEBUG, PRECISION)      # (the tests flip CONV_DEBUG to force the one-tile kernel: another answer)
-        elig = self.__dict__.setdefault('_swapped_eligible', {})
+        elig = self._swapped_eligible
         if key not in elig:
             elig[key] = engine.conv_forward([b, a], self.wps, self.Cout, self.cfg, 9, query_ws=True, **kw) == 2
         if not elig[key]:
@@ -281,10 +306,9 @@ class ConvLayer:
             out, _ = engine.conv_forward(srcs, self.wp, self.Cout, self.cfg, self.taps, self.transposed, bias=bias, H=H, W=W,
                                          out_dtype=out_dtype, eres=eres)
             if training:
-                self.saved = (srcs, out, H, W)
-                self.node_relu, self.node_res = False, None
+                rec = self.rec = ConvRecord(self, srcs, out, H, W, False)
                 if TAPE is not None:
-                    TAPE.append(self)
+                    TAPE.append(rec)
             return Src(out)
         if not training:
             ep = self.eval_pack([s.C for s in srcs])
@@ -311,33 +335,23 @@ class ConvLayer:
                   BN_MOMENTUM if getattr(bn, 'momentum', None) is None else float(bn.momentum),
                   _lib.ptr(bn.running_mean), _lib.ptr(bn.running_var), _lib.ptr(self.scale), _lib.ptr(self.shift),
                   _lib.ptr(self.save_mean), _lib.ptr(self.save_invstd), _lib.stream_ptr())
-        self.saved = (srcs, raw, H, W)
-        self.node_relu, self.node_res = relu, None
-        self.fold_version = None               # the running statistics just moved: an eval-mode fold is stale
+        rec = self.rec = ConvRecord(self, srcs, raw, H, W, relu)
         if TAPE is not None:
-            TAPE.append(self)
+            TAPE.append(rec)
+        self.fold_version = None               # the running statistics just moved: an eval-mode fold is stale
         return Src(raw, self.scale, self.shift, relu=relu)
-
-
-class FuseTerm(C.Structure):                   # cdnet_fuse_term (include/cdnet_hip.h)
-    _fields_ = [('x', C.c_void_p), ('Hs', C.c_int), ('Ws', C.c_int), ('scale', C.c_void_p), ('shift', C.c_void_p),
-                ('f16', C.c_int), ('pad_', C.c_int)]
-
-
-class GradTerm(C.Structure):                   # cdnet_grad_term
-    _fields_ = [('g', C.c_void_p), ('cstride', C.c_int), ('coff', C.c_int)]
 
 
 class FuseNode:
     """out = [relu](sum of 1..4 terms) through cdnet_fuse_sum: the residual adds and multi-resolution fuse sums of HRNet.
     Terms are Src objects: plain bf16 tensors or raw (fp16) BatchNorm-pending convolution outputs (their scale / shift is
     applied on the fly, without ReLU); lower-resolution terms are up-sampled bilinearly.  With `out` the result lands in
-    the channel slice [out_coff, out_coff + C) of a wider tensor (torch.cat of the branches).  In a training forward the
-    node goes onto the tape; backward() routes the output gradient to every term."""
+    the channel slice [out_coff, out_coff + C) of a wider tensor (torch.cat of the branches).  A training forward puts a
+    FuseRecord onto the tape; the tape walk routes the output gradient to every term."""
+    __slots__ = ('name',)
 
     def __init__(self, name):
         self.name = name
-        self.saved = None
 
     def forward(self, terms, relu, out=None, out_coff=0, training=False):
         """`out` (optional) is the wider [N,H,W,Ctot] tensor whose channel slice receives the sum; it also fixes H, W"""
@@ -363,81 +377,9 @@ class FuseNode:
         _lib.call(_lib.entry('cdnet_fuse_sum', f32), C.byref(arr), len(terms), N, H, W, Cc, int(relu), _lib.ptr(o), cs, out_coff,
                   _lib.stream_ptr())
         if training:
-            self.saved = (list(terms), o, relu, H, W, Cc, out_coff)
             if TAPE is not None:
-                TAPE.append(self)
+                TAPE.append(FuseRecord(self, list(terms), o, relu, H, W, Cc, out_coff))
         return Src(o) if out is None else None
-
-    def backward(self, tr, grads, add):
-        """tr: the Trainer (buffer pool).  Gradient of the (slice of the) output -> one contribution per term."""
-        terms, o, relu, H, W, Cc, coff = self.saved
-        sliced = o.shape[3] != Cc
-        if sliced:
-            d, dcs, dco = tr.cat_grad(o, grads), o.shape[3], coff      # the whole concatenation's gradient, summed once
-            if d is None:
-                return
-        else:
-            gl = tr.take(grads, id(o))
-            if gl is None:
-                return
-            if relu and self._residual_tail(tr, grads, gl, terms, o, H, W, Cc):
-                return
-            if relu or len(gl) > 1 or gl[0].coff or gl[0].cstride not in (0, Cc):
-                d = tr.buf(('dfuse', self.name), o.shape, o.dtype)
-                tr.grad_sum(gl, o if relu else None, o.shape[0] * H * W, Cc, d)
-            else:
-                d = gl[0].t
-            dcs, dco = 0, 0
-        N = o.shape[0]
-        for k, t in enumerate(terms):
-            if t.Hs == H and t.Ws == W:
-                add(t.x, tr.G(d, H, W, coff=dco, cstride=dcs))
-            else:
-                din = tr.buf(('dup', self.name, k), (N, t.Hs, t.Ws, Cc), d.dtype)
-                _lib.call(_lib.entry('cdnet_upsample_bilinear_backward', d.dtype == torch.float32), _lib.ptr(d),
-                          N, H, W, Cc, dcs, dco, t.Hs, t.Ws, _lib.ptr(din), _lib.stream_ptr())
-                add(t.x, tr.G(din, t.Hs, t.Ws))
-
-
-def _residual_tail(self, tr, grads, gl, terms, o, H, W, Cc):
-    """relu(bn(y) + x) with x stored and y read by this node alone (BasicBlock / Bottleneck tails, seg_hrnet_rev1.py:76-92, :113-133): the
-    masked sum of the consumers' gradients is the first thing y's BatchNorm backward computes anyway (the kernels' residual form: mask read
-    from the stored output, dz stored for the other branch - what the DAM head's residual units use), so the separate grad_sum pass - one
-    more read and write of the tensor - is skipped and the gradient list goes to y's layer as it is.  Returns False when the shape is not that."""
-    if DEBUG_NORELU:
-        return False
-    if len(terms) == 1:
-        # relu(bn(y)) stored for a stride-2 reader (`_plain`, the down-sampling chains): y's BatchNorm backward takes the ReLU mask from its
-        # own forward values - no masked sum at all
-        y = terms[0]
-        P = tr._producer.get(id(y.x)) if y.scale is not None else None
-        if P is None or P.bn is None or getattr(P, 'node_res', None) is not None or tr._readers.get(id(y.x), 0) != 1 or id(y.x) in grads \
-                or tuple(y.x.shape) != tuple(o.shape) or getattr(P, 'fused_res_of', None) is not None or (y.Hs, y.Ws) != (H, W):
-            return False
-        P.node_relu, P.node_res = True, None
-        grads[id(y.x)] = gl
-        return True
-    if len(terms) != 2 or len(gl) > 3:
-        return False
-    bn_t = [t for t in terms if t.scale is not None]
-    if not bn_t or any((t.Hs, t.Ws) != (H, W) for t in terms):
-        return False
-    # (two BatchNorm terms - a Bottleneck with its downsample branch: the one whose layer comes first in backward takes the list, the other
-    #  one reads the dz that pass stores)
-    y = max(bn_t, key=lambda t: tr._tape_pos.get(id(tr._producer.get(id(t.x))), -1))
-    x = terms[1] if terms[0] is y else terms[0]
-    P = tr._producer.get(id(y.x))
-    if P is None or P.bn is None or getattr(P, 'node_res', None) is not None or tr._readers.get(id(y.x), 0) != 1 or id(y.x) in grads \
-            or tuple(y.x.shape) != tuple(o.shape) or getattr(P, 'fused_res_of', None) is not None:
-        return False
-    if any(g.pooled or g.oy or g.ox or (g.Hg, g.Wg) != (H, W) for g in gl):
-        return False
-    P.node_relu, P.node_res, P.node_res_grad_to = 2, o, x.x
-    grads[id(y.x)] = gl
-    return True
-
-
-FuseNode._residual_tail = _residual_tail
 
 
 def input_pack(x):
@@ -476,7 +418,7 @@ def residual_unit_eval(c1, c2, cr, x, relu2=True, dot=None):
     the three-launch form).  `dot` = (weights f32 [Cout], bias f32 [1]) of a 1x1 classifier that is the unit's ONLY reader (the DAM head's
     point_conv over the point feature, model_unet_rev1.py:252-253): its logits leave with the launch (cdnet_conv_args.dot_out), the
     64-channel output is never stored and a PointLogit comes back - when the launch is not eligible for that, the plain Src as usual."""
-    if not (RU_EVAL_ONE_LAUNCH and EVAL_FOLD_WEIGHTS) or not getattr(c2, 'fold_eval', True) or x.pool or x.C % 16 or c2.Cout % 16:
+    if not (RU_EVAL_ONE_LAUNCH and EVAL_FOLD_WEIGHTS) or not c2.fold_eval or x.pool or x.C % 16 or c2.Cout % 16:
         return None
     H, W = x.logical_hw()
     if H % 16 or W % 16 or x.C != cr.Cin:
@@ -491,15 +433,15 @@ def residual_unit_eval(c1, c2, cr, x, relu2=True, dot=None):
     # the 1x1 branch's pack in c2's configuration, in a buffer of this form's own (`cr` and its packs - which the trainer's batched re-pack
     # holds raw pointers to - are left alone): the two packs lie end to end per output-channel tile
     rver = (cr.weight._version, WEIGHTS_EPOCH[0], tuple(c2.cfg), f32)
-    if getattr(c2, 'ru_wr', None) is None or c2.ru_wr_version != rver:
-        c2.ru_wr = engine.pack_weights(cr.weight.detach(), c2.cfg, 0, out=getattr(c2, 'ru_wr', None), split=f32)
+    if c2.ru_wr is None or c2.ru_wr_version != rver:
+        c2.ru_wr = engine.pack_weights(cr.weight.detach(), c2.cfg, 0, out=c2.ru_wr, split=f32)
         c2.ru_wr_version = rver
     # 16-bit path, an odd number of one-tap chunks (the first unit: 16 input channels): one more one-tap chunk of ZERO weights makes the chunk
     # count even - conv_ws16_kernel's out-image form (whole-line stores by the movers, pair requests) instead of the consumers' direct stores:
     # 548 -> ~440 us per 64 tiles on that launch (engine.conv_forward(pad_chunks=))
     pad = 1 if (not f32 and (x.C // 16) % 2 == 1 and c2.cfg[1] == 16) else 0
     ver = (c2.wpe_version, rver, None if cr.bias is None else cr.bias._version, PRECISION, pad)
-    if getattr(c2, 'ru_pack', None) is None or c2.ru_pack_version != ver:
+    if c2.ru_pack is None or c2.ru_pack_version != ver:
         BN = c2.cfg[2]
         ntile = -(-c2.Cout // BN)
         a, b = ep[0].view(ntile, -1), c2.ru_wr.view(ntile, -1)   # per output-channel tile: the nine-tap chunks, then the one-tap chunks
@@ -514,7 +456,7 @@ def residual_unit_eval(c1, c2, cr, x, relu2=True, dot=None):
     # (the persistent kernel also on small launches - nothing else computes this form: a per-launch request, cdnet_conv_args.debug bit 64
     #  through engine.conv_forward(debug_or=); no module state changes, the path is re-entrant across streams)
     # which kernel serves the launch depends on its shape and flags only: asked once per shape, on a placeholder for conv1's output
-    elig = c2.__dict__.setdefault('_ru_eligible', {})
+    elig = c2._ru_eligible
     key = (x.N, H, W, x.C, hC, PRECISION, keep, bool(relu2))
     want_dot = dot is not None and RU_EVAL_POINT_DOT and relu2
     kw = dict(oshift=c2.ru_shift, H=H, W=W, taps1=1, pad_chunks=pad, debug_or=64)

@@ -2,8 +2,8 @@
 backward, gradient all-reduce over RCCL, optimiser step - the device-side replacement of the body of the reference's
 train_util_dam.train (train_util_dam.py:54-311) with the host loops (:73-142, :278-289) moved onto the GPU.
 
-This module is the tape walk.  No autograd: the forward records a tape of the convolution layers it ran; backward walks the
-tape in reverse.  For every layer it (1) turns the consumers' gradients into the gradient of the raw convolution output
+This module is the tape walk.  No autograd: the forward leaves one record per convolution layer and fuse node it ran
+(runtime.ConvRecord / FuseRecord); backward walks the tape in reverse and reads those records only.  For every layer it (1) turns the consumers' gradients into the gradient of the raw convolution output
 (BatchNorm + residual + ReLU + max-pool/pad routing fused, cdnet_bn_backward), (2) computes dW on the matrix cores
 (cdnet_conv_backward_weight, on a second stream, its split-K sums deferred and batched) and (3) computes the input gradient
 as a forward convolution with a flipped/transposed weight pack (cdnet_conv_forward); it tells the all-reduce which
@@ -19,21 +19,11 @@ import os
 import torch
 
 from . import _lib, engine, optim, runtime, streams
+from ._lib import BnBwdArgs, GradIn, GradTerm             # noqa: F401 (the mirrors live in _lib; the names resolve here as before)
 from .allreduce import BucketReducer, bucketed_allreduce
 from .engine import Src
 from .optim import HEAD_PARAMS, FlatState                    # noqa: F401 (HEAD_PARAMS: the tests import it from here)
 from .synth import synthetic_batch
-
-
-class GradIn(C.Structure):
-    _fields_ = [('g', C.c_void_p), ('Hg', C.c_int), ('Wg', C.c_int), ('oy', C.c_int), ('ox', C.c_int),
-                ('pooled', C.c_int), ('coff', C.c_int), ('cstride', C.c_int), ('pad_', C.c_int)]
-
-
-class BnBwdArgs(C.Structure):
-    _fields_ = [('raw', C.c_void_p), ('res', C.c_void_p), ('scale', C.c_void_p), ('shift', C.c_void_p),
-                ('mean', C.c_void_p), ('invstd', C.c_void_p), ('gin', GradIn * 3), ('ngin', C.c_int),
-                ('f16', C.c_int), ('relu', C.c_int), ('N', C.c_int), ('H', C.c_int), ('W', C.c_int), ('C', C.c_int)]
 
 
 # workgroups of one weight-gradient launch while it runs beside the input-gradient chain (bf16 mode; see _wgrad_wgs):
@@ -104,13 +94,7 @@ def _wgrad_wgs(beside, HW, Cout):
     return _WGRAD_WGS_DEEP if HW <= _WGRAD_DEEP_HW or HW > 65536 else _WGRAD_WGS_SHALLOW    # (512 x 512 layers of HRNet: 128 again)
 
 
-class GradTerm(C.Structure):
-    _fields_ = [('g', C.c_void_p), ('cstride', C.c_int), ('coff', C.c_int)]
-
-
 class Trainer:
-    G = _G
-
     def __init__(self, model, lr=1e-3, weight_decay=1e-4, betas=(0.9, 0.99), eps=None, quirk_sample0=True,
                  world_size=1, bucket_mb=25, optimizer='adam', momentum=0.95):
         """optimizer: one of cdnet_amd.optim.OPTIMIZERS (utils.py:907-939, matched case-insensitively); momentum serves 'sgd' only;
@@ -227,7 +211,7 @@ class Trainer:
     def take(self, grads, key):
         """pop the gradient contributions of a stored tensor for a consumer on the CURRENT stream: a contribution computed beside the chain
         (_RU_1X1_SIDE: the residual units' 1x1 backward-data on the weight-gradient stream) carries an event the consumer's stream must
-        wait for first - wherever the list is consumed (a layer's BatchNorm backward, cat_grad, FuseNode.backward)"""
+        wait for first - wherever the list is consumed (a layer's BatchNorm backward, cat_grad, _fuse_backward)"""
         gl = grads.pop(key, None)
         if gl is not None:
             for g_ in gl:
@@ -345,30 +329,30 @@ class Trainer:
         _lib.call('cdnet_dam_head_backward', C.byref(hf[0]), C.byref(hf[1]), C.byref(hf[2]), _lib.ptr(m.head_weight_block()),
                   _lib.ptr(dmask), _lib.ptr(dpoint), _lib.ptr(ddir), N, H, W, _lib.ptr(df[0]), _lib.ptr(df[1]),
                   _lib.ptr(df[2]), _lib.ptr(ws), ws.numel(), _lib.ptr(dhead), _lib.stream_ptr())
-        self._run_tape([(getattr(f, 'grad_to', (f.x,))[0], _G(d, H, W)) for f, d in zip((f1, f2, f3), df)], None)
+        self._run_tape([((f.grad_to or (f.x,))[0], _G(d, H, W)) for f, d in zip((f1, f2, f3), df)], None)
 
     def _head_fusable(self, f1, f2, f3):
         """cdnet_dam_head_backward_fused's one case: fp32 mode, the rev1 head over three plain stored fp32 features, the third one the
         output of a residual unit with the fused epilogue (BatchNorm + mask from the stored output) that nothing on the tape reads.
-        Returns that unit's conv2 layer or None"""
+        Returns the record of that unit's conv2 or None"""
         if not HEAD_BWD_FUSE or runtime.PRECISION != 'fp32' or getattr(self.model, 'VARIANT', None) != 'rev1':
             return None
         for f in (f1, f2, f3):
             if f.x.dtype != torch.float32 or f.scale is not None or f.shift is not None or f.res is not None or f.relu or f.pool \
-                    or hasattr(f, 'grad_to') or tuple(f.off) != (0, 0) or f.C != 64:
+                    or f.grad_to is not None or tuple(f.off) != (0, 0) or f.C != 64:
                 return None
         owner = None
-        for Lt in self.tape:
-            if isinstance(Lt, runtime.FuseNode):
-                if any(t.x is f3.x for t in Lt.saved[0]):
+        for Rt in self.tape:
+            if isinstance(Rt, runtime.FuseRecord):
+                if any(t.x is f3.x for t in Rt.terms):
                     return None
                 continue
-            if any(sx.x is f3.x or sx.res is f3.x for sx in Lt.saved[0]):
+            if any(sx.x is f3.x or sx.res is f3.x for sx in Rt.srcs):
                 return None
-            if Lt.saved[1] is f3.x:
-                owner = getattr(Lt, 'fused_res_of', None) if Lt.kind == 'conv1' else None
-        if owner is None or owner.bn is None or getattr(owner, 'node_relu', True) != 2 or getattr(owner, 'node_res', None) is not f3.x \
-                or owner.saved[1].dtype != torch.float32 or tuple(owner.saved[1].shape) != tuple(f3.x.shape):
+            if Rt.out is f3.x:
+                owner = Rt.fused_res_of if Rt.layer.kind == 'conv1' else None
+        if owner is None or owner.layer.bn is None or owner.relu != 2 or owner.res is not f3.x \
+                or owner.out.dtype != torch.float32 or tuple(owner.out.shape) != tuple(f3.x.shape):
             return None
         return owner
 
@@ -409,41 +393,41 @@ class Trainer:
         # who reads what: a BatchNorm layer whose raw output has exactly one reader - a 3x3 convolution - gets the first pass of its
         # backward (the channel sums) from that reader's backward-data launch (_input_backward), see _stats_fusable
         self._readers, self._producer, self._bn_partials = {}, {}, {}
-        self._tape_pos = {id(Lt): k for k, Lt in enumerate(self.tape)}
-        for Lt in self.tape:
-            if isinstance(Lt, runtime.FuseNode):
-                for t in Lt.saved[0]:                # (counted too: FuseNode.backward hands a residual sum's BatchNorm term its gradients unsummed
+        self._tape_pos = {Rt: k for k, Rt in enumerate(self.tape)}
+        for Rt in self.tape:
+            if isinstance(Rt, runtime.FuseRecord):
+                for t in Rt.terms:                   # (counted too: _fuse_backward hands a residual sum's BatchNorm term its gradients unsummed
                     self._readers[id(t.x)] = self._readers.get(id(t.x), 0) + 1       # only when nothing else reads that term)
                 continue
-            for sx in Lt.saved[0]:
+            for sx in Rt.srcs:
                 self._readers[id(sx.x)] = self._readers.get(id(sx.x), 0) + 1
                 if sx.res is not None:
                     self._readers[id(sx.res)] = self._readers.get(id(sx.res), 0) + 1
-            self._producer[id(Lt.saved[1])] = Lt
+            self._producer[id(Rt.out)] = Rt
         side = self._side_stream()
         self._side_active = side is not None
         if self._packb_pending:
             torch.cuda.current_stream().wait_event(self._event('packb'))      # backward-data packs made beside the forward
             self._packb_pending = False
-        for k, L in enumerate(reversed(self.tape)):
-            if isinstance(L, runtime.FuseNode):
-                L.backward(self, grads, add)
+        for k, R in enumerate(reversed(self.tape)):
+            if isinstance(R, runtime.FuseRecord):
+                self._fuse_backward(R, grads, add)
                 continue
-            gl = self.take(grads, id(L.saved[1]))
+            gl = self.take(grads, id(R.out))
             if gl is None:
                 continue
-            owner = getattr(L, 'fused_res_of', None)
+            owner = R.fused_res_of
             if owner is not None:
                 # ResidualUnit.conv_1x1 with the fused residual epilogue: its stored output is the unit's output f.  The consumers'
                 # gradients of f first pass bn2 + ReLU of the other branch (mask read from f); that dz is this layer's gradient.
-                grads.setdefault(id(owner.saved[1]), []).extend(gl)
-                owner.deferred_layer = L
+                grads.setdefault(id(owner.out), []).extend(gl)
+                owner.deferred = R
                 continue
-            self._layer_backward(k, L, gl, grads, add, side)
-            d = getattr(L, 'deferred_layer', None)
+            self._layer_backward(k, R, gl, grads, add, side)
+            d = R.deferred
             if d is not None:
-                L.deferred_layer = None
-                self._layer_backward(('deferred', k), d, self.take(grads, id(d.saved[1])), grads, add, side)
+                R.deferred = None
+                self._layer_backward(('deferred', k), d, self.take(grads, id(d.out)), grads, add, side)
         if side is not None:
             with _on_stream(side):
                 self._flush_reduces()
@@ -452,6 +436,73 @@ class Trainer:
             torch.cuda.current_stream().wait_event(ev)
         else:
             self._flush_reduces()
+
+    def _fuse_backward(self, R, grads, add):
+        """a fuse node: gradient of the (slice of the) output -> one contribution per term"""
+        terms, o, relu, H, W, Cc, coff, name = R.terms, R.out, R.relu, R.H, R.W, R.C, R.coff, R.node.name
+        sliced = o.shape[3] != Cc
+        if sliced:
+            d, dcs, dco = self.cat_grad(o, grads), o.shape[3], coff      # the whole concatenation's gradient, summed once
+            if d is None:
+                return
+        else:
+            gl = self.take(grads, id(o))
+            if gl is None:
+                return
+            if relu and self._residual_tail(grads, gl, terms, o, H, W, Cc):
+                return
+            if relu or len(gl) > 1 or gl[0].coff or gl[0].cstride not in (0, Cc):
+                d = self.buf(('dfuse', name), o.shape, o.dtype)
+                self.grad_sum(gl, o if relu else None, o.shape[0] * H * W, Cc, d)
+            else:
+                d = gl[0].t
+            dcs, dco = 0, 0
+        N = o.shape[0]
+        for k, t in enumerate(terms):
+            if t.Hs == H and t.Ws == W:
+                add(t.x, _G(d, H, W, coff=dco, cstride=dcs))
+            else:
+                din = self.buf(('dup', name, k), (N, t.Hs, t.Ws, Cc), d.dtype)
+                _lib.call(_lib.entry('cdnet_upsample_bilinear_backward', d.dtype == torch.float32), _lib.ptr(d),
+                          N, H, W, Cc, dcs, dco, t.Hs, t.Ws, _lib.ptr(din), _lib.stream_ptr())
+                add(t.x, _G(din, t.Hs, t.Ws))
+
+    def _residual_tail(self, grads, gl, terms, o, H, W, Cc):
+        """relu(bn(y) + x) with x stored and y read by this node alone (BasicBlock / Bottleneck tails, seg_hrnet_rev1.py:76-92, :113-133): the
+        masked sum of the consumers' gradients is the first thing y's BatchNorm backward computes anyway (the kernels' residual form: mask read
+        from the stored output, dz stored for the other branch - what the DAM head's residual units use), so the separate grad_sum pass - one
+        more read and write of the tensor - is skipped and the gradient list goes to y's layer as it is.  Returns False when the shape is not that."""
+        if runtime.DEBUG_NORELU:
+            return False
+        if len(terms) == 1:
+            # relu(bn(y)) stored for a stride-2 reader (`_plain`, the down-sampling chains): y's BatchNorm backward takes the ReLU mask from its
+            # own forward values - no masked sum at all
+            y = terms[0]
+            P = self._producer.get(id(y.x)) if y.scale is not None else None
+            if P is None or P.layer.bn is None or P.res is not None or self._readers.get(id(y.x), 0) != 1 or id(y.x) in grads \
+                    or tuple(y.x.shape) != tuple(o.shape) or P.fused_res_of is not None or (y.Hs, y.Ws) != (H, W):
+                return False
+            P.relu, P.res = True, None
+            grads[id(y.x)] = gl
+            return True
+        if len(terms) != 2 or len(gl) > 3:
+            return False
+        bn_t = [t for t in terms if t.scale is not None]
+        if not bn_t or any((t.Hs, t.Ws) != (H, W) for t in terms):
+            return False
+        # (two BatchNorm terms - a Bottleneck with its downsample branch: the one whose layer comes first in backward takes the list, the other
+        #  one reads the dz that pass stores)
+        y = max(bn_t, key=lambda t: self._tape_pos.get(self._producer.get(id(t.x)), -1))
+        x = terms[1] if terms[0] is y else terms[0]
+        P = self._producer.get(id(y.x))
+        if P is None or P.layer.bn is None or P.res is not None or self._readers.get(id(y.x), 0) != 1 or id(y.x) in grads \
+                or tuple(y.x.shape) != tuple(o.shape) or P.fused_res_of is not None:
+            return False
+        if any(g.pooled or g.oy or g.ox or (g.Hg, g.Wg) != (H, W) for g in gl):
+            return False
+        P.relu, P.res, P.res_grad_to = 2, o, x.x
+        grads[id(y.x)] = gl
+        return True
 
     def _weights_done(self, params):
         """the weight-gradient launches of a layer are queued (current stream = the one they run on): sum their slabs now or later, then
@@ -483,15 +534,15 @@ class Trainer:
             self._overlap_done(params)
         self._rd_pending, self._rd_params, self._rd_bytes = [], [], 0
 
-    def _layer_backward(self, k, L, gl, grads, add, side):
+    def _layer_backward(self, k, R, gl, grads, add, side):
         """one convolution layer: BatchNorm / residual / ReLU backward of its output, weight gradient (side stream), input gradient.
         `gl` comes from take() on this stream: the events of contributions computed beside the chain are already waited for"""
-        srcs, out, Hl, Wl = L.saved
+        L, srcs, out, Hl, Wl = R.layer, R.srcs, R.out, R.H, R.W
         No, Ho, Wo, Co = out.shape
         params = (L.weight, L.bias, None if L.bn is None else L.bn.weight, None if L.bn is None else L.bn.bias)
         part = self._bn_partials.pop(id(out), None)
         if len(gl) == 1 and gl[0].masked:
-            g = self._bn_backward_masked(L, out, gl[0], add)
+            g = self._bn_backward_masked(R, out, gl[0], add)
         elif part is not None:
             # the reader's backward-data launch left the channel sums: finalize + second pass only
             assert len(gl) == 1, (L.name, len(gl))
@@ -499,7 +550,7 @@ class Trainer:
             g = self.buf(('draw', L.name), (No, Ho, Wo, Co), runtime.act_dtype())
             _lib.call('cdnet_bn_backward_apply', C.byref(a), _lib.ptr(ktab), _lib.ptr(g), _lib.stream_ptr())
         elif L.bn is not None or len(gl) > 1 or gl[0].pooled or gl[0].coff or (gl[0].cstride not in (0, Co)):
-            g = self._bn_backward(L, out, gl, add)
+            g = self._bn_backward(R, out, gl, add)
         else:
             g = gl[0].t                                     # plain pass-through (conv_1x1 residual branch)
         if side is None:
@@ -513,7 +564,7 @@ class Trainer:
             # keeps its lead either way)
             ev = self._event(k)
             ev.record()             # (recorded after backward-data instead, the weight gradient overlaps the HBM-bound BatchNorm passes of
-            beside = _RU_1X1_SIDE and L.kind == 'conv1' and isinstance(k, tuple) and getattr(L, 'needs_input_grad', True)
+            beside = _RU_1X1_SIDE and L.kind == 'conv1' and isinstance(k, tuple) and L.needs_input_grad
             if not beside:
                 self._input_backward(L, srcs, g, Hl, Wl, add)      # the next layer rather than the convolution: -2 %)
             side.wait_event(ev)
@@ -541,10 +592,11 @@ class Trainer:
                   _lib.ptr(partial), partial.shape[0], _lib.ptr(ktab), _lib.stream_ptr())
         return a, ktab
 
-    def _bn_backward_masked(self, L, out, g, add):
+    def _bn_backward_masked(self, R, out, g, add):
         """a residual unit's bn2 backward behind cdnet_dam_head_backward_fused: g.t is dz already (the consumer's gradient through the
         unit's ReLU), so both passes take it as one plain relu = 0 source without residual - the sums pass reads two tensors instead of
         three and stores none, the same sums in the same order as _bn_backward's; dz goes to the 1x1 branch as there"""
+        L = R.layer
         No, Ho, Wo, Co = out.shape
         a = self._bn_args(L, out, [_G(g.t, g.Hg, g.Wg)], res=None, relu=0)
         draw = self.buf(('draw', L.name), (No, Ho, Wo, Co), runtime.act_dtype())
@@ -552,7 +604,7 @@ class Trainer:
         bn = L.bn
         _lib.call('cdnet_bn_backward', C.byref(a), _lib.ptr(bn.weight.detach()), _lib.ptr(bn.weight.grad), _lib.ptr(bn.bias.grad),
                   _lib.ptr(ws), ws.numel(), _lib.ptr(draw), None, _lib.stream_ptr())
-        add(L.node_res, _G(g.t, Ho, Wo))
+        add(R.res, _G(g.t, Ho, Wo))
         return draw
 
     def _stats_fusable(self, L, srcs, H, W, N, wpb, cfgb, cin_total):
@@ -562,20 +614,21 @@ class Trainer:
         # 16-bit form - the sums accumulated by the movers of conv_ws_kernel - saved 11 reduce passes and was not faster (the movers'
         # per-element arithmetic costs the matrix pipe issue time); it was removed in round 3.
         f32 = runtime.PRECISION == 'fp32'
-        if not f32 or os.environ.get('CDNET_BN_STATS_FUSE', '1') != '1' or getattr(runtime, 'DEBUG_NORELU', False):
+        if not f32 or os.environ.get('CDNET_BN_STATS_FUSE', '1') != '1' or runtime.DEBUG_NORELU:
             return None
         if L.kind != 'conv3' or L.transposed or len(srcs) != 1:
             return None
         sx = srcs[0]
-        if getattr(sx, 'is_input', False) or sx.scale is None or sx.shift is None or sx.relu is not True or sx.res is not None or sx.pool \
-                or tuple(sx.off) != (0, 0) or sx.x.dtype != runtime.raw_dtype() or hasattr(sx, 'grad_to') or sx.row_stride:
+        if sx.is_input or sx.scale is None or sx.shift is None or sx.relu is not True or sx.res is not None or sx.pool \
+                or tuple(sx.off) != (0, 0) or sx.x.dtype != runtime.raw_dtype() or sx.grad_to is not None or sx.row_stride:
             return None
         if f32 and cin_total % 64:
             return None
-        P = self._producer.get(id(sx.x))
-        if P is None or P.bn is None or getattr(P, 'node_res', None) is not None or getattr(P, 'node_relu', True) is not True \
+        PR = self._producer.get(id(sx.x))
+        if PR is None or PR.layer.bn is None or PR.res is not None or PR.relu is not True \
                 or self._readers.get(id(sx.x), 0) != 1 or tuple(sx.x.shape) != (N, H, W, cin_total):
             return None
+        P = PR.layer
         key = ('statsfusable', L.name, N, H, W, runtime.PRECISION)
         hit = self._bufs.get(key)
         if hit is None:
@@ -609,9 +662,10 @@ class Trainer:
         a.N, a.H, a.W, a.C = out.shape
         return a
 
-    def _bn_backward(self, L, out, gl, add):
+    def _bn_backward(self, R, out, gl, add):
+        L = R.layer
         No, Ho, Wo, Co = out.shape
-        res = getattr(L, 'node_res', None)
+        res = R.res
         has_bn = L.bn is not None
         if len(gl) > 3:
             # more consumers than the kernel takes gradient sources (an ablation head's first residual unit feeds two units, four
@@ -622,7 +676,7 @@ class Trainer:
             d = self.buf(('gsum', L.name), (No, Ho, Wo, Co), runtime.act_dtype())
             self.grad_sum(plain, None, No * Ho * Wo, Co, d)
             gl = rest + [_G(d, Ho, Wo)]
-        a = self._bn_args(L, out, gl, res, int(getattr(L, 'node_relu', True)))
+        a = self._bn_args(L, out, gl, res, int(R.relu))
         draw = self.buf(('draw', L.name), (No, Ho, Wo, Co), runtime.act_dtype())
         dz = None
         if res is not None:
@@ -634,9 +688,9 @@ class Trainer:
                   _lib.ptr(ws), ws.numel(), _lib.ptr(draw), _lib.ptr(dz), _lib.stream_ptr())
         if res is not None:
             # gradient of the residual branch = dz; its producer (conv_1x1) is on the tape.  (HRNet's residual sums: `res` is the stored
-            # output the mask is read from, the branch is the block's input - FuseNode.backward names it)
-            add(getattr(L, 'node_res_grad_to', None) if getattr(L, 'node_res_grad_to', None) is not None else res, _G(dz, Ho, Wo))
-            L.node_res_grad_to = None
+            # output the mask is read from, the branch is the block's input - _residual_tail names it)
+            add(R.res_grad_to if R.res_grad_to is not None else res, _G(dz, Ho, Wo))
+            R.res_grad_to = None
         return draw
 
     def _side_stream(self):
@@ -662,7 +716,7 @@ class Trainer:
         cin_real = L.Cin
         mode = {'conv3': 0, 'conv1': 0, 'convT4': 2, 'convT2': 3, 'conv3s2': 6}[L.kind]
         taps, npar, ostride = L.taps, (4 if L.transposed else 1), (2 if L.transposed else 1)
-        cap = _wgrad_wgs(self._side_active and getattr(L, 'needs_input_grad', True), H * W, Cout)
+        cap = _wgrad_wgs(self._side_active and L.needs_input_grad, H * W, Cout)
         coff = 0
         for s in srcs:
             ci_t = _choose_ci_tiles(s.C, Cout)
@@ -686,7 +740,7 @@ class Trainer:
             coff += s.C
         if L.bias is not None and L.bn is None:
             # bias of a BN-less conv (ResidualUnit.conv_1x1): sum of its output gradient == dbeta of the unit's bn2
-            owner = getattr(L, 'bias_grad_from', None)
+            owner = L.bias_grad_from
             if owner is not None:
                 L.bias.grad.copy_(owner.bn.bias.grad)
             else:
@@ -697,7 +751,7 @@ class Trainer:
 
     def _input_backward(self, L, srcs, g, H, W, add):
         """g: the gradient w.r.t. the layer's raw output, or a prepared Src (BatchNorm-backward source of the fused path)"""
-        if not getattr(L, 'needs_input_grad', True):
+        if not L.needs_input_grad:
             return
         N = g.N if isinstance(g, Src) else g.shape[0]
         Cout = L.Cout
@@ -732,10 +786,10 @@ class Trainer:
             engine.conv_forward(views, wpb, cin_total, cfgb, taps=(9 if L.kind == 'convT4' else 1), out=gin, H=H, W=W)
         coff = 0
         for s in srcs:
-            if getattr(s, 'is_input', False):
+            if s.is_input:
                 coff += s.C
                 continue
-            tgt, pool = getattr(s, 'grad_to', (s.x, int(s.pool)))          # a materialised max-pool hands its gradient to the producer
+            tgt, pool = s.grad_to or (s.x, int(s.pool))          # a materialised max-pool hands its gradient to the producer
             add(tgt, _G(gin, H, W, oy=s.off[0], ox=s.off[1], pooled=pool, coff=coff, cstride=cin_total))
             coff += s.C
 
@@ -752,7 +806,7 @@ class Trainer:
         f = self.flat
         base = f.G.data_ptr()
         pend = {}
-        owners = [p for L in self.tape if not isinstance(L, runtime.FuseNode) for p in (L.weight, L.bias, None if L.bn is None else L.bn.weight,
+        owners = [p for L in (R.layer for R in self.tape if not isinstance(R, runtime.FuseRecord)) for p in (L.weight, L.bias, None if L.bn is None else L.bn.weight,
                                                  None if L.bn is None else L.bn.bias) if p is not None]
         for p in owners:
             off = (p.grad.data_ptr() - base) // 4
@@ -1019,7 +1073,7 @@ class AblationTrainer(Trainer):
         for name, f, conv, dl in (('m', f1m, m.mask_conv, dmask), ('d', f2, m.direction_conv, ddir), ('p', f3, m.point_conv, dpoint)):
             if f is None or dl is None:
                 continue
-            heads.append((getattr(f, 'grad_to', (f.x,))[0], self._classifier_backward('dF' + name, f, conv, dl)))
+            heads.append(((f.grad_to or (f.x,))[0], self._classifier_backward('dF' + name, f, conv, dl)))
             params += [conv.weight, conv.bias]
         self._run_tape(heads, params)
 

@@ -37,6 +37,8 @@ grad_sum adds its terms in index order in fp32, masks, and rounds once: the refe
 the requirement is equality for real inputs too.  bias_grad: see bias_depth()."""
 import ctypes as C
 
+from cdnet_amd._lib import GradTerm                     # cdnet_grad_term (test_gpu_glue_kernels builds tables of it too)
+
 EPS = 2.0 ** -24
 SENTINEL = 4096.0                 # exact in bf16; no result here comes near it
 F16_CODE = {'bf16': 0, 'f16': 1, 'f32': 2}
@@ -198,10 +200,6 @@ def upsample_bwd_case(f32, N, Hs, Ws, H, W, Cc, sliced, exact, seed, ref_dtype=N
 # ------------------------------------------------------------------------------------------------------
 # cdnet_grad_sum
 # ------------------------------------------------------------------------------------------------------
-class GradTerm(C.Structure):                   # cdnet_grad_term (include/cdnet_hip.h)
-    _fields_ = [('g', C.c_void_p), ('cstride', C.c_int), ('coff', C.c_int)]
-
-
 def grad_sum_case(f32, npix, Cc, nterm, masked, seed, exact=False):
     """term k reads: k = 0 a tensor of its own with cstride = 0 (= C); k odd a slice of a wider tensor (cstride = C + 8 * (k + 1),
     coff = 8 * k); other k a tensor of its own with cstride = C given.  Returns (got, want) on the CPU, in the output dtype."""

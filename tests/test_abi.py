@@ -28,15 +28,14 @@ def test_library_exports_every_declared_symbol():
 
 def test_ctypes_mirrors_have_the_library_struct_sizes():
     """every argument struct the Python host side mirrors with ctypes has the size the library was compiled with (a field added on one
-    side only would shift every later field silently)"""
-    from cdnet_amd import _lib, engine, runtime, trainer
-    lib = _lib.load()
-    mirrors = {'cdnet_conv_src': engine.ConvSrc, 'cdnet_conv_args': engine.ConvArgs, 'cdnet_pack_job': engine.PackJob,
-               'cdnet_head_feat': runtime.HeadFeat, 'cdnet_wgrad_reduce_desc': _lib.WgradReduceDesc, 'cdnet_grad_in': trainer.GradIn,
-               'cdnet_bn_bwd_args': trainer.BnBwdArgs, 'cdnet_fuse_term': runtime.FuseTerm, 'cdnet_grad_term': trainer.GradTerm}
+    side only would shift every later field silently); the table of mirrors names exactly the structs cdnet_abi_sizeof knows"""
     import ctypes
-    for name, cls in mirrors.items():
-        assert lib.cdnet_abi_sizeof(name.encode()) == ctypes.sizeof(cls), name
+    from cdnet_amd import _lib
+    lib = _lib.load()
+    known = re.findall(r'CDNET_SZ\((cdnet_\w+)\)', open(os.path.join(ROOT, 'cdnet_amd', 'csrc', 'abi.hip')).read())
+    assert len(known) == 16 and set(known) == set(_lib.MIRRORS), set(known) ^ set(_lib.MIRRORS)
+    for name, cls in _lib.MIRRORS.items():
+        assert lib.cdnet_abi_sizeof(name.encode()) == ctypes.sizeof(cls) > 0, name
     assert lib.cdnet_abi_sizeof(b'no_such_struct') == 0
 
 

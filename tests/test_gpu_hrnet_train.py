@@ -289,7 +289,7 @@ def test_fp32_mode_two_steps_follow_the_reference_train_loop(golden, fp32_mode):
 @pytest.mark.parametrize('precision', ['bf16', 'fp32'])
 def test_residual_1x1_backward_beside_the_chain_is_bit_identical_on_hrnet(monkeypatch, precision):
     """HRNet's first residual unit reads the concatenation of the four branches: the input gradient of its 1x1 branch - computed on the
-    weight-gradient stream (trainer._RU_1X1_SIDE) - is consumed by FuseNode.backward / Trainer.cat_grad, not by a convolution layer's
+    weight-gradient stream (trainer._RU_1X1_SIDE) - is consumed by Trainer._fuse_backward / Trainer.cat_grad, not by a convolution layer's
     BatchNorm backward.  Every consumer of a gradient list waits for the producing stream's event (Trainer.take): beside == on the chain,
     bit for bit on every parameter gradient (a missed wait reads a half-written buffer and shows up here)."""
     import torch

@@ -217,7 +217,7 @@ def test_full_size_fp32_step_is_deterministic_learns_and_matches_the_one_tile_ke
     try:
         tr1, p1, l1 = run(3)
         # the routes under test were really taken at this size
-        cfgs = {L.name: L.cfg for L in tr1.tape if hasattr(L, 'cfg')}
+        cfgs = {R.layer.name: R.layer.cfg for R in tr1.tape}
         assert cfgs['upsample_blocks.0.conv2'] == (16, 16, 32) and cfgs['backbone.37'] == (16, 16, 32), cfgs
         fused = [k for k, v in tr1._bufs.items() if isinstance(k, tuple) and k and k[0] == 'statsfusable' and v is not False]
         assert len(fused) >= 6, fused
@@ -228,7 +228,7 @@ def test_full_size_fp32_step_is_deterministic_learns_and_matches_the_one_tile_ke
         variants = {}
         monkeypatch.setenv('CDNET_F32_WS16', '0')
         trv, variants['ws16=0'], gv = first_step()
-        assert {L.name: L.cfg for L in trv.tape if hasattr(L, 'cfg')}['backbone.37'] == (8, 16, 64)
+        assert {R.layer.name: R.layer.cfg for R in trv.tape}['backbone.37'] == (8, 16, 64)
         grads = {'ws16=0': gv}
         monkeypatch.delenv('CDNET_F32_WS16')
         monkeypatch.setenv('CDNET_BN_STATS_FUSE', '0')

@@ -37,14 +37,11 @@ for n, mod in ref.named_modules():
 with torch.no_grad():
     want = ref(x)
     got = m(x.cuda())
-def act_of(layer):
-    srcs, raw, H, W = layer.saved if layer.saved is not None else (None, None, None, None)
-    return raw
 print('%-34s %10s %10s %10s' % ('layer (pre-activation BN output)', 'scale', 'maxerr', 'meanerr'))
 for L in m.conv_layers():
     if mode != 'train':
         break
-    raw = L.saved[1].float().cpu().permute(0, 3, 1, 2)
+    raw = L.rec.out.float().cpu().permute(0, 3, 1, 2)
     if L.bn is not None:
         bn_name = L.name.replace('.up', '.bn1').replace('.conv2', '.bn2').replace('.conv1', '.bn1')
         if L.name.startswith('backbone.'):

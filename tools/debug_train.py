@@ -46,7 +46,7 @@ print('hip losses [total,dce,wdice,mse,ce,dice]', [round(float(v), 5) for v in t
 tr.backward(dm, dp, dd)
 torch.cuda.synchronize()
 print('%-40s %10s' % ('d(raw conv output)', 'rel.err'))
-for L in reversed(tr.tape):
+for L in (R.layer for R in reversed(tr.tape)):        # (the rev1 DAM-Unet's tape holds convolution records only)
     key = ('draw', L.name)
     if key in tr._bufs and L.name in conv_out and conv_out[L.name].grad is not None:
         g = tr._bufs[key].float().cpu().permute(0, 3, 1, 2)
