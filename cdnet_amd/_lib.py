@@ -58,7 +58,9 @@ class GradIn(C.Structure):                   # cdnet_grad_in
 class BnBwdArgs(C.Structure):                # cdnet_bn_bwd_args
     _fields_ = [('raw', C.c_void_p), ('res', C.c_void_p), ('scale', C.c_void_p), ('shift', C.c_void_p),
                 ('mean', C.c_void_p), ('invstd', C.c_void_p), ('gin', GradIn * 3), ('ngin', C.c_int),
-                ('f16', C.c_int), ('relu', C.c_int), ('N', C.c_int), ('H', C.c_int), ('W', C.c_int), ('C', C.c_int)]
+                ('f16', C.c_int), ('relu', C.c_int), ('N', C.c_int), ('H', C.c_int), ('W', C.c_int), ('C', C.c_int),
+                ('hc_coef', C.c_void_p), ('hc_w', C.c_void_p), ('hc_slot', C.c_int), ('hc_k0', C.c_int), ('hc_nk', C.c_int),
+                ('hc_pad_', C.c_int)]
 
 
 class AugSample(C.Structure):                # cdnet_aug_sample
@@ -213,6 +215,8 @@ SIGNATURES = {
     'cdnet_dam_head_backward_fused_scratch_bytes': (_i, []),
     'cdnet_dam_head_backward_fused_workspace_floats': (_sz, []),
     'cdnet_dam_head_backward_fused': (_i, [_vp] * 7 + [_i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    'cdnet_dam_head_backward_coef_scratch_bytes': (_i, []),
+    'cdnet_dam_head_backward_coef': (_i, [_vp] * 7 + [_i, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
     'cdnet_dam_loss_workspace_floats': (_sz, [_i, _i]),
     'cdnet_dam_loss': (_i, [_vp] * 7 + [_i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     'cdnet_dam_loss_classes_workspace_floats': (_sz, [_i, _i, _i]),

@@ -39,6 +39,8 @@ struct BnBwdArgs {
     unsigned short *draw;        // bf16 [N][H][W][C]
     unsigned short *dz_out;      // optional bf16 copy of dz (gradient of the residual branch)
     int rev;                     // apply pass walks the tensor back to front (see cdnet_bn_backward)
+    const float *hc_coef, *hc_w; // head-coefficient source (cdnet_bn_bwd_args.hc_*): rows f32 [px][16], weights f32 [hc_nk][64]
+    int hc_slot, hc_nk;          // ... its position among the sources, 3 or 9 terms (0: none); first column HC_K0(hc_nk), checked by the host
 };
 
 
@@ -384,10 +386,42 @@ __global__ __launch_bounds__(256) void bn_bwd_flat_kernel(BnBwdArgs A) {
     if (!APPLY) bn_write_partial<8>(A.partial, A.C, VPP, s1, s2);
 }
 
+// Head-coefficient source: the columns [K0, K0 + NK) of a pixel's row [dpt | du[9] | dm[3] | 0 0 0] as the aligned vectors that hold
+// them (NK = 3: floats 10..12, NK = 9: floats 1..9); one 64-byte line per pixel, shared by the pixel's 16 threads
+constexpr int HC_K0(int nk) { return nk == 3 ? 10 : 1; }
+template <int NK> struct HcRow;
+template <> struct HcRow<3> {
+    f32x2 a; float b;
+    __device__ __forceinline__ void load(const float *row) { a = *reinterpret_cast<const f32x2 *>(row + 10); b = row[12]; }
+    template <int K> __device__ __forceinline__ float at() const { if constexpr (K < 2) return a[K]; else return b; }
+};
+template <> struct HcRow<9> {
+    f32x4 a, b; f32x2 c;
+    __device__ __forceinline__ void load(const float *row) {
+        a = *reinterpret_cast<const f32x4 *>(row); b = *reinterpret_cast<const f32x4 *>(row + 4); c = *reinterpret_cast<const f32x2 *>(row + 8);
+    }
+    template <int K> __device__ __forceinline__ float at() const {
+        if constexpr (K < 3) return a[K + 1]; else if constexpr (K < 7) return b[K - 3]; else return c[K - 7];
+    }
+};
+template <> struct HcRow<0> {
+    __device__ __forceinline__ void load(const float *) {}
+};
+// the source's value for channel weights w[0 .. NK): xf_axpy16's chain, fma(s, w, +0) first, then fma(s, w, sum)
+template <int NK, int K = 0>
+__device__ __forceinline__ float hc_value(const HcRow<NK> &row, const float (*w)[4], int j, float v = 0.f) {
+    if constexpr (K < NK) return hc_value<NK, K + 1>(row, w, j, fmaf(row.template at<K>(), w[K][j], v));
+    else return v;
+}
+
 // fp32 variants of the flat kernels: 4 channels per thread (one float4 per tensor and pixel), BN_U pixels in flight, plain
 // fp32 arithmetic (no 16-bit rounding of the activation); relu == 2 reads the mask from the stored output in `res`.
-template <int NG, bool RES, bool APPLY>
+// HS >= 0: source HS is a head-coefficient source of NK terms - no tensor is read for it; its value is the head kernels' xf_axpy16 chain
+// (explicit fma from +0, in their order) over the pixel's coefficients and this thread's 4 channels of the NK weight rows, which stay in
+// registers; it takes the tensor's place in the sum over the sources, so every result has the bits of the dense form.
+template <int NG, bool RES, bool APPLY, int HS = -1, int NK = 0>
 __global__ __launch_bounds__(256) void bn_bwd_flat32_kernel(BnBwdArgs A) {
+    static_assert(HS < NG && (HS < 0) == (NK == 0) && (HS < 0 || (RES && !APPLY)), "head-coefficient source: sums pass of the residual form");
     const int VPP = A.C / 4;
     const int slot = (int)threadIdx.x % VPP, c0 = slot * 4;
     float sc[4], sh[4], mu[4], is[4], k1[4], k2[4], k3[4], s1[4], s2[4];
@@ -402,8 +436,14 @@ __global__ __launch_bounds__(256) void bn_bwd_flat32_kernel(BnBwdArgs A) {
     const bool relu = A.relu != 0, outmask = A.relu == 2;
     const float *raw = reinterpret_cast<const float *>(A.raw), *resp = reinterpret_cast<const float *>(A.res);
     float *draw = reinterpret_cast<float *>(A.draw), *dzo = reinterpret_cast<float *>(A.dz_out);
+    float hw[NK > 0 ? NK : 1][4];
+#pragma unroll
+    for (int k = 0; k < NK; ++k)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) hw[k][j] = A.hc_w[k * 64 + c0 + j];
     for (unsigned p0 = first_pixel(ppb, VPP); p0 < npix; p0 += step * BN_U) {
         f32x4 x[BN_U], r[BN_U], g[BN_U][NG];
+        HcRow<NK> hc[BN_U];
 #pragma unroll
         for (int u = 0; u < BN_U; ++u) {
             unsigned p = p0 + u * step;
@@ -413,7 +453,8 @@ __global__ __launch_bounds__(256) void bn_bwd_flat32_kernel(BnBwdArgs A) {
             if (RES) r[u] = *reinterpret_cast<const f32x4 *>(resp + (size_t)p * A.C + c0);
 #pragma unroll
             for (int k = 0; k < NG; ++k)
-                g[u][k] = *reinterpret_cast<const f32x4 *>(reinterpret_cast<const float *>(A.gin[k].g) + (size_t)p * A.gin[k].cstride + A.gin[k].coff + c0);
+                if (k != HS) g[u][k] = *reinterpret_cast<const f32x4 *>(reinterpret_cast<const float *>(A.gin[k].g) + (size_t)p * A.gin[k].cstride + A.gin[k].coff + c0);
+            if (HS >= 0) hc[u].load(A.hc_coef + (size_t)p * 16);
         }
 #pragma unroll
         for (int u = 0; u < BN_U; ++u) {
@@ -424,9 +465,10 @@ __global__ __launch_bounds__(256) void bn_bwd_flat32_kernel(BnBwdArgs A) {
             for (int j = 0; j < 4; ++j) {
                 float v = fmaf(x[u][j], sc[j], sh[j]);
                 if (RES) v = outmask ? r[u][j] : v + r[u][j];
-                float gs = g[u][0][j];
+                const float hv = hc_value<NK>(hc[u], hw, j);
+                float gs = HS == 0 ? hv : g[u][0][j];
 #pragma unroll
-                for (int k = 1; k < NG; ++k) gs += g[u][k][j];
+                for (int k = 1; k < NG; ++k) gs += k == HS ? hv : g[u][k][j];
                 const float dz = (!valid || (relu && !(v > 0.f))) ? 0.f : gs;
                 const float xh = (x[u][j] - mu[j]) * is[j];
                 if (APPLY) { o[j] = k1[j] * (dz - k2[j] - xh * k3[j]); z[j] = dz; }
@@ -610,7 +652,7 @@ __global__ void bn_ktab_copy_kernel(const float *scale, const float *shift, cons
 // ------------------------------------------------------------------------------------------------------
 // Host: launch plan and C ABI
 // ------------------------------------------------------------------------------------------------------
-static int fill_bn_args(const cdnet_bn_bwd_args *a, BnBwdArgs &A, const char *who) {
+static int fill_bn_args(const cdnet_bn_bwd_args *a, BnBwdArgs &A, const char *who, bool hc_ok = false) {
     CDNET_REQUIRE(a && a->raw, "%s: null pointer", who);
     CDNET_REQUIRE(a->C % 8 == 0 && a->C >= 8 && a->C <= 2048 , "%s: C=%d unsupported", who, a->C);
     CDNET_REQUIRE(a->ngin >= 1 && a->ngin <= 3, "%s: ngin=%d", who, a->ngin);
@@ -620,12 +662,21 @@ static int fill_bn_args(const cdnet_bn_bwd_args *a, BnBwdArgs &A, const char *wh
         A.gin[k].g = a->gin[k].g; A.gin[k].Hg = a->gin[k].Hg; A.gin[k].Wg = a->gin[k].Wg;
         A.gin[k].oy = a->gin[k].oy; A.gin[k].ox = a->gin[k].ox; A.gin[k].pooled = a->gin[k].pooled;
         A.gin[k].coff = a->gin[k].coff; A.gin[k].cstride = a->gin[k].cstride ? a->gin[k].cstride : a->C;
-        if (k < a->ngin) CDNET_REQUIRE(a->gin[k].g, "%s: null gradient input %d", who, k);
+        if (k < a->ngin) CDNET_REQUIRE(a->gin[k].g || (a->hc_nk && k == a->hc_slot), "%s: null gradient input %d", who, k);
         // (a floor-mode pool of a one-pixel-high or -wide tensor has no output: the window kernels' clamped load would read element 0 of it)
         if (k < a->ngin) CDNET_REQUIRE(a->gin[k].Hg >= 1 && a->gin[k].Wg >= 1, "%s: empty gradient input %d (%d x %d)", who, k, a->gin[k].Hg, a->gin[k].Wg);
     }
     A.ngin = a->ngin; A.N = a->N; A.H = a->H; A.W = a->W; A.C = a->C;
     A.partial = nullptr; A.k1 = A.k2 = A.k3 = nullptr; A.draw = nullptr; A.dz_out = nullptr;
+    A.hc_coef = a->hc_coef; A.hc_w = a->hc_w; A.hc_slot = a->hc_slot; A.hc_nk = a->hc_nk;
+    if (a->hc_nk) {
+        // a head-coefficient source: cdnet_bn_backward alone takes one (and serves it on one plan, see there); the arguments are checked here
+        CDNET_REQUIRE(hc_ok, "%s: no head-coefficient source here (cdnet_bn_backward, flat fp32 residual form only)", who);
+        CDNET_REQUIRE((a->hc_nk == 3 || a->hc_nk == 9) && a->hc_k0 == HC_K0(a->hc_nk) && a->hc_coef && a->hc_w && a->C == 64 && a->hc_slot >= 0 &&
+                      a->hc_slot < a->ngin && !a->gin[a->hc_slot].g,
+                      "%s: head-coefficient source: hc_nk=%d hc_k0=%d hc_slot=%d C=%d (3 terms from column 10 or 9 from column 1, 64 channels, a slot "
+                      "below ngin whose g is NULL)", who, a->hc_nk, a->hc_k0, a->hc_slot, a->C);
+    }
     return CDNET_OK;
 }
 
@@ -697,6 +748,22 @@ static void launch(const BnPlan &P, const BnBwdArgs &A, hipStream_t st, bool dz_
     auto flat = [&](auto ng, auto res) {
         constexpr int NG = decltype(ng)::value;
         constexpr bool RES = decltype(res)::value;
+        if constexpr (RES && !APPLY) {
+            // head-coefficient source (cdnet_bn_backward has checked the plan): the instantiation of its slot and term count
+            if (A.hc_nk) {
+                auto hc = [&](auto hs) {
+                    constexpr int HS = decltype(hs)::value;
+                    if constexpr (HS < NG) {
+                        if (A.hc_nk == 3) bn_bwd_flat32_kernel<NG, true, false, HS, 3><<<P.nb, 256, 0, st>>>(A);
+                        else bn_bwd_flat32_kernel<NG, true, false, HS, 9><<<P.nb, 256, 0, st>>>(A);
+                    }
+                };
+                if (A.hc_slot == 0) hc(std::integral_constant<int, 0>{});
+                else if (A.hc_slot == 1) hc(std::integral_constant<int, 1>{});
+                else hc(std::integral_constant<int, 2>{});
+                return;
+            }
+        }
         if (P.f32) bn_bwd_flat32_kernel<NG, RES, APPLY><<<P.nb, 256, 0, st>>>(A);
         else bn_bwd_flat_kernel<NG, RES, APPLY><<<P.nb, 256, 0, st>>>(A);
     };
@@ -747,7 +814,7 @@ static BnBwdArgs bn_dz_as_source(const BnBwdArgs &A, const unsigned short *dz) {
 extern "C" int cdnet_bn_backward(const cdnet_bn_bwd_args *a, const float *gamma, float *dgamma, float *dbeta, float *workspace,
                                  size_t workspace_floats, uint16_t *draw, uint16_t *dz_out, void *stream) {
     BnBwdArgs A;
-    int rc = fill_bn_args(a, A, "cdnet_bn_backward");
+    int rc = fill_bn_args(a, A, "cdnet_bn_backward", true);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     const size_t npix = bn_npix(A);
@@ -758,6 +825,9 @@ extern "C" int cdnet_bn_backward(const cdnet_bn_bwd_args *a, const float *gamma,
     // tensor instead of the gradient sources and the mask again (bit-identical, 9 instead of 12 tensor passes in fp32).
     static const bool dz_reuse = !(getenv("CDNET_BN_DZ_REUSE") && atoi(getenv("CDNET_BN_DZ_REUSE")) == 0);
     const bool reuse = dz_reuse && P.path == BN_FLAT && A.mean && A.res && dz_out;
+    // a head-coefficient source: the sums pass of the flat fp32 residual form rebuilds it, the apply pass must read the stored dz
+    CDNET_REQUIRE(!A.hc_nk || (reuse && P.f32), "cdnet_bn_backward: a head-coefficient source needs fp32 tensors, same-size sources, BatchNorm, res and dz_out "
+                  "(the flat fp32 residual form, its second pass on the stored dz)");
     A.draw = draw;
     // The apply pass re-reads what the reduce pass just streamed (raw + gradients, up to 2 x 134 MB against 256 MB of
     // Infinity Cache): walking it back to front meets the most recently cached lines first instead of chasing the LRU tail.

@@ -376,11 +376,16 @@ __device__ __forceinline__ void head_wgrad_rows(float (&gw)[7][8], const float *
     }
 }
 
+// COEF: dF1 and dF2 are not stored (nor computed); the pixel's coefficient row [dpt | du[9] | dm[3] | 0 0 0] goes to coef f32 [px][16]
+// (dam_head_bwd_kernel's layout) instead, 16 bytes per lane, and their one reader each - the sums pass of mask_feature.bn2 /
+// direction_feature.bn2, bn_bwd_flat32_kernel's head-coefficient form - rebuilds its element with the xf_axpy16 chains below: the step
+// stores 67 MB in place of 536 MB.  Everything else is the same code in the same order.
+template <bool COEF>
 __global__ __launch_bounds__(512)
 void dam_head_bwd_fused_kernel(const float *__restrict__ f1, const float *__restrict__ f2, const float *__restrict__ f3,
                                const HeadW *__restrict__ hw, const float *__restrict__ dmask, const float *__restrict__ dpoint,
                                const float *__restrict__ ddir, int N, int plane, float *__restrict__ df1, float *__restrict__ df2,
-                               float *__restrict__ dz3, float *__restrict__ partial, float *__restrict__ sgbuf) {
+                               float *__restrict__ coef, float *__restrict__ dz3, float *__restrict__ partial, float *__restrict__ sgbuf) {
     __shared__ HeadW w;
     __shared__ __attribute__((aligned(16))) float s_cf[128 * 16];
     __shared__ __attribute__((aligned(16))) float s_f[3][128 * HF_ROW];     // (>= 4 x 13 x 64: the waves' weight-gradient blocks at the end)
@@ -465,10 +470,12 @@ void dam_head_bwd_fused_kernel(const float *__restrict__ f1, const float *__rest
         }
         stage(F1, 2);
         __builtin_amdgcn_sched_barrier(0);
-        xf_axpy16(dm[0], w.wm[0] + q * 16, v, false);
-        xf_axpy16(dm[1], w.wm[1] + q * 16, v, true);
-        xf_axpy16(dm[2], w.wm[2] + q * 16, v, true);
-        if (ok) { stf8(df1, e, v); stf8(df1, e + 8, v + 8); }
+        if (!COEF) {
+            xf_axpy16(dm[0], w.wm[0] + q * 16, v, false);
+            xf_axpy16(dm[1], w.wm[1] + q * 16, v, true);
+            xf_axpy16(dm[2], w.wm[2] + q * 16, v, true);
+            if (ok) { stf8(df1, e, v); stf8(df1, e + 8, v + 8); }
+        }
         __builtin_amdgcn_sched_barrier(0);
         const float dq2 = dg2 * sg2 * (1.f - sg2);
         float du[9], dd[9], dg1 = 0.f;
@@ -478,9 +485,11 @@ void dam_head_bwd_fused_kernel(const float *__restrict__ f1, const float *__rest
             dg1 = fmaf(dd[k], u[k], dg1);
             du[k] = dd[k] * g1;
         }
+        if (!COEF) {
 #pragma unroll
-        for (int k = 0; k < 9; ++k) xf_axpy16(du[k], w.wd[k] + q * 16, v, k != 0);
-        if (ok) { stf8(df2, e, v); stf8(df2, e + 8, v + 8); }
+            for (int k = 0; k < 9; ++k) xf_axpy16(du[k], w.wd[k] + q * 16, v, k != 0);
+            if (ok) { stf8(df2, e, v); stf8(df2, e + 8, v + 8); }
+        }
         __builtin_amdgcn_sched_barrier(0);
         const float dsg1 = dg1 * sg1 * (1.f - sg1);
         const float dpt = go_p + dsg1 * w.a1;
@@ -520,6 +529,7 @@ void dam_head_bwd_fused_kernel(const float *__restrict__ f1, const float *__rest
             else if (q == 2) cf = make_float4(du[7], du[8], dm[0], dm[1]);
             else cf = make_float4(dm[2], 0.f, 0.f, 0.f);
             *reinterpret_cast<float4 *>(s_cf + slot * 16 + q * 4) = cf;
+            if (COEF && ok) *reinterpret_cast<float4 *>(coef + ii * 16 + q * 4) = cf;
         }
         __syncthreads();
         // the chain's next pixel (iteration h + 2 of this group) was computed by the quad 256 threads up
@@ -753,12 +763,21 @@ extern "C" size_t cdnet_dam_head_backward_workspace_floats(int N, int H, int W) 
 
 extern "C" int cdnet_dam_head_backward_fused_blocks(void) { return HEAD_FUSED_BLOCKS; }
 /* private (scratch) memory per lane of dam_head_bwd_fused_kernel as built: it holds 256 VGPRs only just - a test keeps this at 0 */
-extern "C" int cdnet_dam_head_backward_fused_scratch_bytes(void) {
+template <bool COEF>
+static int head_fused_scratch_bytes() {
     hipFuncAttributes at;
-    if (hipFuncGetAttributes(&at, reinterpret_cast<const void *>(dam_head_bwd_fused_kernel)) != hipSuccess) return -1;
+    if (hipFuncGetAttributes(&at, reinterpret_cast<const void *>(dam_head_bwd_fused_kernel<COEF>)) != hipSuccess) return -1;
     return (int)at.localSizeBytes;
 }
+extern "C" int cdnet_dam_head_backward_fused_scratch_bytes(void) { return head_fused_scratch_bytes<false>(); }
+extern "C" int cdnet_dam_head_backward_coef_scratch_bytes(void) { return head_fused_scratch_bytes<true>(); }
 extern "C" size_t cdnet_dam_head_backward_fused_workspace_floats(void) { return (size_t)HEAD_FUSED_BLOCKS * (HEADW_FLOATS + 64 * 24); }
+
+// both forms of the one-pass head backward: coef == NULL stores df1 and df2, otherwise the coefficient rows
+static int head_backward_fused(const char *who, const cdnet_head_feat *f1, const cdnet_head_feat *f2, const cdnet_head_feat *f3,
+                               const float *head_weights, const float *dmask, const float *dpoint, const float *ddir, int N, int H, int W,
+                               float *df1, float *df2, float *coef, float *dz3, float *workspace, size_t workspace_floats,
+                               float *dhead_weights, void *stream);
 
 extern "C" int cdnet_dam_head_backward_fused(const cdnet_head_feat *f1, const cdnet_head_feat *f2, const cdnet_head_feat *f3,
                                              const float *head_weights, const float *dmask, const float *dpoint, const float *ddir,
@@ -766,23 +785,42 @@ extern "C" int cdnet_dam_head_backward_fused(const cdnet_head_feat *f1, const cd
                                              size_t workspace_floats, float *dhead_weights, void *stream) {
     CDNET_REQUIRE(f1 && f2 && f3 && head_weights && dmask && dpoint && ddir && df1 && df2 && dz3 && workspace && dhead_weights,
                   "cdnet_dam_head_backward_fused: null pointer");
+    return head_backward_fused("cdnet_dam_head_backward_fused", f1, f2, f3, head_weights, dmask, dpoint, ddir, N, H, W, df1, df2, nullptr, dz3,
+                               workspace, workspace_floats, dhead_weights, stream);
+}
+
+extern "C" int cdnet_dam_head_backward_coef(const cdnet_head_feat *f1, const cdnet_head_feat *f2, const cdnet_head_feat *f3,
+                                            const float *head_weights, const float *dmask, const float *dpoint, const float *ddir,
+                                            int N, int H, int W, float *coef, float *dz3, float *workspace, size_t workspace_floats,
+                                            float *dhead_weights, void *stream) {
+    CDNET_REQUIRE(f1 && f2 && f3 && head_weights && dmask && dpoint && ddir && coef && dz3 && workspace && dhead_weights,
+                  "cdnet_dam_head_backward_coef: null pointer");
+    return head_backward_fused("cdnet_dam_head_backward_coef", f1, f2, f3, head_weights, dmask, dpoint, ddir, N, H, W, nullptr, nullptr, coef, dz3,
+                               workspace, workspace_floats, dhead_weights, stream);
+}
+
+static int head_backward_fused(const char *who, const cdnet_head_feat *f1, const cdnet_head_feat *f2, const cdnet_head_feat *f3,
+                               const float *head_weights, const float *dmask, const float *dpoint, const float *ddir, int N, int H, int W,
+                               float *df1, float *df2, float *coef, float *dz3, float *workspace, size_t workspace_floats,
+                               float *dhead_weights, void *stream) {
     auto plain32 = [](const cdnet_head_feat &f) { return f.raw && f.f16 == 2 && !f.scale && !f.shift && !f.relu && !f.res; };
     CDNET_REQUIRE(plain32(*f1) && plain32(*f2) && plain32(*f3),
-                  "cdnet_dam_head_backward_fused: plain stored fp32 features only (f16 = 2, no scale / shift / relu / res)");
-    CDNET_REQUIRE(N >= 1 && H >= 1 && W >= 1, "cdnet_dam_head_backward_fused: N=%d H=%d W=%d", N, H, W);
-    CDNET_REQUIRE((size_t)N * H * W * 64 < ((size_t)1 << 32), "cdnet_dam_head_backward_fused: tensor too large for 32-bit element indexing");
+                  "%s: plain stored fp32 features only (f16 = 2, no scale / shift / relu / res)", who);
+    CDNET_REQUIRE(N >= 1 && H >= 1 && W >= 1, "%s: N=%d H=%d W=%d", who, N, H, W);
+    CDNET_REQUIRE((size_t)N * H * W * 64 < ((size_t)1 << 32), "%s: tensor too large for 32-bit element indexing", who);
     static_assert(HEAD_FUSED_BLOCKS == 1024, "the chains of the two-kernel path: 1024 workgroups");
     const int nb = HEAD_FUSED_BLOCKS;
     const size_t need = (size_t)nb * (HEADW_FLOATS + 64 * 24);
-    if (workspace_floats < need) { set_error("cdnet_dam_head_backward_fused: workspace %zu < %zu floats", workspace_floats, need); return CDNET_E_WORKSPACE; }
+    if (workspace_floats < need) { set_error("%s: workspace %zu < %zu floats", who, workspace_floats, need); return CDNET_E_WORKSPACE; }
     hipStream_t st = (hipStream_t)stream;
     float *partial = workspace, *sgbuf = workspace + (size_t)nb * HEADW_FLOATS;
     auto fp = [](const cdnet_head_feat &f) { return reinterpret_cast<const float *>(f.raw); };
-    dam_head_bwd_fused_kernel<<<nb, 512, 0, st>>>(fp(*f1), fp(*f2), fp(*f3), reinterpret_cast<const HeadW *>(head_weights), dmask, dpoint, ddir,
-                                                  N, H * W, df1, df2, dz3, partial, sgbuf);
+    const HeadW *hw = reinterpret_cast<const HeadW *>(head_weights);
+    if (coef) dam_head_bwd_fused_kernel<true><<<nb, 512, 0, st>>>(fp(*f1), fp(*f2), fp(*f3), hw, dmask, dpoint, ddir, N, H * W, df1, df2, coef, dz3, partial, sgbuf);
+    else dam_head_bwd_fused_kernel<false><<<nb, 512, 0, st>>>(fp(*f1), fp(*f2), fp(*f3), hw, dmask, dpoint, ddir, N, H * W, df1, df2, coef, dz3, partial, sgbuf);
     head_scalar_reduce_kernel<<<nb, 64, 0, st>>>(sgbuf, partial);
     reduce_partials_kernel<<<cdiv(HEADW_FLOATS, 4), 256, 0, st>>>(workspace, nb, HEADW_FLOATS, dhead_weights);
-    return check_launch("cdnet_dam_head_backward_fused");
+    return check_launch(who);
 }
 
 extern "C" size_t cdnet_final_conv1x1_backward_workspace_floats(void) { return (size_t)1025 * (FC_KMOST * 64 + FC_KMOST); }

@@ -34,6 +34,9 @@ _WGRAD_WGS_F32 = 160                      # (128 / 160 / 256: 989 / 994 / 987 ti
 _RU_1X1_SIDE = True      # residual units' 1x1 backward-data beside the chain (tests flip it: same gradients either way)
 WGRAD_STREAM = True       # weight gradients on a second stream beside the input-gradient chain
 HEAD_BWD_FUSE = True      # fp32 mode, rev1 head: head backward + its weight gradients in one launch, dF3 behind the unit's ReLU (same bits)
+# ... and dF1 / dF2 never stored: the launch leaves the pixels' 16 coefficients, the sums passes of mask_feature.bn2 / direction_feature.bn2
+# rebuild their element (cdnet_dam_head_backward_coef, cdnet_bn_bwd_args.hc_*; same bits, 0.9 GB less traffic).  CDNET_HEAD_COEF_SRC=0: off
+HEAD_COEF_SRC = os.environ.get('CDNET_HEAD_COEF_SRC', '1') != '0'
 _WGRAD_DEFER = 0x100                       # CDNET_WGRAD_DEFER_REDUCE (include/cdnet_hip.h)
 _WGRAD_DEEP_HW = 16384
 
@@ -57,13 +60,15 @@ class _on_stream:
 
 class _G:
     """a gradient contribution for a stored tensor"""
-    __slots__ = ('t', 'Hg', 'Wg', 'oy', 'ox', 'pooled', 'coff', 'cstride', 'event', 'masked')
+    __slots__ = ('t', 'Hg', 'Wg', 'oy', 'ox', 'pooled', 'coff', 'cstride', 'event', 'masked', 'hc')
 
     def __init__(self, t, Hg, Wg, oy=0, ox=0, pooled=0, coff=0, cstride=0):
         self.t, self.Hg, self.Wg, self.oy, self.ox, self.pooled, self.coff, self.cstride = t, Hg, Wg, oy, ox, pooled, coff, cstride
         self.event = None                    # produced on another stream: the consumer's stream waits for this event first
         self.masked = False                  # t is already dz of a residual unit's bn2: the consumer's gradient behind the unit's ReLU
                                              # (cdnet_dam_head_backward_fused, _head_fusable)
+        self.hc = None                       # t is None: a head-coefficient source (coefficient rows, head weight block, first weight
+                                             # float, first column, terms) that the sums pass of a residual unit's bn2 rebuilds (_bn_args)
 
 
 def _choose_ci_tiles(C_src, Cout):
@@ -132,6 +137,7 @@ class Trainer:
         self._packb_stream = True              # backward-data re-packs beside the next forward
         self._side_active = False
         self.head_fused = False                 # the last backward took cdnet_dam_head_backward_fused (_head_fusable)
+        self.head_coef = False                  # ... in the form that stores coefficients instead of dF1 / dF2 (HEAD_COEF_SRC)
         # split-K sums of the weight gradients: deferred and batched (one cdnet_wgrad_reduce_batch launch per ~CDNET_WGRAD_REDUCE_MB of
         # slabs instead of one reduce behind every weight-gradient launch; every call keeps its own slab buffer - 1.4 GB for the UNet)
         # Memory: with the default every weight-gradient call keeps its own split-K slab buffer for the trainer's lifetime (`buf(('wslab', ...))`,
@@ -309,11 +315,30 @@ class Trainer:
         m = self.model
         f1, f2, f3 = m._last_feats
         N, H, W, _ = f1.x.shape
-        df = [self.buf('dF%d' % k, (N, H, W, 64), runtime.act_dtype()) for k in range(3)]
         hf = [runtime.head_feat(f) for f in (f1, f2, f3)]
         dhead = self.flat.G[:self.flat.n_head]
         owner = self._head_fusable(f1, f2, f3)
         self.head_fused = owner is not None
+        # (the rebuilt source needs the second BatchNorm pass on the stored dz: with the library's A/B switch CDNET_BN_DZ_REUSE=0 the tensors stay)
+        self.head_coef = owner is not None and HEAD_COEF_SRC and os.environ.get('CDNET_BN_DZ_REUSE', '1').strip() not in ('0', '') \
+            and self._head_coef_ok(f1) and self._head_coef_ok(f2)
+        if self.head_coef:
+            # the same launch without dF1 and dF2: 16 coefficients a pixel instead of 2 x 64 gradient values; each one's only reader, the
+            # sums pass of its unit's bn2, rebuilds its element from them and the head's weight rows (wd at float 64, wm at 640 of the block)
+            coef = self.buf('head_coef', (N, H, W, 16), torch.float32)
+            dz3 = self.buf('dF2', (N, H, W, 64), torch.float32)
+            hw = m.head_weight_block()
+            ws = self._ws('head', _lib.load().cdnet_dam_head_backward_fused_workspace_floats())
+            _lib.call('cdnet_dam_head_backward_coef', C.byref(hf[0]), C.byref(hf[1]), C.byref(hf[2]), _lib.ptr(hw), _lib.ptr(dmask),
+                      _lib.ptr(dpoint), _lib.ptr(ddir), N, H, W, _lib.ptr(coef), _lib.ptr(dz3), _lib.ptr(ws), ws.numel(), _lib.ptr(dhead),
+                      _lib.stream_ptr())
+            heads = [(f1.x, _G(None, H, W)), (f2.x, _G(None, H, W)), (f3.x, _G(dz3, H, W))]
+            heads[0][1].hc = (coef, hw, 640, 10, 3)
+            heads[1][1].hc = (coef, hw, 64, 1, 9)
+            heads[2][1].masked = True
+            self._run_tape(heads, None)
+            return
+        df = [self.buf('dF%d' % k, (N, H, W, 64), runtime.act_dtype()) for k in range(3)]
         if owner is not None:
             # one launch instead of two (every feature read once, no coefficient tensor), bit-identical to them; dF3 leaves as dz3, behind
             # the unit's ReLU - the tape walk runs point_feature.bn2's backward on it without the mask (_bn_backward_masked)
@@ -330,6 +355,25 @@ class Trainer:
                   _lib.ptr(dmask), _lib.ptr(dpoint), _lib.ptr(ddir), N, H, W, _lib.ptr(df[0]), _lib.ptr(df[1]),
                   _lib.ptr(df[2]), _lib.ptr(ws), ws.numel(), _lib.ptr(dhead), _lib.stream_ptr())
         self._run_tape([((f.grad_to or (f.x,))[0], _G(d, H, W)) for f, d in zip((f1, f2, f3), df)], None)
+
+    def _head_coef_ok(self, f):
+        """the head's gradient of feature f may stay a head-coefficient source: f.x is the stored output of a residual unit with the fused
+        epilogue, so the consumers' gradients go unsummed to the unit's bn2 (the flat fp32 residual form, mask from f.x, dz stored) - at
+        most two more of them, same size, and no fuse node that would sum them first"""
+        readers = 0
+        for Rt in self.tape:
+            if isinstance(Rt, runtime.FuseRecord):
+                if any(t.x is f.x for t in Rt.terms):
+                    return False
+                continue
+            for sx in Rt.srcs:
+                if sx.res is f.x or (sx.x is f.x and (sx.pool or tuple(sx.off) != (0, 0))):
+                    return False
+                readers += sx.x is f.x
+        P = next((Rt for Rt in self.tape if not isinstance(Rt, runtime.FuseRecord) and Rt.out is f.x), None)
+        owner = None if P is None or P.layer.kind != 'conv1' else P.fused_res_of
+        return readers <= 2 and owner is not None and owner.layer.bn is not None and owner.relu == 2 and owner.res is f.x \
+            and owner.out.dtype == torch.float32 and tuple(owner.out.shape) == tuple(f.x.shape)
 
     def _head_fusable(self, f1, f2, f3):
         """cdnet_dam_head_backward_fused's one case: fp32 mode, the rev1 head over three plain stored fp32 features, the third one the
@@ -654,7 +698,10 @@ class Trainer:
         a.ngin = len(gl)
         assert 1 <= len(gl) <= 3, (L.name, len(gl))
         for k, g in enumerate(gl):
-            a.gin[k].g = g.t.data_ptr()
+            if g.hc is not None:
+                coef, hw, w0, k0, nk = g.hc
+                a.hc_coef, a.hc_w, a.hc_slot, a.hc_k0, a.hc_nk = coef.data_ptr(), hw.data_ptr() + 4 * w0, k, k0, nk
+            a.gin[k].g = None if g.t is None else g.t.data_ptr()
             a.gin[k].Hg, a.gin[k].Wg, a.gin[k].oy, a.gin[k].ox = g.Hg, g.Wg, g.oy, g.ox
             a.gin[k].pooled, a.gin[k].coff, a.gin[k].cstride = int(g.pooled), g.coff, g.cstride or out.shape[3]
         a.f16 = {torch.bfloat16: 0, torch.float16: 1, torch.float32: 2}[out.dtype]

@@ -674,6 +674,16 @@ typedef struct cdnet_bn_bwd_args {
     int ngin;
     int f16, relu;                 /* relu: 0 none, 1 relu(affine [+ res]), 2 mask = res > 0 (fused residual epilogue of cdnet_conv_forward) */
     int N, H, W, C;
+    /* Head-coefficient source (hc_nk = 0: none).  Gradient source number hc_slot is then not a stored tensor (gin[hc_slot].g = NULL, its
+     * Hg x Wg = H x W, nothing else set) but the DAM head's feature gradient rebuilt per element from the per-pixel coefficient rows of
+     * cdnet_dam_head_backward_coef, hc_coef f32 [N * H * W][16], and hc_nk rows of 64 weights inside the head weight block, hc_w f32
+     * [hc_nk][64]:   v = fma(coef[p][hc_k0], w[0][c], +0);  v = fma(coef[p][hc_k0 + k], w[k][c], v), k = 1 .. hc_nk - 1
+     * - the operations, in the order, of the head kernels' own dF, so the value has the bits of the tensor it replaces, and it is added
+     * at position hc_slot of the sum over the sources.  hc_nk is 3 (mask head: hc_k0 = 10) or 9 (direction head: hc_k0 = 1), C = 64.
+     * Served by cdnet_bn_backward alone, for fp32 tensors with same-size sources, res and dz_out (the flat fp32 residual form); every
+     * other entry or plan refuses the arguments (CDNET_E_ARG) before any launch. */
+    const float *hc_coef, *hc_w;
+    int hc_slot, hc_k0, hc_nk, hc_pad_;
 } cdnet_bn_bwd_args;
 
 /* BatchNorm(train) + residual + ReLU backward with the consumers' max-pool / pad routing and the summation of up to
@@ -744,6 +754,16 @@ int cdnet_dam_head_backward_fused(const cdnet_head_feat *f1, const cdnet_head_fe
                                   const float *head_weights, const float *dmask, const float *dpoint, const float *ddir, int N, int H,
                                   int W, float *df1, float *df2, float *dz3, float *workspace, size_t workspace_floats,
                                   float *dhead_weights, void *stream);
+/* The same launch without df1 and df2: they are rank 3 and rank 9 per pixel, dF1[p][c] = sum_k dm_k[p] wm[k][c] and dF2[p][c] = sum_k
+ * du_k[p] wd[k][c], so what leaves is the pixel's coefficient row coef f32 [N * H * W][16] = [dpt | du[0..8] | dm[0..2] | 0 0 0] - the
+ * layout and the bits of the rows cdnet_dam_head_backward keeps in its workspace -, 64 bytes a pixel in place of 512.  The one reader of
+ * each gradient, the sums pass of its residual unit's bn2, rebuilds the element (cdnet_bn_bwd_args.hc_*).  dz3, dhead_weights,
+ * workspace, the refusals and the order of every sum are cdnet_dam_head_backward_fused's. */
+int cdnet_dam_head_backward_coef_scratch_bytes(void);    /* as cdnet_dam_head_backward_fused_scratch_bytes, of this form's kernel */
+int cdnet_dam_head_backward_coef(const cdnet_head_feat *f1, const cdnet_head_feat *f2, const cdnet_head_feat *f3,
+                                 const float *head_weights, const float *dmask, const float *dpoint, const float *ddir, int N, int H,
+                                 int W, float *coef, float *dz3, float *workspace, size_t workspace_floats, float *dhead_weights,
+                                 void *stream);
 
 /* The five-term CDNet loss (train_util_dam.py:167-276; loss.py:131-260) and its gradient w.r.t. the logits.
  * label u8 {0,1,2}, dirlab u8 0..8, point target f16, weight map u8 (divided by 20 on the fly, :102).
