@@ -1,6 +1,7 @@
 // Wave-specialised, persistent 3x3 convolution of the 16-bit path for every launch that carries no BatchNorm statistics: the eval-mode
 // forward (inference tiles, sliding windows), every backward-data pass of training, the space-to-depth backward of the transposed
-// convolutions.  Round 4: the recipe of conv_ws32_kernel (conv32ws.hip) for bf16 operands -
+// convolutions.  The movers' scaffolding (run of tiles, tile cursor, halo validity masks, buffer descriptors, barriers, weight DMA) is
+// persist.h.  The recipe, for bf16 operands -
 //
 //   * OPERAND ROLES SWAPPED against conv_fwd_kernel / conv_ws_kernel: the packed weights are the MFMA's A operand (M = 32 output channels),
 //     the halo pixels its B operand (N = 32 pixels).  An accumulator block then holds, per lane, ONE pixel x 16 output channels, and with
@@ -12,7 +13,7 @@
 //     the next tile (the eval-mode BatchNorm scale is folded into the packed weights by the host, runtime.ConvLayer.eval_pack);
 //   * any number of 16-channel chunks from one up (the stem 16 -> 64, the decoder's 80 -> 16 and 160 -> 32, the 512-channel loops):
 //     one barrier per TWO chunks of the workgroup's run of chunks, wherever tile boundaries fall; weights resident in LDS when the tile's
-//     chunks fit (<= 82 KB), else streamed through a four-slot ring by LDS-DMA two chunks ahead (conv_ws_kernel's scheme);
+//     chunks fit (<= 82 KB), else streamed through a four-slot ring by LDS-DMA two chunks ahead (dma_weight_chunk, persist.h);
 //   * a second source may carry ONE tap per chunk instead of nine (cdnet_conv_args.taps1 = 1): the 1x1 branch of a residual unit then is
 //     four more K steps of its second 3x3 convolution - relu(bn2(conv2(h)) + conv_1x1(x)) in one launch, eval mode
 //     (model_unet_rev1.py:161-170), no stored conv2 output, no separate 1x1 pass;
@@ -24,8 +25,8 @@
 //     chunks, odd counts) store straight from the accumulators, a pixel block's lines in consecutive gaps;
 //   * the streamed-weight launches (128+ input channels: matrix-bound) run v_mfma_f32_16x16x32_bf16 (K32): the chip holds a higher clock
 //     on it (tools/micro/mfma_shapes.hip);
-//   * waves 4..7 (movers) are conv_ws_kernel's: four halo chunks in flight in registers, requests through buffer descriptors (zero fill by
-//     the range check), generic source transform, four-slot halo ring.
+//   * waves 4..7 (movers): four halo chunks in flight in registers, requests through buffer descriptors (zero fill by the range check,
+//     persist.h), generic source transform, four-slot halo ring.
 // Accumulation order per output (chunk, tap, k) is conv_fwd_kernel's in the 32x32x16 forms: without bias the outputs are bit-identical to
 // it (tests/test_gpu_conv16ws.py); with bias the sum starts from the bias instead of ending with it (one rounding moved); K32 adds 32
 // products per MFMA: one bf16 ulp.
@@ -35,6 +36,7 @@
 #include "common.h"
 #include "conv_args.h"
 #include "launch.h"
+#include "persist.h"
 #include "xform.h"
 #include "stage16.h"
 #include <stdlib.h>
@@ -46,7 +48,7 @@ using namespace cdnet;
 // debug build only (CDNET_HIPCC_FLAGS=-DCDNET_WS_STAMPS, tools/ws16_stamps.py): wall-clock stamps (100 MHz) of consumer wave 0 and mover wave 4
 // of ONE workgroup over a window of barrier intervals in the middle of its run, parked in LDS (6 KB behind the kernel's own) and dumped at the
 // end; the production build carries none of it
-__device__ unsigned long long g_ws16_stamps[3 * 1024];      // consumer stamps from 0, mover stamps from 1024 (255 each + a zero; the third region served the storer waves of a removed experiment)
+__device__ unsigned long long g_ws16_stamps[2 * 1024];      // consumer stamps from 0, mover stamps from 1024 (255 each + a zero)
 extern "C" __attribute__((visibility("default"))) int cdnet_debug_ws16_stamps(unsigned long long *dst) {
     return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_ws16_stamps), sizeof(g_ws16_stamps)) == hipSuccess ? 0 : 1;
 }
@@ -86,8 +88,8 @@ __device__ __forceinline__ int sigma32(int m) { return (m & ~12) | ((m & 4) << 1
 // STREAM: the weight chunks stream through a four-slot ring (even chunk count); else all of a tile's chunks are resident
 // MIX: the second source's chunks carry one tap (the centre) instead of nine
 // NCS: chunks per tile known to the compiler - 1: one, 2: two or three, 0: four or more (how the finished tile's epilogue is spread)
-// NS: halo ring slots (4).  PFD: halo chunks in flight per mover thread (4; 8 and 12 were measured: no gain - the launch is not latency-bound;
-// so was a DMA form of the movers, buffer_load ... lds into a seven-slot ring: profiles/HISTORY.md)
+// (A four-slot halo ring and four halo chunks in flight per mover thread throughout: 8 and 12 in flight were measured - no gain, the launch
+// is not latency-bound; so was a DMA form of the movers, buffer_load ... lds into a seven-slot ring: profiles/HISTORY.md)
 // OUT: the finished tile leaves through an LDS out image and the MOVERS store it (register movers, an even chunk count >= 4): a store issued by
 // a consumer wave between MFMAs waits for the memory pipeline behind the movers' requests, and the matrix pipe waits with it
 // K32: the consumers of the out-image form run v_mfma_f32_16x16x32_bf16 - K = 32 = two (tap, 8-channel) pairs of a pair of chunks, 9 K steps per
@@ -106,20 +108,20 @@ __device__ __forceinline__ int sigma32(int m) { return (m & ~12) | ((m & 4) << 1
 // 0.54 GB input (profiles/r05/dominant_conv_bf16_64tiles_pmc.json).  Three pair register sets: the even pairs use group 0, the odd pairs
 // alternate between groups 1 and 2 (a quad is requested when its first pair's group has just been written to the ring and the odd group of the
 // quad before last is free); the ring slot of a pair is its parity, whatever group it arrived in.
-template <int BN, int XF, bool STREAM, bool MIX, int NCS, int NS, int PFD, bool OUT, bool K32 = false, bool PAIR = false, bool QUAD = false>
+template <int BN, int XF, bool STREAM, bool MIX, int NCS, bool OUT, bool K32 = false, bool PAIR = false, bool QUAD = false>
 __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
     using L = W16Lds<BN>;
     constexpr int TH = 16, TW = 16, CK = 16, PSTR = L::PSTR, HW_ = TW + 2, NPIX = L::NPIX;
     constexpr int NCI = BN / 32, NPI = 2;                         // consumer wave: NCI blocks of 32 output channels x two blocks of 32 pixels
     constexpr int NMV = 256;                                      // mover threads
     constexpr int VPP = CK / 8, NA = (NPIX * VPP + NMV - 1) / NMV;
-    constexpr int PF = QUAD ? 6 : PFD;
+    constexpr int NS = 4;                                         // halo ring slots
+    constexpr int PF = QUAD ? 6 : 4;                              // halo chunks in flight per mover thread (register sets)
     constexpr int A_BYTES = L::A_IMG;                             // halo ring slot stride
-    constexpr int IPG = QUAD ? 4 : PF / 2;                        // barrier intervals per iteration of the movers' loop
+    constexpr int IPG = QUAD ? 4 : 2;                             // barrier intervals per iteration of the movers' loop
     static_assert(!(STREAM && MIX), "one-tap chunks only with resident weights");
     static_assert(!OUT || NCS == 0, "LDS out image: tiles of an even number (>= 4) of chunks");
     static_assert(!K32 || OUT, "the 16x16x32 consumers serve the out-image form");
-    static_assert(NS == 4 && (QUAD || PF % 4 == 0), "a four-slot halo ring, register sets = slots mod 4");
     static_assert(!QUAD || (PAIR && !STREAM && OUT), "quad requests: the out-image form with resident weights and pair requests");
     static_assert(!PAIR || NCS == 0, "pair requests: tiles of an even number (>= 4) of chunks");
     const int NCH = A.nchunk;
@@ -140,23 +142,12 @@ __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
     const int cout_tile = blockIdx.y;
     const int cout0 = cout_tile * BN;
 
-    // this workgroup's contiguous run of tiles; XCD k (workgroups k, k+8, ...) serves the k-th eighth of the tiles (conv_ws_kernel)
+    // this workgroup's contiguous run of tiles (persist.h)
     const int tiles_x = A.W / TW, tiles_y = A.H / TH;
     const int tiles_img = tiles_x * tiles_y;
     const int T = A.N * tiles_img;
     int t_lo, t_hi;
-    {
-        const int G = (int)gridDim.x, b = (int)blockIdx.x;
-        if ((G & 7) == 0) {
-            const int xcd = b & 7, idx = b >> 3, nw = G >> 3;
-            const long long x0 = (long long)T * xcd / 8, x1 = (long long)T * (xcd + 1) / 8;
-            t_lo = (int)(x0 + (x1 - x0) * idx / nw);
-            t_hi = (int)(x0 + (x1 - x0) * (idx + 1) / nw);
-        } else {
-            t_lo = (int)((long long)T * b / G);
-            t_hi = (int)((long long)T * (b + 1) / G);
-        }
-    }
+    tile_run(T, (int)gridDim.x, (int)blockIdx.x, t_lo, t_hi);
     const int ntl = t_hi - t_lo;
     const int S = ntl * NCH;                                      // chunks of this workgroup's run
     if (S == 0) return;
@@ -169,7 +160,7 @@ __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
 #endif
 
     if (wave >= 4) {
-        // ================================ movers (conv_ws_kernel's, without the out path) ================================
+        // ================================ movers ================================
         const int ptid = tid - 256, pw = wave - 4;
         constexpr int VPQ = PAIR ? 2 * VPP : VPP;                 // 16-byte vectors per halo pixel of a request group (PAIR: a pair of chunks)
         constexpr int NG = PAIR ? 2 : 1;                          // register-set groups that share one lane -> (pixel, segment) map
@@ -190,24 +181,12 @@ __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
             }
         const unsigned src_bytes0 = (unsigned)A.N * A.src[0].Hs * (A.src[0].row_stride ? A.src[0].row_stride : A.src[0].Ws * A.src[0].C) * 2u;
         const unsigned src_bytes1 = A.nsrc > 1 ? (unsigned)A.N * A.src[1].Hs * (A.src[1].row_stride ? A.src[1].row_stride : A.src[1].Ws * A.src[1].C) * 2u : 0u;
-        const __amdgpu_buffer_rsrc_t rsx0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short *>(A.src[0].x), 0, (int)src_bytes0, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsx1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short *>(A.nsrc > 1 ? A.src[1].x : A.src[0].x), 0, (int)src_bytes1, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsr0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short *>(A.src[0].res ? A.src[0].res : A.src[0].x), 0, (int)src_bytes0, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsr1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short *>(A.nsrc > 1 && A.src[1].res ? A.src[1].res : A.src[0].x), 0, (int)src_bytes1, 0x00020000);
-        auto bload = [](__amdgpu_buffer_rsrc_t r, unsigned voff) -> u32x4 {
-            return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, 0, 0));
-        };
-        auto bad_mask = [](int lo, int hi) -> unsigned {
-            lo = lo < 0 ? 0 : (lo > 31 ? 31 : lo);
-            hi = hi < lo ? lo : (hi > 31 ? 31 : hi);
-            return ~(((1u << hi) - 1u) & ~((1u << lo) - 1u));
-        };
+        const __amdgpu_buffer_rsrc_t rsx0 = buf_rsrc(A.src[0].x, src_bytes0);
+        const __amdgpu_buffer_rsrc_t rsx1 = buf_rsrc(A.nsrc > 1 ? A.src[1].x : A.src[0].x, src_bytes1);
+        const __amdgpu_buffer_rsrc_t rsr0 = buf_rsrc(A.src[0].res ? A.src[0].res : A.src[0].x, src_bytes0);
+        const __amdgpu_buffer_rsrc_t rsr1 = buf_rsrc(A.nsrc > 1 && A.src[1].res ? A.src[1].res : A.src[0].x, src_bytes1);
         int ik = 0, ic = 0, in_, iy0, ix0;
-        {
-            in_ = t_lo / tiles_img;
-            const int r = t_lo - in_ * tiles_img, ty = r / tiles_x;
-            iy0 = ty * TH; ix0 = (r - ty * tiles_x) * TW;
-        }
+        seek_tile(t_lo, tiles_img, tiles_x, in_, iy0, ix0);
         int ck = 0;
         unsigned ge[NG][NA];
         auto chunk_src = [&](int k, int &si, int &cc0) {
@@ -222,10 +201,11 @@ __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
             const ConvSrc &s = A.src[si];
             const int ikb = PAIR ? (ik & ~1) : ik;
             if (ikb == 0 || ikb == n0) {
+                // halo geometry of the tile in this source (persist.h, halo_bad_mask)
                 const int rs = s.row_stride ? s.row_stride : s.Ws * s.C;
                 const int ylo = s.off_y > 0 ? s.off_y : 0, yhi = A.H < s.off_y + s.Hs ? A.H : s.off_y + s.Hs;
                 const int xlo = s.off_x > 0 ? s.off_x : 0, xhi = A.W < s.off_x + s.Ws ? A.W : s.off_x + s.Ws;
-                const unsigned rowbad = bad_mask(ylo - (iy0 - 1), yhi - (iy0 - 1)), colbad = bad_mask(xlo - (ix0 - 1), xhi - (ix0 - 1));
+                const unsigned rowbad = halo_bad_mask(ylo - (iy0 - 1), yhi - (iy0 - 1)), colbad = halo_bad_mask(xlo - (ix0 - 1), xhi - (ix0 - 1));
                 const unsigned img_b = (unsigned)((in_ * s.Hs + (iy0 - 1 - s.off_y)) * rs + (ix0 - 1 - s.off_x) * s.C) * 2u;
                 const unsigned rs_b = (unsigned)rs * 2u, c_b = (unsigned)s.C * 2u;
 #pragma unroll
@@ -240,16 +220,12 @@ __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
 #pragma unroll
             for (int i = 0; i < NA; ++i) {
                 const unsigned voff = ge[G][i] + cc0_b;
-                if (XF != 0) eo[R][i] = voff;
-                if (!(A.debug & 2)) pa[R][i] = bload(rsx, voff);     // (2: ablation - no halo requests)
+                if (XF != 0) eo[XF != 0 ? R : 0][i] = voff;
+                if (!(A.debug & 2)) pa[R][i] = buf_load128<u32x4>(rsx, voff);     // (2: ablation - no halo requests)
             }
             if (ic + 1 < S) {
                 ++ic;
-                if (++ik == NCH) {
-                    ik = 0;
-                    ix0 += TW;
-                    if (ix0 >= A.W) { ix0 = 0; iy0 += TH; if (iy0 >= A.H) { iy0 = 0; ++in_; } }
-                }
+                if (++ik == NCH) { ik = 0; next_tile(in_, iy0, ix0, A.H, A.W); }
             }
         };
         // run chunk c_ (register set R = c_ % 4) -> ring slot c_ % 4 (QUAD: the register set is any of six, the slot pair is given: SB = 0 / 2)
@@ -282,11 +258,11 @@ __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
                     raw.u = __builtin_bit_cast(uint4, pa[R][i]);
                     const bool relu = s.relu != 0, f16 = s.f16 != 0;
                     if (s.res) {
-                        rr.u = __builtin_bit_cast(uint4, bload(si ? rsr1 : rsr0, eo[R][i]));
+                        rr.u = __builtin_bit_cast(uint4, buf_load128<u32x4>(si ? rsr1 : rsr0, eo[XF != 0 ? R : 0][i]));
                         val = __builtin_bit_cast(u32x4, xform8(raw, &rr, t, relu, f16).u);
                     } else if (!t.on && !relu && !f16) val = pa[R][i];
                     else val = __builtin_bit_cast(u32x4, xform8(raw, nullptr, t, relu, f16).u);
-                    const unsigned keep = (int)eo[R][i] < 0 ? 0u : 0xffffffffu;      // outside the image / source: zeros (after the transform)
+                    const unsigned keep = (int)eo[XF != 0 ? R : 0][i] < 0 ? 0u : 0xffffffffu;      // outside the image / source: zeros (after the transform)
                     val &= keep;
                 }
                 if (ptid + (G * NA + i) * NMV < NPIX * VPQ)
@@ -297,34 +273,12 @@ __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
         // STREAM: weight chunk wk of the tile -> weight slot (run chunk & 3) by LDS-DMA (the packed chunk is the LDS image)
         int wk = 0, wq = 0;
         auto dma_w = [&]() {
-            constexpr int NVEC = L::WCH9 / 16;
-            static_assert(NVEC % 64 == 0, "whole wave-instructions");
-            const unsigned short *wsrc = A.w + ((size_t)cout_tile * NCH + wk) * (L::WCH9 / 2);
-            unsigned char *wdst = lds_w + (wq & 3) * L::WCH9;
-#pragma unroll
-            for (int i = 0; i < (NVEC / 64 + 3) / 4; ++i) {
-                const int v0 = (i * 4 + pw) * 64;
-                if (v0 < NVEC)
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(wsrc + (size_t)(v0 + lane) * 8),
-                                                     (__attribute__((address_space(3))) void *)(wdst + v0 * 16), 16, 0, 0);
-            }
+            dma_weight_chunk<L::WCH9>(A.w + ((size_t)cout_tile * NCH + wk) * (L::WCH9 / 2), lds_w + (wq & 3) * L::WCH9, pw, lane);
             if (++wk == NCH) wk = 0;
             ++wq;
         };
-        auto wait_vm = [](auto n_c) {
-            constexpr int N = decltype(n_c)::value;
-            __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));
-        };
-        using NHL = std::integral_constant<int, 2 * NA>;          // halo requests of one interval (two chunks)
-        // the movers' barrier of the streaming loop by hand (conv_ws_kernel): this wave's LDS writes done, its weight DMA landed (everything
-        // older than the N youngest vector-memory operations), then the barrier; the halo requests issued after the DMA stay in flight
-        auto stream_sync = [](auto n_c) {
-            constexpr int N = decltype(n_c)::value;
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (0 << 8) | ((N >> 4) << 14));
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-        };
+        constexpr int NHL = 2 * NA;                               // halo requests of one interval (two chunks): they stay in flight over the
+                                                                  // streaming loop's barrier (barrier_keep_vm, persist.h)
         // OUT: the half (pixel block pi of the four consumer waves) of a finished tile the consumers parked in the PREVIOUS interval leaves
         // here: wave pw stores the block of consumer wave pw - 8 lanes per pixel, one 128-byte line each (BN = 64)
         const int NIT = NCH >> 1;                                // intervals per tile (OUT: even chunk counts)
@@ -422,22 +376,10 @@ __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
                     st_it = 0; ++st_jt;
                     h_n[1] = h_n[0]; h_y0[1] = h_y0[0]; h_x0[1] = h_x0[0];
                     h_n[0] = c_n; h_y0[0] = c_y0; h_x0[0] = c_x0;
-                    c_x0 += TW;
-                    if (c_x0 >= A.W) { c_x0 = 0; c_y0 += TH; if (c_y0 >= A.H) { c_y0 = 0; ++c_n; } }
+                    next_tile(c_n, c_y0, c_x0, A.H, A.W);
                 }
             }
             return stored;
-        };
-        // lgkmcnt(0) + barrier, no wait for vector memory (the stores of the out image stay in flight)
-        auto lds_sync = []() {
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_s_waitcnt((63 & 15) | (7 << 4) | (0 << 8) | ((63 >> 4) << 14));
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-        };
-        // register set of run chunk c = c mod PF (compile-time inside the unrolled loop body), ring slot = c mod 4
-        auto for_sets = [&](auto f) {                            // f(integral_constant<int, k>) for k = 0 .. PF - 1
-            [&]<int... K>(std::integer_sequence<int, K...>) { (f(std::integral_constant<int, K>{}), ...); }(std::make_integer_sequence<int, PF>{});
         };
         if constexpr (QUAD) {
             // ================================ movers, quad requests ================================
@@ -459,19 +401,19 @@ __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
             // interval i: the consumers work on pair i, pair i + 1 is staged here; a quad is requested in the odd intervals
             for (int i0 = 0; i0 < NI; i0 += 4) {
                 W16_STAMP(1); commit3(R2{}, 2 * i0 + 2, S2{}); commit3(R3{}, 2 * i0 + 3, S2{}); W16_STAMP(3);      // pair i0 + 1 (group 1)
-                store_prev(i0); W16_STAMP(4); lds_sync(); W16_STAMP(5); W16_STAMP_NEXT();
+                store_prev(i0); W16_STAMP(4); barrier_lds_only(); W16_STAMP(5); W16_STAMP_NEXT();
                 W16_STAMP(1); commit3(R0{}, 2 * i0 + 4, S0{}); commit3(R1{}, 2 * i0 + 5, S0{});                    // pair i0 + 2 (group 0)
                 issue(R0{}); issue(R1{}); issue(R2{}); issue(R3{}); W16_STAMP(3);                                // pairs i0 + 4, i0 + 5 -> groups 0, 1
-                store_prev(i0 + 1); W16_STAMP(4); lds_sync(); W16_STAMP(5); W16_STAMP_NEXT();
+                store_prev(i0 + 1); W16_STAMP(4); barrier_lds_only(); W16_STAMP(5); W16_STAMP_NEXT();
                 W16_STAMP(1); commit3(R4{}, 2 * i0 + 6, S2{}); commit3(R5{}, 2 * i0 + 7, S2{}); W16_STAMP(3);      // pair i0 + 3 (group 2)
-                store_prev(i0 + 2); W16_STAMP(4); lds_sync(); W16_STAMP(5); W16_STAMP_NEXT();
+                store_prev(i0 + 2); W16_STAMP(4); barrier_lds_only(); W16_STAMP(5); W16_STAMP_NEXT();
                 W16_STAMP(1); commit3(R0{}, 2 * i0 + 8, S0{}); commit3(R1{}, 2 * i0 + 9, S0{});                    // pair i0 + 4 (group 0)
                 issue(R0{}); issue(R1{}); issue(R4{}); issue(R5{}); W16_STAMP(3);                                // pairs i0 + 6, i0 + 7 -> groups 0, 2
-                store_prev(i0 + 3); W16_STAMP(4); lds_sync(); W16_STAMP(5); W16_STAMP_NEXT();
+                store_prev(i0 + 3); W16_STAMP(4); barrier_lds_only(); W16_STAMP(5); W16_STAMP_NEXT();
             }
             store_prev((NI + IPG - 1) / IPG * IPG);              // what the consumers parked in the very last interval
-            lds_sync();                                          // E
-            lds_sync();                                          // F
+            barrier_lds_only();                                          // E
+            barrier_lds_only();                                          // F
             const int tl = t_hi - 1, ln = tl / tiles_img, lr = tl - ln * tiles_img, lty = lr / tiles_x;
             store_half(0, ln, lty * TH, (lr - lty * tiles_x) * TW);
             store_half(1, ln, lty * TH, (lr - lty * tiles_x) * TW);
@@ -480,7 +422,12 @@ __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
 #endif
             return;
         }
-        for_sets([&](auto k) { issue(k); });
+        // register set of run chunk c = ring slot = c mod 4
+        using I0 = std::integral_constant<int, 0>;
+        using I1 = std::integral_constant<int, 1>;
+        using I2 = std::integral_constant<int, 2>;
+        using I3 = std::integral_constant<int, 3>;
+        issue(I0{}); issue(I1{}); issue(I2{}); issue(I3{});
         for (int c = ptid; c < ctot; c += NMV) {
             const ConvSrc &Sx = c < c0n ? A.src[0] : A.src[1];
             const int cc = c < c0n ? c : c - c0n;
@@ -488,14 +435,12 @@ __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
             s_xf[xfs + c] = Sx.shift ? Sx.shift[cc] : 0.f;
         }
         __syncthreads();                                         // B0: table (+ resident weights)
-        using I0 = std::integral_constant<int, 0>;
-        using I1 = std::integral_constant<int, 1>;
         commit(I0{}, 0);
         commit(I1{}, 1);
         if (STREAM) { dma_w(); dma_w(); }
         issue(I0{});
         issue(I1{});
-        if (STREAM) wait_vm(NHL{});
+        if (STREAM) wait_vmcnt<NHL>();
         __syncthreads();                                         // B1: run chunks 0, 1 staged
         // interval i: the consumers work on run chunks 2i, 2i+1; here the two chunks after them are staged (their register sets are
         // refilled with the chunks PF further on).  One loop iteration = PF / 2 intervals, so that every set index is a constant.
@@ -506,39 +451,39 @@ __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
                     const int qa = 2 * (i0 + M) + 2;
                     using SA = std::integral_constant<int, RA>;
                     using SB = std::integral_constant<int, RB>;
-                    if (!STREAM) {
-                        W16_STAMP(1); commit(SA{}, qa); W16_STAMP(2); issue(SA{}); commit(SB{}, qa + 1); issue(SB{}); W16_STAMP(3);
-                        store_prev(i0 + M);
-                        W16_STAMP(4);
-                        if (OUT) lds_sync(); else __syncthreads();
-                        W16_STAMP(5); W16_STAMP_NEXT();
-                    } else {
-                        commit(SA{}, qa); commit(SB{}, qa + 1);
-                        dma_w(); dma_w();
-                        if (OUT) {
-                            // (the stores sit between the weight DMA and the halo requests: the wait leaves them in flight too; the compiler
-                            //  fences keep that issue order - the explicit vmcnt below counts on it)
-                            asm volatile("" ::: "memory");
-                            const bool stored = store_prev(i0 + M);
-                            asm volatile("" ::: "memory");
-                            issue(SA{}); issue(SB{});
-                            // (the stores of a half - NRS of them, plus NRS / 2 pooled ones - are younger than the weight DMA and stay in flight)
-                            constexpr int NRS = 32 / (64 / (BN / 8));
-                            if (!stored) stream_sync(NHL{});
-                            else if (A.pool_out) stream_sync(std::integral_constant<int, 2 * NA + NRS + NRS / 2>{});
-                            else stream_sync(std::integral_constant<int, 2 * NA + NRS>{});
-                        } else {
-                            issue(SA{}); issue(SB{});
-                            stream_sync(NHL{});
-                        }
-                    }
+            if (!STREAM) {
+                W16_STAMP(1); commit(SA{}, qa); W16_STAMP(2); issue(SA{}); commit(SB{}, qa + 1); issue(SB{}); W16_STAMP(3);
+                store_prev(i0 + M);
+                W16_STAMP(4);
+                if (OUT) barrier_lds_only(); else __syncthreads();
+                W16_STAMP(5); W16_STAMP_NEXT();
+            } else {
+                commit(SA{}, qa); commit(SB{}, qa + 1);
+                dma_w(); dma_w();
+                if (OUT) {
+                    // (the stores sit between the weight DMA and the halo requests: the wait leaves them in flight too; the compiler
+                    //  fences keep that issue order - the explicit vmcnt below counts on it)
+                    asm volatile("" ::: "memory");
+                    const bool stored = store_prev(i0 + M);
+                    asm volatile("" ::: "memory");
+                    issue(SA{}); issue(SB{});
+                    // (the stores of a half - NRS of them, plus NRS / 2 pooled ones - are younger than the weight DMA and stay in flight)
+                    constexpr int NRS = 32 / (64 / (BN / 8));
+                    if (!stored) barrier_keep_vm<NHL>();
+                    else if (A.pool_out) barrier_keep_vm<2 * NA + NRS + NRS / 2>();
+                    else barrier_keep_vm<2 * NA + NRS>();
+                } else {
+                    issue(SA{}); issue(SB{});
+                    barrier_keep_vm<NHL>();
+                }
+            }
                 }(), ...);
             }(std::make_integer_sequence<int, IPG>{});
         }
         if (OUT) {
             store_prev((NI + IPG - 1) / IPG * IPG);              // what the consumers parked in the very last interval
-            lds_sync();                                          // E: this wave's reads of the out image are done - the consumers park the last tile
-            lds_sync();                                          // F: ... both halves of it are in the image
+            barrier_lds_only();                                          // E: this wave's reads of the out image are done - the consumers park the last tile
+            barrier_lds_only();                                          // F: ... both halves of it are in the image
             const int tl = t_hi - 1, ln = tl / tiles_img, lr = tl - ln * tiles_img, lty = lr / tiles_x;
             store_half(0, ln, lty * TH, (lr - lty * tiles_x) * TW);
             store_half(1, ln, lty * TH, (lr - lty * tiles_x) * TW);
@@ -747,11 +692,7 @@ __global__ __launch_bounds__(512) void conv_ws16_kernel(ConvArgs A) {
     const unsigned l_off = ((unsigned)(l31 >> 4) * (unsigned)A.W + (unsigned)(l31 & 15)) * pix_b + (unsigned)half * 16u;
     char *const out_b = reinterpret_cast<char *>(A.out + A.out_coff + cout0);
     int p_n, p_y0, p_x0;                                         // the finished tile (whose epilogue rides in the current one)
-    {
-        p_n = t_lo / tiles_img;
-        const int r = t_lo - p_n * tiles_img, ty = r / tiles_x;
-        p_y0 = ty * TH; p_x0 = (r - ty * tiles_x) * TW;
-    }
+    seek_tile(t_lo, tiles_img, tiles_x, p_n, p_y0, p_x0);
     char *row_base[NPI];
     auto set_row_bases = [&]() {
 #pragma unroll
@@ -957,9 +898,7 @@ static int try_launch_ws16(const ConvArgs &A, hipStream_t st, bool dry_run) {
     const int wres = mix ? L::wbytes(n0, n1) : L::wbytes(nch, 0);
     const bool stream = wres > L::RES_MAX;
     if (stream && (mix || (nch & 1))) return -1;
-    // halo ring: four slots under the register movers; under the DMA movers (plain sources) seven - five chunks ahead of the consumers -
-    // or six beside the one-tap chunks' extra weights
-    const int ns = 4;
+    const int ns = 4;                                             // halo ring slots
     static const int out_env = getenv("CDNET_WS16_OUT") ? atoi(getenv("CDNET_WS16_OUT")) : 1;
     // (the out-image form requests its halo by chunk PAIRS: every pair from one source)
     const bool out = out_env && nch >= 4 && !(nch & 1) && !(n0 & 1) && L::bytes(ns, stream ? 4 * L::WCH9 : wres, ctot, true) + W16_STAMP_BYTES <= 160 * 1024;
@@ -980,7 +919,7 @@ static int try_launch_ws16(const ConvArgs &A, hipStream_t st, bool dry_run) {
 #ifndef CDNET_WS16_PAIR_DEFAULT
 #define CDNET_WS16_PAIR_DEFAULT 1
 #endif
-    auto go = [&](auto xf_c, auto sm_c, auto mx_c, auto ncs_c, auto pf_c) -> int {
+    auto go = [&](auto xf_c, auto sm_c, auto mx_c, auto ncs_c) -> int {
         constexpr int XF = decltype(xf_c)::value;
         constexpr bool PAIR_ = CDNET_WS16_PAIR_DEFAULT != 0;    // (A/B builds: tools/build_variant.sh nopair "-DCDNET_WS16_PAIR_DEFAULT=0" conv16ws.hip)
         constexpr bool OUTOK = decltype(ncs_c)::value == 0;
@@ -994,7 +933,7 @@ static int try_launch_ws16(const ConvArgs &A, hipStream_t st, bool dry_run) {
                 // 64 - profiles/HISTORY.md); the one-tap form spilled.
                 if constexpr (STREAM_) {
                     g_conv_last_form = conv_form(CDNET_CONV_FAMILY_WS16, BN, 9, XF, false, STREAM_, MIX_, 0, 3);
-                    return launch_lds<conv_ws16_kernel<BN, XF, STREAM_, MIX_, 0, 4, decltype(pf_c)::value, true, true, PAIR_>>(
+                    return launch_lds<conv_ws16_kernel<BN, XF, STREAM_, MIX_, 0, true, true, PAIR_>>(
                         grid, 512, 160 * 1024, smem, st, "hipFuncSetAttribute(conv_ws16 k32)", "conv_ws16_kernel(k32)", A);
                 }
 #ifndef CDNET_WS16_QUAD_DEFAULT
@@ -1007,21 +946,19 @@ static int try_launch_ws16(const ConvArgs &A, hipStream_t st, bool dry_run) {
                 const long long io_bytes = 2LL * A.N * A.H * A.W * (ctot + A.Cout);
                 if constexpr (!STREAM_ && PAIR_ && CDNET_WS16_QUAD_DEFAULT != 0) if (!(n0 & 3) && !(n1 & 3) && (io_bytes >= (512LL << 20) || (A.debug & CONV_DBG_WS16_QUAD))) {      // (tests: the quad form on small launches)
                     g_conv_last_form = conv_form(CDNET_CONV_FAMILY_WS16, BN, 9, XF, false, STREAM_, MIX_, 0, 2);
-                    return launch_lds<conv_ws16_kernel<BN, XF, STREAM_, MIX_, 0, 4, decltype(pf_c)::value, true, false, true, true>>(
+                    return launch_lds<conv_ws16_kernel<BN, XF, STREAM_, MIX_, 0, true, false, true, true>>(
                         grid, 512, 160 * 1024, smem, st, "hipFuncSetAttribute(conv_ws16 quad)", "conv_ws16_kernel(quad)", A);
                 }
                 g_conv_last_form = conv_form(CDNET_CONV_FAMILY_WS16, BN, 9, XF, false, STREAM_, MIX_, 0, 1);
-                return launch_lds<conv_ws16_kernel<BN, XF, STREAM_, MIX_, 0, 4, decltype(pf_c)::value, true, false, PAIR_>>(
+                return launch_lds<conv_ws16_kernel<BN, XF, STREAM_, MIX_, 0, true, false, PAIR_>>(
                     grid, 512, 160 * 1024, smem, st, "hipFuncSetAttribute(conv_ws16 out)", "conv_ws16_kernel(out)", A);
             }
         }
         constexpr bool STREAM = decltype(sm_c)::value;
         constexpr bool MIX = decltype(mx_c)::value;
         constexpr int NCS = decltype(ncs_c)::value;
-        constexpr int PFD = decltype(pf_c)::value;
-        constexpr int NS = 4;
         g_conv_last_form = conv_form(CDNET_CONV_FAMILY_WS16, BN, 9, XF, false, STREAM, MIX, NCS, 0);
-        return launch_lds<conv_ws16_kernel<BN, XF, STREAM, MIX, NCS, NS, PFD, false>>(grid, 512, 160 * 1024, smem, st, "hipFuncSetAttribute(conv_ws16)", "conv_ws16_kernel", A);
+        return launch_lds<conv_ws16_kernel<BN, XF, STREAM, MIX, NCS, false>>(grid, 512, 160 * 1024, smem, st, "hipFuncSetAttribute(conv_ws16)", "conv_ws16_kernel", A);
     };
     using C0 = std::integral_constant<int, 0>;
     using C1 = std::integral_constant<int, 1>;
@@ -1029,7 +966,7 @@ static int try_launch_ws16(const ConvArgs &A, hipStream_t st, bool dry_run) {
     using F_ = std::false_type;
     using T_ = std::true_type;
     auto by_xf = [&](auto sm_c, auto mx_c, auto ncs_c) -> int {
-        return with_int<2, 0>(all_plain ? 0 : 2, [&](auto xf_c) { return go(xf_c, sm_c, mx_c, ncs_c, std::integral_constant<int, 4>{}); });
+        return with_int<2, 0>(all_plain ? 0 : 2, [&](auto xf_c) { return go(xf_c, sm_c, mx_c, ncs_c); });
     };
     if (stream) return by_xf(T_{}, F_{}, C0{});                  // (an even chunk count >= 6)
     if (mix) return by_xf(F_{}, T_{}, C0{});

@@ -18,6 +18,8 @@
 //     straight from the accumulators to HBM (bias / folded BatchNorm / ReLU in fp32; the 32 lanes of a half write one 128-byte line of
 //     a pixel), a quarter of it per chunk interval, one 256-byte store every ~7 MFMAs.  No LDS out image, no second pass;
 //   * one barrier per chunk interval (108 MFMAs per consumer wave); 120 KB of LDS.
+// The movers' scaffolding - run of tiles, tile cursor, halo validity masks, buffer descriptors, the barrier that keeps requests in flight,
+// the LDS-DMA piece - is persist.h; what is written out here is what this kernel alone does: hi / lo planes, the BNS raw DMA, MIX, POOL.
 // The MFMA sequence per accumulator (chunk, tap, lo*hi, hi*lo, hi*hi) is conv_f32_kernel's, so the outputs are bit-identical
 // (tests/test_gpu_fp32_kernels.py compares the two and both against fp64); the per-tile statistics are summed in conv_ws_kernel's
 // order (blocks (ni, mi), registers ascending, the two lane halves, then the four waves).
@@ -31,6 +33,7 @@
 #include "common.h"
 #include "conv_args.h"
 #include "launch.h"
+#include "persist.h"
 #include "split_bf16.h"
 #include <stdlib.h>
 
@@ -38,17 +41,6 @@ using namespace cdnet;
 
 
 namespace {
-
-// One LDS-DMA piece (64 lanes x 16 bytes = 1 KB): global (uniform base + this lane's byte offset) -> LDS (uniform byte address + lane * 16).
-// Inline assembly on purpose: the compiler does not count it, so (a) it puts no alias guard - s_waitcnt vmcnt(<everything up to the
-// DMA>) - in front of this wave's later LDS accesses, which lets the weight DMA of an interval be issued FIRST and land while the halo
-// chunk is transformed and written, and (b) the wave waits for it itself: conv_ws32_kernel's stream_sync counts the vector-memory
-// operations issued after it.  M0 (the DMA's LDS base) is saved and restored around the piece.
-__device__ __forceinline__ void glds_piece(const void *gbase, unsigned lane_bytes, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(lane_bytes), "s"(gbase), "s"(lds_dst) : "memory");
-}
 
 template <int BN>
 struct Ws32Lds {
@@ -111,23 +103,12 @@ __global__ __launch_bounds__(512) void conv_ws32_kernel(ConvArgs A) {
     const int cout_tile = blockIdx.y;
     const int cout0 = cout_tile * BN;
 
-    // this workgroup's contiguous run of tiles; XCD k (workgroups k, k+8, ...) serves the k-th eighth of the tiles (conv_ws_kernel)
+    // this workgroup's contiguous run of tiles (persist.h)
     const int tiles_x = A.W / TW, tiles_y = A.H / TH;
     const int tiles_img = tiles_x * tiles_y;
     const int T = A.N * tiles_img;
     int t_lo, t_hi;
-    {
-        const int G = (int)gridDim.x, b = (int)blockIdx.x;
-        if ((G & 7) == 0) {
-            const int xcd = b & 7, idx = b >> 3, nw = G >> 3;
-            const long long x0 = (long long)T * xcd / 8, x1 = (long long)T * (xcd + 1) / 8;
-            t_lo = (int)(x0 + (x1 - x0) * idx / nw);
-            t_hi = (int)(x0 + (x1 - x0) * (idx + 1) / nw);
-        } else {
-            t_lo = (int)((long long)T * b / G);
-            t_hi = (int)((long long)T * (b + 1) / G);
-        }
-    }
+    tile_run(T, (int)gridDim.x, (int)blockIdx.x, t_lo, t_hi);
     const int ntl = t_hi - t_lo;
     const int S = ntl * NCH;                                      // chunk intervals of this workgroup
     if (S == 0) return;
@@ -146,32 +127,16 @@ __global__ __launch_bounds__(512) void conv_ws32_kernel(ConvArgs A) {
             hyx[i] = ptid + i * 256 < NPIX * VPP ? ((hy << 8) | hx) : 0x1f1f;      // (31 = a vector that never exists: bit 31 of the masks is always set)
             doff[i] = pix * PSTR + ((slot ^ (hy & 1)) * 16);
         }
-        // Requests go through buffer descriptors (one per source, tensors below 2 GB): a vector outside the image / the source window
-        // carries bit 31 in its byte offset, the range check returns zeros for it - no select, no 64-bit address arithmetic and, for plain
-        // sources, no mask per vector (every vector instruction of a mover wave costs the consumers' MFMA stream issue time).  Validity of a
-        // tile's halo rows / columns = two scalar bit masks per tile and source.
+        // requests go through buffer descriptors, zero fill by bit 31 of the byte offset (persist.h)
         const unsigned src_bytes0 = (unsigned)A.N * A.src[0].Hs * (A.src[0].row_stride ? A.src[0].row_stride : A.src[0].Ws * A.src[0].C) * 4u;
         const unsigned src_bytes1 = A.nsrc > 1 ? (unsigned)A.N * A.src[1].Hs * (A.src[1].row_stride ? A.src[1].row_stride : A.src[1].Ws * A.src[1].C) * 4u : 0u;
-        const __amdgpu_buffer_rsrc_t rsx0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short *>(A.src[0].x), 0, (int)src_bytes0, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsx1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short *>(A.nsrc > 1 ? A.src[1].x : A.src[0].x), 0, (int)src_bytes1, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsr0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short *>(A.src[0].res ? A.src[0].res : A.src[0].x), 0, (int)src_bytes0, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsr1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short *>(A.nsrc > 1 && A.src[1].res ? A.src[1].res : A.src[0].x), 0, (int)src_bytes1, 0x00020000);
-        auto bload = [](__amdgpu_buffer_rsrc_t r, unsigned voff) -> f32x4 {
-            return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, 0, 0));
-        };
-        // bits [lo, hi) clear, everything else set (lo, hi clamped to [0, 31])
-        auto bad_mask = [](int lo, int hi) -> unsigned {
-            lo = lo < 0 ? 0 : (lo > 31 ? 31 : lo);
-            hi = hi < lo ? lo : (hi > 31 ? 31 : hi);
-            return ~(((1u << hi) - 1u) & ~((1u << lo) - 1u));
-        };
+        const __amdgpu_buffer_rsrc_t rsx0 = buf_rsrc(A.src[0].x, src_bytes0);
+        const __amdgpu_buffer_rsrc_t rsx1 = buf_rsrc(A.nsrc > 1 ? A.src[1].x : A.src[0].x, src_bytes1);
+        const __amdgpu_buffer_rsrc_t rsr0 = buf_rsrc(A.src[0].res ? A.src[0].res : A.src[0].x, src_bytes0);
+        const __amdgpu_buffer_rsrc_t rsr1 = buf_rsrc(A.nsrc > 1 && A.src[1].res ? A.src[1].res : A.src[0].x, src_bytes1);
         // issue cursor: chunk ik of the tile at (in_, iy0, ix0); saturates on the last chunk of the run
         int ik = 0, ic = 0, in_, iy0, ix0;
-        {
-            in_ = t_lo / tiles_img;
-            const int r = t_lo - in_ * tiles_img, ty = r / tiles_x;
-            iy0 = ty * TH; ix0 = (r - ty * tiles_x) * TW;
-        }
+        seek_tile(t_lo, tiles_img, tiles_x, in_, iy0, ix0);
         int o_n = in_, o_y0 = iy0, o_x0 = ix0;   // BNS: the tile the consumers are accumulating,
         int s_n = 0, s_y0 = 0, s_x0 = 0;         //      the finished tile whose epilogue rides in the current one
         bool s_ok = false;
@@ -192,7 +157,7 @@ __global__ __launch_bounds__(512) void conv_ws32_kernel(ConvArgs A) {
                 // halo row r <-> y = iy0 - 1 + r, halo column c <-> x = ix0 - 1 + c; valid = inside the image and the source window
                 const int ylo = s.off_y > 0 ? s.off_y : 0, yhi = A.H < s.off_y + s.Hs ? A.H : s.off_y + s.Hs;
                 const int xlo = s.off_x > 0 ? s.off_x : 0, xhi = A.W < s.off_x + s.Ws ? A.W : s.off_x + s.Ws;
-                const unsigned rowbad = bad_mask(ylo - (iy0 - 1), yhi - (iy0 - 1)), colbad = bad_mask(xlo - (ix0 - 1), xhi - (ix0 - 1));
+                const unsigned rowbad = halo_bad_mask(ylo - (iy0 - 1), yhi - (iy0 - 1)), colbad = halo_bad_mask(xlo - (ix0 - 1), xhi - (ix0 - 1));
                 const unsigned img_b = (unsigned)((in_ * s.Hs + (iy0 - 1 - s.off_y)) * rs + (ix0 - 1 - s.off_x) * s.C) * 4u;
                 const unsigned rs_b = (unsigned)rs * 4u, c_b = (unsigned)s.C * 4u;
 #pragma unroll
@@ -208,16 +173,12 @@ __global__ __launch_bounds__(512) void conv_ws32_kernel(ConvArgs A) {
             for (int i = 0; i < NA; ++i) {
                 const unsigned voff = ge[i] + cc0_b;                   // (a zero-fill vector keeps bit 31: beyond every tensor the launcher admits)
                 eo[R][i] = voff;
-                pa[R][i][0] = bload(rsx, voff);
-                pa[R][i][1] = bload(rsx, voff + 16u);
+                pa[R][i][0] = buf_load128<f32x4>(rsx, voff);
+                pa[R][i][1] = buf_load128<f32x4>(rsx, voff + 16u);
             }
             if (ic + 1 < S) {
                 ++ic;
-                if (++ik == NCH) {
-                    ik = 0;
-                    ix0 += TW;
-                    if (ix0 >= A.W) { ix0 = 0; iy0 += TH; if (iy0 >= A.H) { iy0 = 0; ++in_; } }
-                }
+                if (++ik == NCH) { ik = 0; next_tile(in_, iy0, ix0, A.H, A.W); }
             }
         };
         // chunk c_ of the run (register set R = c_ & 1) -> halo slot c_ & 1
@@ -241,8 +202,8 @@ __global__ __launch_bounds__(512) void conv_ws32_kernel(ConvArgs A) {
                 const __amdgpu_buffer_rsrc_t rsr = si ? rsr1 : rsr0;
 #pragma unroll
                 for (int i = 0; i < NA; ++i) {
-                    rr[i][0] = bload(rsr, eo[R][i]);
-                    rr[i][1] = bload(rsr, eo[R][i] + 16u);
+                    rr[i][0] = buf_load128<f32x4>(rsr, eo[R][i]);
+                    rr[i][1] = buf_load128<f32x4>(rsr, eo[R][i] + 16u);
                 }
             }
             unsigned char *dst0 = lds_a + R * L::A_SLOT;
@@ -318,16 +279,8 @@ __global__ __launch_bounds__(512) void conv_ws32_kernel(ConvArgs A) {
             for (int i = 0; i < 4; ++i)
                 glds_piece(rb + ((size_t)(i >> 1) * A.W + (i & 1) * 8) * A.Cout * 4, raw_lane, lds_raw_addr + (q & 1) * L::RAW_Q + pw * 4096 + i * 1024);
         };
-        // the movers' barrier by hand (conv_ws_kernel): this wave's LDS writes done, everything older than its N youngest vector-memory
-        // operations - the weight DMA of this interval - landed, then the barrier; the halo requests issued after the DMA stay in flight
-        auto stream_sync = [](auto n_c) {
-            constexpr int N = decltype(n_c)::value;
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (0 << 8) | ((N >> 4) << 14));
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-        };
-        using NHL = std::integral_constant<int, 2 * NA>;          // halo requests of one interval (one chunk: NA vectors of two loads)
+        constexpr int NHL = 2 * NA;                               // halo requests of one interval (one chunk: NA vectors of two loads): they
+                                                                  // stay in flight over the movers' barrier (barrier_keep_vm, persist.h)
         using I0 = std::integral_constant<int, 0>;
         using I1 = std::integral_constant<int, 1>;
         issue(I0{});
@@ -342,7 +295,7 @@ __global__ __launch_bounds__(512) void conv_ws32_kernel(ConvArgs A) {
         dma_w(0);
         commit(I0{}, 0);
         issue(I0{});
-        stream_sync(NHL{});                                      // chunk 0 staged, its weights landed
+        barrier_keep_vm<NHL>();                                      // chunk 0 staged, its weights landed
         // interval k: the consumers work on chunk k (slots k & 1).  Here: the weights of chunk k+1 leave for the other weight slot first
         // (DMA: they land while the rest of the interval runs), chunk k+1 is transformed, split and written into the other halo slot,
         // chunk k+3 is requested.  The explicit wait in front of the barrier leaves the 2 NA youngest vector-memory operations - those
@@ -359,12 +312,11 @@ __global__ __launch_bounds__(512) void conv_ws32_kernel(ConvArgs A) {
             commit(rc, k + 1);
             asm volatile("" ::: "memory");
             issue(rc);
-            stream_sync(NHL{});
+            barrier_keep_vm<NHL>();
             if (BNS && ++kt == NCH) {
                 kt = 0;
                 s_n = o_n; s_y0 = o_y0; s_x0 = o_x0; s_ok = true;
-                o_x0 += TW;
-                if (o_x0 >= A.W) { o_x0 = 0; o_y0 += TH; if (o_y0 >= A.H) { o_y0 = 0; ++o_n; } }
+                next_tile(o_n, o_y0, o_x0, A.H, A.W);
             }
         };
         for (int k = 0; k < S; k += 2) {
@@ -398,11 +350,7 @@ __global__ __launch_bounds__(512) void conv_ws32_kernel(ConvArgs A) {
     const unsigned l_off = (unsigned)(4 * half) * pix_b + (unsigned)l31 * 4u;
     char *const out_b = reinterpret_cast<char *>(reinterpret_cast<float *>(A.out) + A.out_coff + cout0);
     int p_n, p_y0, p_x0;                                         // the finished tile (whose epilogue rides in the current one)
-    {
-        p_n = t_lo / tiles_img;
-        const int r = t_lo - p_n * tiles_img, ty = r / tiles_x;
-        p_y0 = ty * TH; p_x0 = (r - ty * tiles_x) * TW;
-    }
+    seek_tile(t_lo, tiles_img, tiles_x, p_n, p_y0, p_x0);
     float e_osc[NPW], e_osh[NPW];
     bool e_ok[NPW];
 #pragma unroll

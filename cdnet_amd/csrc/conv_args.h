@@ -75,7 +75,7 @@ static_assert(sizeof(ConvArgs) == sizeof(cdnet_conv_args), "ConvArgs layout");
 
 namespace cdnet {
 // which instantiation the last launch of this thread took (cdnet_conv_forward_last_form; host only, bit layout in cdnet_hip.h): every
-// launcher of conv.hip / conv16ws.hip / conv32.hip / conv32ws.hip writes it just before its launch, the tests assert it
+// launcher of conv.hip / conv_ws.hip / conv16ws.hip / conv32.hip / conv32ws.hip writes it just before its launch, the tests assert it
 extern thread_local int g_conv_last_form;
 constexpr int conv_form(int family, int bn, int taps, int xf = 0, bool stats = false, bool stream = false, bool mix = false, int ncs = 0,
                         int site = 0, int tile = 16, int ck = 16, int nch = 0, bool eres = false) {
@@ -89,5 +89,7 @@ int conv_forward_f32(const ConvArgs &A, hipStream_t st);
 int conv_forward_f32_ws(const ConvArgs &A, hipStream_t st, bool dry_run = false);
 // conv16ws.hip: the 16-bit path's persistent kernel for launches without statistics (any chunk count, direct stores); -1 = not eligible
 int conv_forward_ws16(const ConvArgs &A, hipStream_t st, bool dry_run = false);
+// conv_ws.hip: the 16-bit path's persistent kernel for launches with statistics (3x3, 16-channel chunks in fours); -1 = not eligible
+int conv_forward_ws(const ConvArgs &A, hipStream_t st, bool dry_run = false);
 int materialize_f32(const ConvSrc &s, int N, int H, int W, void *out, hipStream_t st);
 }

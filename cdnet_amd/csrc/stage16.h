@@ -1,5 +1,6 @@
-// Staging helpers shared by the 16-bit convolution kernels (conv.hip, conv16ws.hip): storage-format loads, the generic fused source
-// transform of 8 channels (producer BatchNorm scale / shift, residual operand, ReLU -> bf16 MFMA operand).
+// Staging helpers shared by the 16-bit convolution kernels (conv.hip, conv_ws.hip, conv16ws.hip) and the weight packer (pack.hip):
+// storage-format loads, the generic fused source transform of 8 channels (producer BatchNorm scale / shift, residual operand, ReLU ->
+// bf16 MFMA operand).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "vec.h"

@@ -16,6 +16,7 @@
 #include "common.h"
 #include "conv_args.h"
 #include "launch.h"
+#include "persist.h"
 #include "split_bf16.h"
 #include "xform.h"
 
@@ -1040,12 +1041,9 @@ __global__ __launch_bounds__(512) void wgrad_ws32_kernel(WgradArgs A) {
         // range check returns zeros for it - no test, no select and no 64-bit address arithmetic per vector (a vector instruction of a
         // mover wave costs ~10 ns beside the consumers' MFMA stream, stamped: the movers, not the matrix pipe, bounded this kernel).
         // Validity of a tile's halo rows / columns = two scalar bit masks per tile; per vector: two shifts, or, bit extract.
-        const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(sx), 0, (int)((unsigned)A.N * s.Hs * rs * 4u), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(sr ? sr : sx), 0, (int)((unsigned)A.N * s.Hs * rs * 4u), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_g = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(gx), 0, (int)((unsigned)A.N * A.H * A.W * A.Cout * 4u), 0x00020000);
-        auto bload = [](__amdgpu_buffer_rsrc_t r, unsigned voff) -> f32x4 {
-            return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, 0, 0));
-        };
+        const __amdgpu_buffer_rsrc_t rs_a = buf_rsrc(sx, (unsigned)A.N * s.Hs * rs * 4u);
+        const __amdgpu_buffer_rsrc_t rs_r = buf_rsrc(sr ? sr : sx, (unsigned)A.N * s.Hs * rs * 4u);
+        const __amdgpu_buffer_rsrc_t rs_g = buf_rsrc(gx, (unsigned)A.N * A.H * A.W * A.Cout * 4u);
         // what depends on the thread only: halo coordinates (31 = a vector that never exists: the masks' bit 31 is always set), byte
         // offsets inside a tile and LDS addresses of its vectors
         int ahy[NA], ahx[NA], adst[NA], gpy[NG], gpx[NG], gdst[NG];
@@ -1071,12 +1069,6 @@ __global__ __launch_bounds__(512) void wgrad_ws32_kernel(WgradArgs A) {
         }
         const int ylo = s.off_y > 0 ? s.off_y : 0, yhi = A.H < s.off_y + s.Hs ? A.H : s.off_y + s.Hs;       // valid rows / columns of
         const int xlo = s.off_x > 0 ? s.off_x : 0, xhi = A.W < s.off_x + s.Ws ? A.W : s.off_x + s.Ws;       // the input: image and source window
-        // bits [lo, hi) clear, everything else set (lo, hi clamped to [0, 31])
-        auto bad_mask = [](int lo, int hi) -> unsigned {
-            lo = lo < 0 ? 0 : (lo > 31 ? 31 : lo);
-            hi = hi < lo ? lo : (hi > 31 ? 31 : hi);
-            return ~(((1u << hi) - 1u) & ~((1u << lo) - 1u));
-        };
         // tile cursor of the request stream: tile ks + j * ksplit as (image, tile row, tile column), advanced by ksplit without divisions
         int c_n, c_ty, c_tx, c_j = 0;
         {
@@ -1091,24 +1083,24 @@ __global__ __launch_bounds__(512) void wgrad_ws32_kernel(WgradArgs A) {
             constexpr int R = decltype(rc)::value;
             const int y0 = c_ty * TH_, x0 = c_tx * TW;
             // halo row r <-> y = y0 - 1 + r, halo column c <-> x = x0 - 1 + c
-            const unsigned rowbad = bad_mask(ylo - (y0 - 1), yhi - (y0 - 1)), colbad = bad_mask(xlo - (x0 - 1), xhi - (x0 - 1));
+            const unsigned rowbad = halo_bad_mask(ylo - (y0 - 1), yhi - (y0 - 1)), colbad = halo_bad_mask(xlo - (x0 - 1), xhi - (x0 - 1));
             const unsigned abase_b = (unsigned)((c_n * s.Hs + (y0 - 1 - s.off_y)) * rs + (x0 - 1 - s.off_x) * s.C + ib * CI) * 4u;
 #pragma unroll
             for (int i = 0; i < NA; ++i) {
                 const unsigned t = (rowbad >> ahy[i]) | (colbad >> ahx[i]);
                 const unsigned voff = (abase_b + aoffb[i]) | (unsigned)(-(int)(t & 1u));
                 av[R][i] = voff;
-                pa_[R][i][0] = bload(rs_a, voff);
-                pa_[R][i][1] = bload(rs_a, voff | 16u);          // (| 16: the ~0 of a zero-fill vector stays out of range)
+                pa_[R][i][0] = buf_load128<f32x4>(rs_a, voff);
+                pa_[R][i][1] = buf_load128<f32x4>(rs_a, voff | 16u);          // (| 16: the ~0 of a zero-fill vector stays out of range)
             }
-            const unsigned growbad = bad_mask(0, A.H - y0), gcolbad = bad_mask(0, A.W - x0);
+            const unsigned growbad = halo_bad_mask(0, A.H - y0), gcolbad = halo_bad_mask(0, A.W - x0);
             const unsigned gbase_b = (unsigned)(((c_n * A.H + y0) * A.W + x0) * A.Cout + cb * CO) * 4u;
 #pragma unroll
             for (int i = 0; i < NG; ++i) {
                 const unsigned t = (growbad >> gpy[i]) | (gcolbad >> gpx[i]);
                 const unsigned voff = (gbase_b + goffb[i]) | (unsigned)(-(int)(t & 1u));
-                pg_[R][i][0] = bload(rs_g, voff);
-                pg_[R][i][1] = bload(rs_g, voff | 16u);
+                pg_[R][i][0] = buf_load128<f32x4>(rs_g, voff);
+                pg_[R][i][1] = buf_load128<f32x4>(rs_g, voff | 16u);
             }
             if (c_j + 1 < ntl) {             // (past the end the last tile is requested and staged again, into the buffer nobody reads)
                 ++c_j;
@@ -1124,8 +1116,8 @@ __global__ __launch_bounds__(512) void wgrad_ws32_kernel(WgradArgs A) {
             if (has_res) {
 #pragma unroll
                 for (int i = 0; i < NA; ++i) {
-                    rr[i][0] = bload(rs_r, av[R][i]);
-                    rr[i][1] = bload(rs_r, av[R][i] | 16u);
+                    rr[i][0] = buf_load128<f32x4>(rs_r, av[R][i]);
+                    rr[i][1] = buf_load128<f32x4>(rs_r, av[R][i] | 16u);
                 }
             }
 #pragma unroll

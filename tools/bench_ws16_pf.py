@@ -1,5 +1,6 @@
 """dominant layer (3x3 64->64 @256x256) on conv_ws16_kernel, 16 and 64 tiles, with the ablations (8 no stores, 2 no halo requests, 1 no MFMAs);
-the round-4 A/B of the mover variants (DMA / 4, 8, 12 chunks in flight: profiles/HISTORY.md) was taken with this script under CDNET_WS16_PF"""
+the round-4 A/B of the mover variants (DMA / 4, 8, 12 chunks in flight: profiles/HISTORY.md) was taken with this script; those variants and
+the environment variable that selected them were removed with the experiment - the kernel has one form of movers, four chunks in flight"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -27,21 +27,19 @@ f.argtypes = [ctypes.c_void_p]
 cfg = (16, 16, 64)
 NAMES = {(1, 2): 'mover: wait halo A + LDS writes', (2, 3): 'mover: request A, commit B, request B', (3, 4): 'mover: out-image reads + global stores',
          (4, 5): 'mover: lgkmcnt(0) + barrier', (5, 1): 'mover: loop', (12, 13): 'consumer: chunk 1 (36 MFMAs)', (13, 11): 'consumer: chunk 2 (36 MFMAs)',
-         (11, 12): 'consumer: barrier',
-         (21, 22): 'storer: out-image reads + global stores', (22, 23): 'storer: lgkmcnt(0) + barrier', (23, 21): 'storer: loop'}
+         (11, 12): 'consumer: barrier'}
 
 
 def report(tag):
-    buf = np.zeros(3072, dtype=np.uint64)
+    buf = np.zeros(2048, dtype=np.uint64)
     assert f(buf.ctypes.data) == 0
-    for role, off in (('consumer', 0), ('mover', 1024), ('storer', 2048)):
+    for role, off in (('consumer', 0), ('mover', 1024)):
         v = buf[off:off + 1024]
         n = int(np.argmax(v == 0))
         ids = (v[:n] & np.uint64(255)).astype(int)
         ts = (v[:n] >> np.uint64(8)).astype(np.int64)
         if n < 8:
-            if role != 'storer':
-                print('  %s: no stamps' % role)
+            print('  %s: no stamps' % role)
             continue
         ts = (ts - ts[0]) / 100.0
         d = collections.defaultdict(list)
