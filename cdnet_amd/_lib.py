@@ -249,6 +249,11 @@ SIGNATURES = {
     'cdnet_label_encoding': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     'cdnet_weight_map_radius': (_i, [C.c_double, C.c_double]),
     'cdnet_weight_map': (_i, [_vp, _i, _i, C.c_double, C.c_double, _vp, _vp]),
+    'cdnet_resize_workspace_bytes': (_sz, [_i] * 7),
+    'cdnet_resize_bilinear': (_i, [_vp] + [_i] * 6 + [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    'cdnet_resize_last_form': (_i, []),
+    'cdnet_fill_remove_small': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    'cdnet_label8_dilate': (_i, [_vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

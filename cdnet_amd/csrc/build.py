@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 LIB = os.path.join(PKG, 'libcdnet_hip.so')
 OBJ_DIR = os.path.join(HERE, 'build')
-SOURCES = ['abi.hip', 'box.hip', 'postproc.hip', 'postproc_tile.hip', 'conv.hip', 'conv_ws.hip', 'pack.hip', 'conv32.hip', 'conv32ws.hip', 'conv16ws.hip', 'dilated.hip', 'dilated_train.hip', 'resample.hip', 'wgrad.hip', 'model.hip', 'head_bwd.hip', 'classifier16.hip', 'dam_loss.hip', 'bn_bwd.hip', 'cdm.hip', 'metrics.hip', 'augment.hip', 'optim.hip', 'variance.hip', 'boundary.hip', 'mask_loss.hip', 'weight_map.hip', 'instance_fill.hip']
+SOURCES = ['abi.hip', 'box.hip', 'postproc.hip', 'postproc_tile.hip', 'conv.hip', 'conv_ws.hip', 'pack.hip', 'conv32.hip', 'conv32ws.hip', 'conv16ws.hip', 'dilated.hip', 'dilated_train.hip', 'resample.hip', 'wgrad.hip', 'model.hip', 'head_bwd.hip', 'classifier16.hip', 'dam_loss.hip', 'bn_bwd.hip', 'cdm.hip', 'metrics.hip', 'augment.hip', 'optim.hip', 'variance.hip', 'boundary.hip', 'mask_loss.hip', 'weight_map.hip', 'instance_fill.hip', 'resize.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++20', '-fPIC', '-ffp-contract=off', '-Wall',
          '-Wno-unused-function', '-Wno-unused-result']
 

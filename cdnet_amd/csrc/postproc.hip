@@ -902,6 +902,68 @@ extern "C" int cdnet_cc_chain(const uint8_t *pred, int fg_value, int N, int H, i
     return check_launch("cdnet_cc_chain");
 }
 
+// The first two stages of cdnet_cc_chain alone, up to its `small` output: binary_fill_holes then remove_small_objects(min_area)
+// (test_dam.py:546-548) - what the 'scale' transform resizes back before anything is labelled.  The same launches as stages 1-2 of
+// cdnet_cc_chain and its cc_diag_merge_kernel, which writes `small`; the chain's numbering, relabel and dilation are not queued.
+// Workspace: cdnet_cc_workspace_bytes(N, H, W).
+extern "C" int cdnet_fill_remove_small(const uint8_t *pred, int fg_value, int N, int H, int W, int min_area, void *workspace,
+                                       size_t workspace_bytes, uint8_t *small, void *stream) {
+    CDNET_REQUIRE(pred && small && workspace, "cdnet_fill_remove_small: null pointer");
+    CDNET_REQUIRE(N > 0 && H > 0 && W > 0, "cdnet_fill_remove_small: bad size N=%d H=%d W=%d", N, H, W);
+    CDNET_REQUIRE((size_t)H * W < (1u << 30), "cdnet_fill_remove_small: image too large for 32-bit pixel indices");
+    size_t oL, oAux, oA, oB, oC;
+    const size_t need = cc_ws_layout(N, H, W, &oL, &oAux, &oA, &oB, &oC);
+    if (workspace_bytes < need) {
+        set_error("cdnet_fill_remove_small: workspace %zu < %zu bytes", workspace_bytes, need);
+        return CDNET_E_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    int *L = (int *)(ws + oL), *aux = (int *)(ws + oAux);
+    uint8_t *A = (uint8_t *)(ws + oA);
+    const int plane = H * W;
+    const dim3 gr = grid_rows(N, H, W), br(64, 4);
+    const dim3 gl(lin_grid(plane, 2048), N);
+    cc_init_kernel<0><<<gr, br, 0, st>>>(pred, fg_value, H, W, L);
+    cc_merge_kernel<0, 4><<<gr, br, 0, st>>>(pred, fg_value, H, W, L);
+    cc_flatten_kernel<FLAT_PLAIN><<<gr, br, 0, st>>>(H, W, L, nullptr);
+    fill_mark_border_kernel<<<dim3(cdiv(2 * (H + W), 256), N), 256, 0, st>>>(H, W, L);
+    fill_output_kernel<<<gl, 256, 0, st>>>(pred, fg_value, plane, L, A);
+    if (hipMemsetAsync(aux, 0, (size_t)N * plane * 4, st) != hipSuccess) return check_launch("memset area");
+    cc_init_kernel<1><<<gr, br, 0, st>>>(A, 0, H, W, L);
+    cc_merge_kernel<1, 4><<<gr, br, 0, st>>>(A, 0, H, W, L);
+    cc_flatten_kernel<FLAT_AREA><<<gr, br, 0, st>>>(H, W, L, aux);
+    cc_diag_merge_kernel<<<gr, br, 0, st>>>(A, H, W, min_area, aux, L, small);
+    return check_launch("cdnet_fill_remove_small");
+}
+
+// The last two stages of cdnet_cc_chain alone: measure.label (8-connected, ids in raster order) of a mask as it is - holes stay holes,
+// small components stay - then dilation(disk(radius)).  test_dam.py:561-563 / test.py:292-295 after the 'scale' resize of :551-553.
+// Workspace: cdnet_cc_workspace_bytes(N, H, W).
+extern "C" int cdnet_label8_dilate(const uint8_t *mask, int N, int H, int W, int radius, void *workspace, size_t workspace_bytes,
+                                   int32_t *label, int32_t *final_, int32_t *counts, void *stream) {
+    CDNET_REQUIRE(mask && final_ && counts && workspace, "cdnet_label8_dilate: null pointer");
+    CDNET_REQUIRE(N > 0 && H > 0 && W > 0, "cdnet_label8_dilate: bad size N=%d H=%d W=%d", N, H, W);
+    CDNET_REQUIRE((size_t)H * W < (1u << 30), "cdnet_label8_dilate: image too large for 32-bit pixel indices");
+    CDNET_REQUIRE(radius >= 0 && radius <= 8, "cdnet_label8_dilate: radius %d not in [0,8]", radius);
+    size_t oL, oAux, oA, oB, oC;
+    const size_t need = cc_ws_layout(N, H, W, &oL, &oAux, &oA, &oB, &oC);
+    if (workspace_bytes < need) {
+        set_error("cdnet_label8_dilate: workspace %zu < %zu bytes", workspace_bytes, need);
+        return CDNET_E_WORKSPACE;
+    }
+    const size_t n = (size_t)N * H * W;
+    CDNET_REQUIRE(!label || final_ + n <= label || label + n <= final_, "cdnet_label8_dilate: final overlaps label (the dilation reads neighbours)");
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    int *L = (int *)(ws + oL), *aux = (int *)(ws + oAux), *chunk = (int *)(ws + oC);
+    int32_t *lab = label ? label : (int32_t *)L;             // (label8_raster's labels may alias L)
+    const int rc = cdnet::label8_raster(mask, N, H, W, L, aux, chunk, lab, counts, st);
+    if (rc) return rc;
+    dilate_disk_kernel<<<grid_rows(N, H, W), dim3(64, 4), 0, st>>>(lab, H, W, radius, final_);
+    return check_launch("cdnet_label8_dilate");
+}
+
 // ======================================================================================================
 // Watershed variant of the post-processing (postproc_other.py:15-99, ws branch :36-48)
 //   dist   = per-instance Euclidean distance transform scaled to 0..255 (gen_inst_dst_map :16-27)

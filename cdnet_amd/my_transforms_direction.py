@@ -3,6 +3,7 @@
   LabelEncoding(out_c=3, radius=1, do_direction=0)      :687-885   3-class label + centre-point map + centripetal classes
   label_encoding_batch(label_ch0)                        device API for whole batches (input pipeline on the GPU)
   ToTensor / Normalize                                   :889-1012  (host-side tensor conversion helpers)
+  Scale(size, interpolation=Image.BILINEAR)              :38-65     the 'scale' test transform on PIL images (Pillow itself)
 
 The per-nucleus Python loop of the reference (EDT + numba centre search + whole-image 11x11 convolution per nucleus,
 seconds per sample) is one pass of HBM-bound kernels behind cdnet_label_encoding.
@@ -106,6 +107,27 @@ class LabelEncoding(object):
             out_imgs.append(point[0].cpu().numpy())
             out_imgs.append(direction[0].cpu().numpy().astype(np.int64))
         return tuple(out_imgs)
+
+
+class Scale(object):
+    """Scale(size)(imgs) -> tuple of PIL images (:38-65): an int `size` sets the smaller edge (resize.scaled_size; an image already at that
+    size is passed on as the same object), a (w, h) pair is the new size as is.  Host-side and on Pillow itself, for callers written against
+    the reference; the inference entries resize on the device instead (resize.resize_bilinear: the same bytes)."""
+
+    def __init__(self, size, interpolation=None):
+        from PIL import Image
+        assert isinstance(size, int) or (hasattr(size, '__len__') and len(size) == 2)
+        self.size = size
+        self.interpolation = Image.BILINEAR if interpolation is None else interpolation
+
+    def __call__(self, imgs):
+        from .resize import scaled_size
+        pics = []
+        for img in imgs:
+            w, h = img.size
+            new = scaled_size(w, h, self.size)
+            pics.append(img if new is None else img.resize(new, self.interpolation))
+        return tuple(pics)
 
 
 class ToTensor(object):

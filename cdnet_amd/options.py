@@ -136,6 +136,8 @@ class Options:
             p.add_argument('--label-dir', type=str, default=self.test['label_dir'])
             p.add_argument('--save-dir', type=str, default=self.test['save_dir'])
             p.add_argument('--model-path', type=str, default=self.test['model_path'])
+            p.add_argument('--scale', type=int, default=0,
+                           help="the 'scale' test transform: resize the smaller image edge to N before the network (0 = off)")
         a = p.parse_args(argv)
         self.dataset = a.dataset
         self.model['modelName'] = a.model_name
@@ -167,7 +169,11 @@ class Options:
                 if v != p.get_default(k):
                     te[k] = v
             # options.py:463-472: normalise with mean_std.npy unless the experiment is a "_noNorm" one
-            self.transform['test'] = {'to_tensor': 1}
+            # get_transforms applies the keys in the dict's order (my_transforms_direction.py:1033, 'scale': Scale(x)), so 'scale' goes in
+            # front of 'to_tensor'.  The key comes from --scale N, or from a caller who set transform['test']['scale'] by hand before
+            # parsing - the reference has no flag for it and is used that way
+            scale = a.scale if a.scale else self.transform.get('test', {}).get('scale', 0)
+            self.transform['test'] = {'scale': scale, 'to_tensor': 1} if scale else {'to_tensor': 1}
             ms = '{:s}/{:s}.npy'.format(self.train['data_dir'], self.model['mean_std'])
             if '_noNorm' not in te['save_dir'] and os.path.exists(ms):
                 mean, std = np.load(ms)

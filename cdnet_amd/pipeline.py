@@ -81,7 +81,7 @@ def check_tiles(r):
 
 @torch.no_grad()
 def infer_image(model, image, opt=None, tta=True, all_img_test=1, patch_size=256, overlap=40, classes=9, min_area=20,
-                radius=2, want_stages=False, defer=False, postproc=0, model_mode='Unet_rev1'):
+                radius=2, want_stages=False, defer=False, postproc=0, model_mode='Unet_rev1', restore=None):
     """The reference's per-image inference (test_dam.py:297-563) for one image tensor [3,H,W] float32 on the GPU
     (already ToTensor'd / normalised): the eight dihedral views (TTA) through the network - whole image
     (all_img_test == 1, options.py:35) or 256/40 sliding windows (utils.split_forward_dam) - softmax / gated direction
@@ -94,13 +94,23 @@ def infer_image(model, image, opt=None, tta=True, all_img_test=1, patch_size=256
     read it with postproc.check_postproc_err (test_dam.main does not: the ids come from this package's own labelling and the flood's pass bound
     cannot be reached, so the flag cannot be raised there).  postproc=0: the chain above, unchanged.
     `defer=True`: nothing is read back - no host synchronisation; instead of `count` the device tensor `counts` stays in the result and the
-    reference's constant-DDM assertion is left to the caller (postproc.check_views on `minmax`) - the form test_dam.main pipelines images with."""
+    reference's constant-DDM assertion is left to the caller (postproc.check_views on `minmax`) - the form test_dam.main pipelines images with.
+    `restore=(ori_h, ori_w)` (the 'scale' test transform: `image` was resized for the network, test_dam.py:551-553): holes are filled and small
+    objects removed at the network's size, that mask is resized to (ori_h, ori_w) on the device (resize.resize_mask), then labelled and
+    dilated (postproc.restore_chain): `final`, `counts` and `count` are at the original size, `pred` and `prob_mean` stay at the scaled
+    size, where the reference saves them.  With postproc=1 a ValueError.  None: the path above, unchanged.
+    With 'scale' in opt.transform['test'] and no `restore`, `image` is the transformed image at its ORIGINAL size - what test_dam.main and
+    test_dam.process_image hand over - and the transform's Scale step runs here, on the device (scale_transformed)."""
     from . import postproc as postproc_mod, utils                         # (`postproc` is the reference's option name here)
     if opt is not None:
         tta, all_img_test = opt.test['tta'], opt.all_img_test
         patch_size, overlap = opt.test['patch_size'], opt.test['overlap']
         classes, min_area, radius = opt.direction_classes, opt.post['min_area'], opt.post['radius']
         postproc, model_mode = int(opt.post['postproc']), opt.model['modelName']
+    if (restore is not None or _has_scale(opt)) and int(postproc) == 1:
+        raise ValueError(postproc_mod.SCALE_POSTPROC1)
+    if restore is None and _has_scale(opt):
+        image, restore = scale_transformed(image, opt.transform['test'])
     assert not model.training and image.dim() == 3
     _, H, W = image.shape
     xforms = list(postproc_mod.TTA_XFORMS) if tta else [0]
@@ -122,7 +132,8 @@ def infer_image(model, image, opt=None, tta=True, all_img_test=1, patch_size=256
         utils.split_forward_views(model, image, patch_size, overlap, xforms, classes, out=bufs)
     postproc_mod.probmaps(mask_all.view(V, 3, 1, plane), dir_all.view(V, classes, 1, plane), prob_out=probs, dcm_out=dcms)
     r = postproc_mod.postprocess_views(probs, points, dcms, xforms=xforms, H=H, W=W, classes=classes, min_area=min_area,
-                                   radius=radius, want_stages=want_stages, check=not defer, postproc=int(postproc), model_mode=model_mode)
+                                   radius=radius, want_stages=want_stages, check=not defer, postproc=int(postproc), model_mode=model_mode,
+                                   restore=restore)
     out = {k: (v[0] if torch.is_tensor(v) and v.dim() > 0 and v.shape[0] == 1 else v) for k, v in r.items()}
     if not defer:
         out['count'] = int(r['counts'][0])
@@ -177,7 +188,7 @@ def infer_tiles_mask(model, x, min_area=20, radius=2, post_stream=None, want_sta
 
 @torch.no_grad()
 def infer_image_mask(model, image, opt=None, tta=True, all_img_test=1, patch_size=256, overlap=40, min_area=20, radius=2, postproc=0,
-                     model_mode='UNet', want_prob=False, defer=False):
+                     model_mode='UNet', want_prob=False, defer=False, restore=None):
     """The reference's per-image procedure of test.py:213-296 for one image tensor [3,H,W] float32 on the GPU (already ToTensor'd /
     normalised) and a network with one mask output: the eight dihedral views (TTA) - whole image (all_img_test == 1) or sliding windows
     (utils.split_forward, :627) - stitched into ONE buffer, then ONE launch for every view's softmax, the mean and the class
@@ -187,13 +198,17 @@ def infer_image_mask(model, image, opt=None, tta=True, all_img_test=1, patch_siz
                      :289-290 passes it), then the disk dilation (:295).  The reference passes model_mode = opt.model['modelName'] = 'UNet',
                      and 'UNet' != 'unet' (postproc_other.py:35), so the watershed branch IS taken there: kept.
     Returns dict(final int32 [H,W], pred u8 [H,W] [, prob_mean f32 [K,H,W] with want_prob] [, counts int32 [1] with postproc 0]; `count`
-    unless defer).  `defer=True`: nothing is read back (test.main pipelines images with this form)."""
+    unless defer).  `defer=True`: nothing is read back (test.main pipelines images with this form).
+    `restore=(ori_h, ori_w)` (the 'scale' test transform, test.py:281-283): as for infer_image - `final`, `counts` and `count` at the original
+    size through postproc.restore_chain, `pred` and `prob_mean` at the scaled size; a ValueError with postproc == 1."""
     from . import postproc as postproc_mod, postproc_other, utils          # (`postproc` is the reference's option name here)
     if opt is not None:
         tta, all_img_test = opt.test['tta'], opt.all_img_test
         patch_size, overlap = opt.test['patch_size'], opt.test['overlap']
         min_area, radius, postproc =  opt.post['min_area'], opt.post['radius'], int(opt.post['postproc'])
         model_mode = opt.model['modelName']
+    if restore is not None and int(postproc) == 1:
+        raise ValueError(postproc_mod.SCALE_POSTPROC1)
     assert not model.training and image.dim() == 3
     _, H, W = image.shape
     xforms = list(postproc_mod.TTA_XFORMS) if tta else [0]
@@ -209,7 +224,7 @@ def infer_image_mask(model, image, opt=None, tta=True, all_img_test=1, patch_siz
         lab = postproc_other.process((pred == 1).to(torch.uint8), model_mode, min_size=min_area)
         out = dict(final=postproc_mod.dilate_labels(lab, radius)[0], pred=pred[0])
     else:
-        cc = postproc_mod.cc_chain(pred, 1, min_area, radius)
+        cc = postproc_mod.cc_chain(pred, 1, min_area, radius) if restore is None else postproc_mod.restore_chain(pred, restore, 1, min_area, radius)
         out = dict(final=cc['final'][0], counts=cc['counts'], pred=pred[0])
     if want_prob:
         out['prob_mean'] = m['prob_mean'][0]
@@ -220,3 +235,82 @@ def infer_image_mask(model, image, opt=None, tta=True, all_img_test=1, patch_siz
             f = out['final'].cpu().numpy()
             out['count'] = int(len(np.unique(f[f > 0])))
     return out
+
+
+_NORM = {}
+
+
+def scaled_input(img_u8, transform, device=None):
+    """The test transform of an image with the 'scale' key on the device (test_transform((img,)) of test_dam.py:297 / test.py:213: Scale ->
+    ToTensor -> Normalize).  img_u8: uint8 [H,W,3] tensor, on the host (uploaded as bytes through pinned memory) or already on the device.
+    The image is resized there with Pillow's bilinear filter (resize.resize_bilinear, the size by resize.scaled_size), then converted and
+    normalised with the fp32 operations of the host path (`/ 255.0`, `(x - mean) / std`).  Returns (x float32 [3,h,w] on the device,
+    restore): restore = (H, W) for infer_image / infer_image_mask when the size changed, else None.  Nothing is read back."""
+    from . import resize
+    assert img_u8.dtype == torch.uint8 and img_u8.dim() == 3 and img_u8.shape[2] == 3
+    H, W = int(img_u8.shape[0]), int(img_u8.shape[1])
+    if not img_u8.is_cuda:
+        dev = torch.device('cuda', torch.cuda.current_device()) if device is None else device
+        img_u8 = img_u8.contiguous().pin_memory().to(dev, non_blocking=True)
+    new = resize.scaled_size(W, H, transform['scale']) if 'scale' in transform else None
+    restore = None
+    if new is not None and (new[1], new[0]) != (H, W):
+        img_u8 = resize.resize_bilinear(img_u8, (new[1], new[0]))
+        restore = (H, W)
+    # (tensor / tensor: the device's division by a Python scalar is a multiplication by its reciprocal, one ulp off the host's `/ 255.0`
+    #  for some bytes)
+    if ('255', img_u8.device) not in _NORM:
+        _NORM[('255', img_u8.device)] = torch.full((1,), 255.0, dtype=torch.float32, device=img_u8.device)
+    x = img_u8.permute(2, 0, 1).contiguous().float() / _NORM[('255', img_u8.device)]
+    if 'normalize' in transform:
+        mean, std = transform['normalize']
+        key = (tuple(float(v) for v in mean), tuple(float(v) for v in std), x.device)
+        if key not in _NORM:                                   # (uploaded once: a pageable copy would wait for the images in flight)
+            _NORM[key] = tuple(torch.tensor(v, dtype=torch.float32).view(3, 1, 1).to(x.device) for v in (mean, std))
+        x = (x - _NORM[key][0]) / _NORM[key][1]
+    return x, restore
+
+
+def _has_scale(opt):
+    return opt is not None and 'scale' in getattr(opt, 'transform', {}).get('test', {})
+
+
+def scale_transformed(image, transform):
+    """The Scale step for an image that already went through the rest of the test transform at its original size: image float32 [3,H,W] on
+    the device = (bytes / 255.0 [- mean) / std], as test_dam.main and test_dam.process_image build it.  Pillow resizes bytes, so the bytes
+    are recovered first - round((x * std + mean) * 255) is exact: the float32 error of the round trip is below 1e-4 of a grey level - and
+    then go through scaled_input, whose result has the bits of Scale -> ToTensor -> Normalize on the original bytes.  Returns (x, restore);
+    the image itself and None when Scale leaves its size alone.  Nothing is read back."""
+    from . import resize
+    assert image.is_cuda and image.dtype == torch.float32 and image.dim() == 3 and image.shape[0] == 3
+    H, W = int(image.shape[1]), int(image.shape[2])
+    new = resize.scaled_size(W, H, transform['scale'])
+    if new is None or (new[1], new[0]) == (H, W):
+        return image, None
+    x = image
+    if 'normalize' in transform:
+        mean, std = transform['normalize']
+        key = (tuple(float(v) for v in mean), tuple(float(v) for v in std), x.device)
+        if key not in _NORM:
+            _NORM[key] = tuple(torch.tensor(v, dtype=torch.float32).view(3, 1, 1).to(x.device) for v in (mean, std))
+        x = x * _NORM[key][1] + _NORM[key][0]
+    img_u8 = torch.round(x * 255.0).clamp_(0, 255).to(torch.uint8).permute(1, 2, 0).contiguous()
+    return scaled_input(img_u8, transform)
+
+
+def scale_inputs(image, opt, ori_size=None):
+    """(x float32 [3,h,w] on the device, restore) for the entries' process_image.  A uint8 image [H,W,3] (tensor, numpy array or PIL image:
+    before the test transform) goes through scaled_input, which applies opt.transform['test'] on the device.  A float tensor [3,h,w] is
+    already transformed: with `ori_size=(ori_h, ori_w)` it was also scaled by the caller (the reference's Scale on the host) and the mask
+    is resized back to ori_size; without it, it is at its original size and the Scale step runs here (scale_transformed)."""
+    if not torch.is_tensor(image):
+        image = torch.from_numpy(np.array(image if isinstance(image, np.ndarray) else image.convert('RGB'), dtype=np.uint8))
+    if image.dtype == torch.uint8:
+        return scaled_input(image, opt.transform['test'])
+    x = image.cuda().float()
+    if ori_size is not None:
+        restore = (int(ori_size[0]), int(ori_size[1]))
+        return x, (restore if restore != tuple(x.shape[-2:]) else None)
+    if _has_scale(opt):
+        return scale_transformed(x, opt.transform['test'])
+    return x, None

@@ -17,6 +17,10 @@ TTA_XFORMS = (0, 1, 2, 3, 4, 5, 6, 7)
 
 _LUT_CACHE = {}
 
+# the reference's watershed branch takes pred_inside at the scaled size (test_dam.py:559, test.py:289) and its label map is never resized back
+SCALE_POSTPROC1 = ("--postproc 1 cannot be combined with the 'scale' test transform: the watershed branch labels the prediction at the scaled "
+                   "size, a map that cannot be scored against the ground truth at the original size")
+
 
 def ddm_lut(classes):
     """int8 [classes, classes]: round(cos) between the vectors of two direction classes, with the reference's
@@ -135,6 +139,47 @@ def cc_chain(pred, fg_value=1, min_area=20, radius=2, want_stages=False):
     out = dict(final=final, counts=counts)
     if want_stages:
         out.update(fill=fill, small=small, label=label)
+    return out
+
+
+def label8_dilate(mask, radius=2, want_label=False):
+    """mask uint8 [N,H,W] or [H,W] (non-zero = foreground) -> dict(final int32, counts int32 [N] [, label]): skimage.measure.label
+    (8-connected) then dilation(disk(radius)) - the tail of cc_chain without hole filling and small-object removal, which the reference does
+    not repeat on a mask resized back to the original size (cdnet_label8_dilate; test_dam.py:561-563)."""
+    assert mask.dtype == torch.uint8 and mask.dim() in (2, 3)
+    mask = mask.contiguous()
+    N, H, W = (1,) + tuple(mask.shape) if mask.dim() == 2 else tuple(mask.shape)
+    dev = mask.device
+    nbytes = _lib.load().cdnet_cc_workspace_bytes(N, H, W)
+    ws = _workspace(nbytes, dev)
+    final = torch.empty(mask.shape, dtype=torch.int32, device=dev)
+    counts = torch.empty((N,), dtype=torch.int32, device=dev)
+    label = torch.empty(mask.shape, dtype=torch.int32, device=dev) if want_label else None
+    _lib.call('cdnet_label8_dilate', _lib.ptr(mask), N, H, W, int(radius), _lib.ptr(ws), ws.numel(), _lib.ptr(label), _lib.ptr(final),
+              _lib.ptr(counts), _lib.stream_ptr())
+    out = dict(final=final, counts=counts)
+    if want_label:
+        out['label'] = label
+    return out
+
+
+def restore_chain(pred, size, fg_value=1, min_area=20, radius=2):
+    """The chain of test_dam.py:546-563 with the 'scale' transform: fill holes and remove small objects at the network's size (cc_chain's
+    `small` stage alone: cdnet_fill_remove_small), resize that mask to size = (ori_h, ori_w) with Pillow's bilinear filter and threshold it
+    (:552-553, resize.resize_mask), then label and dilate it as it is (label8_dilate: the reference fills no hole twice).  pred uint8 [N,H,W] -> dict(final int32
+    [N,ori_h,ori_w], counts int32 [N], small uint8 [N,H,W], restored uint8 [N,ori_h,ori_w]); nothing is read back."""
+    from . import resize
+    assert pred.dtype == torch.uint8 and pred.dim() == 3
+    N, H, W = pred.shape
+    pred = pred.contiguous()
+    dev = pred.device
+    ws = _workspace(_lib.load().cdnet_cc_workspace_bytes(N, H, W), dev)
+    small = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
+    _lib.call('cdnet_fill_remove_small', _lib.ptr(pred), int(fg_value), N, H, W, int(min_area), _lib.ptr(ws), ws.numel(), _lib.ptr(small),
+              _lib.stream_ptr())
+    restored = resize.resize_mask(small, (int(size[0]), int(size[1])))
+    out = label8_dilate(restored, radius)
+    out.update(small=small, restored=restored)
     return out
 
 
@@ -274,12 +319,13 @@ def other_chain(pred, model_mode, radius=2):
 
 
 def postprocess_views(probs, points, dcms, xforms=None, H=None, W=None, classes=9, min_area=20, radius=2,
-                      want_stages=False, check=True, postproc=0, model_mode='Unet_rev1'):
+                      want_stages=False, check=True, postproc=0, model_mode='Unet_rev1', restore=None):
     """Everything after get_probmaps for I images with V views each (test_dam.py:445-563).
     postproc=1 (test_dam.py:558-559, --postproc 1): `final` and `counts` come from `other_chain(pred, model_mode, radius)` instead of the
     connected-component chain (min_size 10, the raw prediction: see there); postproc=0 is the chain of :546-563.
     probs f32 [I,V,3,H,W], points f32 [I,V,H,W] (or [I,V,1,H,W]), dcms u8 [I,V,H,W] (or [I,V,1,H,W]); views in
-    their own frame.  Raises AssertionError (like test_dam.py:535) if a view's DDM is constant (0/0 = NaN) - `check=False` leaves that test
+    their own frame.  `restore=(ori_h, ori_w)` (the 'scale' test transform, test_dam.py:551-553): `final` and `counts` come from
+    `restore_chain` at that size; it cannot be combined with postproc=1 (ValueError).  Raises AssertionError (like test_dam.py:535) if a view's DDM is constant (0/0 = NaN) - `check=False` leaves that test
     to the caller (`check_views(r)` on the returned dict): the assertion reads the codes' (min, max) back, a device-to-host synchronisation a
     pipelined caller (test_dam.main: image i + 1 in flight while image i is copied out) postpones."""
     I, V = probs.shape[0], probs.shape[1]
@@ -316,7 +362,11 @@ def postprocess_views(probs, points, dcms, xforms=None, H=None, W=None, classes=
     r = tta_boost_argmax(probs.reshape(I, V, 3 * plane), points.reshape(I, V, plane), codes, minmax, xforms, H, W,
                          want_stages=want_stages)
     if int(postproc) == 1:
+        if restore is not None:
+            raise ValueError(SCALE_POSTPROC1)
         cc = other_chain(r['pred'], model_mode, radius)
+    elif restore is not None:
+        cc = restore_chain(r['pred'], restore, 1, min_area, radius)
     else:
         cc = cc_chain(r['pred'], 1, min_area, radius, want_stages=want_stages)
     r.update(cc)

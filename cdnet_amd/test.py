@@ -2,7 +2,7 @@
 
   get_probmaps(input, model, opt, branch_value)                      test.py:609-636  -> numpy [K,H,W] softmax of the logits
   save_results(header, avg_results, all_results, filename, mode='w') test.py:639-664
-  process_image(model, image, opt)                                   test.py:213-296 for one image -> dict(final, pred, count[, prob_inside])
+  process_image(model, image, opt, ori_size=None)                    test.py:213-296 for one image -> dict(final, pred, count[, prob_inside])
   image_metrics(pred_labeled, gt_instances)                          test.py:316-371: the 22 numbers of one row of <img_dir>_result.txt
   main(argv=None)                                                    test.py:34-606 (command line; images from opt.test['img_dir'])
 
@@ -10,7 +10,11 @@ Models: UNet, UNet_vgg16 (models/model_unet.py), FullNet (inference on csrc/dila
 with three outputs (UNet2RevA1_vgg16, model_unet_MandDandP, HRNet18_rev1) is refused with a ValueError - cdnet_amd.test_dam evaluates those (the
 reference's test.py fails on them too).
 
-Not carried over: the 'scale' test transform (misc.imresize, :281-283); --groundtruth 1 (XML annotations: NotImplementedError, as in test_dam);
+The 'scale' test transform (--scale N, or opt.transform['test']['scale'] set by hand; my_transforms_direction.py:38-65, :281-283) runs on the
+device: the decoded bytes are uploaded, resized with Pillow's bilinear filter (csrc/resize.hip, bit-exact), converted and normalised there; the
+cleaned mask is resized back to the original size before it is labelled and dilated.  Not with --postproc 1 (ValueError).
+
+Not carried over: --groundtruth 1 (XML annotations: NotImplementedError, as in test_dam);
 the experiments/*_logExl_*.csv bookkeeping (:80-92, :459-606); _seg_colored.png (random colours, :382-394); AJI_sklearn (:309-311, :400, :425:
 only printed, and sklearn's jaccard_score with average='samples' on {0, 255} arrays does not run on current scikit-learn).
 """
@@ -77,11 +81,16 @@ def save_results(header, avg_results, all_results, filename, mode='w'):
             file.write('\n')
 
 
-def process_image(model, image, opt):
+def process_image(model, image, opt, ori_size=None):
     """image: float tensor [3,H,W] (after the test transform).  Returns dict(final=np.int32 [H,W] (the dilated label map, :295), pred=np.uint8,
-    count=int[, prob_inside=np.float32 [H,W] when opt.test['save_flag']])."""
+    count=int[, prob_inside=np.float32 [H,W] when opt.test['save_flag']]).
+    With 'scale' in opt.transform['test'] (pipeline.scale_inputs): image is the uint8 image [ori_h,ori_w,3] before the transform (resized,
+    converted and normalised on the device), the transformed float tensor at the original size (the Scale step then runs on the device), or
+    the float tensor the caller scaled already together with ori_size=(ori_h, ori_w); `final` is at the original size (:281-295), `pred` and
+    `prob_inside` at the scaled one."""
     want_prob = bool(opt.test.get('save_flag', True))
-    r = pipeline.infer_image_mask(model, image.cuda().float(), opt, want_prob=want_prob)
+    x, restore = pipeline.scale_inputs(image, opt, ori_size)
+    r = pipeline.infer_image_mask(model, x, opt, want_prob=want_prob, restore=restore)
     out = dict(final=r['final'].cpu().numpy(), pred=r['pred'].cpu().numpy(), count=r['count'])
     if want_prob:
         out['prob_inside'] = r['prob_mean'][min(1, r['prob_mean'].shape[0] - 1)].cpu().numpy()
@@ -137,12 +146,19 @@ def _run_shard(opt, trusted, mine):
     rows = {}
 
     def launch(f):
-        img = np.asarray(Image.open(os.path.join(img_dir, f)).convert('RGB'), dtype=np.float32) / 255.0
-        x = torch.from_numpy(img).permute(2, 0, 1).contiguous()
-        if 'normalize' in opt.transform['test']:
-            mean, std = opt.transform['test']['normalize']
-            x = (x - torch.tensor(mean, dtype=torch.float32).view(3, 1, 1)) / torch.tensor(std, dtype=torch.float32).view(3, 1, 1)
-        r = pipeline.infer_image_mask(model, x.pin_memory().to(dev, non_blocking=True), opt, want_prob=save_flag, defer=True)
+        if 'scale' in opt.transform['test']:
+            # the decoded bytes go up as they are; resize, conversion and normalisation run on the device (pipeline.scaled_input), and the
+            # mask comes back at the original size (restore); the probability map stays at the scaled size, where the reference saves it
+            raw = torch.from_numpy(np.array(Image.open(os.path.join(img_dir, f)).convert('RGB'), dtype=np.uint8))
+            x, restore = pipeline.scaled_input(raw, opt.transform['test'], dev)
+            r = pipeline.infer_image_mask(model, x, opt, want_prob=save_flag, defer=True, restore=restore)
+        else:
+            img = np.asarray(Image.open(os.path.join(img_dir, f)).convert('RGB'), dtype=np.float32) / 255.0
+            x = torch.from_numpy(img).permute(2, 0, 1).contiguous()
+            if 'normalize' in opt.transform['test']:
+                mean, std = opt.transform['test']['normalize']
+                x = (x - torch.tensor(mean, dtype=torch.float32).view(3, 1, 1)) / torch.tensor(std, dtype=torch.float32).view(3, 1, 1)
+            r = pipeline.infer_image_mask(model, x.pin_memory().to(dev, non_blocking=True), opt, want_prob=save_flag, defer=True)
         dev_out = {'final': r['final']}
         if save_flag:
             pm = r['prob_mean']
@@ -210,6 +226,8 @@ def main(argv=None):
         # test.py:331-333: object metrics against the XML annotations (utils.nuclei_accuracy_annotation_object_level)
         raise NotImplementedError('--groundtruth 1 (XML annotation files) is outside the accelerated path: supply instance labels')
     check_model_name(opt.model['modelName'])
+    if 'scale' in opt.transform['test'] and int(opt.post['postproc']) == 1:
+        raise ValueError(postproc.SCALE_POSTPROC1)
     rank, world, made_group = _dist_env()
     if torch.cuda.device_count() > 1:
         torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', '0')) % torch.cuda.device_count())

@@ -1131,6 +1131,42 @@ int cdnet_hausdorff_pairs(const int32_t *true_lab, const int32_t *true_tab, cons
 int cdnet_weight_map_radius(double w0, double sigma);
 int cdnet_weight_map(const int32_t *instances, int H, int W, double w0, double sigma, uint8_t *weight, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * The 'scale' test transform on the device (resize.hip): Pillow's 8-bit bilinear resampler, bit for bit.  Replaces
+ *   my_transforms_direction.py:38-65 (Scale: img.resize((ow, oh), Image.BILINEAR) before the network, through test_dam.py:297 /
+ *   test.py:213) and test_dam.py:551-553 / test.py:281-283 (misc.imresize(pred2 * 255, (ori_h, ori_w), 'bilinear') > 127.5: the mask back).
+ *
+ * cdnet_resize_bilinear: src u8 [N][H][W][C] -> out u8 [N][oh][ow][C]; C = 1 (mode L) or 3 (mode RGB, interleaved as np.asarray gives
+ *   it); any H, W, oh, ow >= 1 (at most 2^20), N <= 65535.  Pointers and rows need byte alignment only.
+ *   Tables (device memory, made by cdnet_amd/resize.py resize_tables in float64 in Pillow's operation order; the device computes no
+ *   coefficient): per axis bounds i32 [out][2] = (first source index, taps) and kk i32 [out][ksize], 22-bit fixed point, with
+ *   ksize = 2 * ceil(max(in / out, 1)) + 1.  An axis whose size does not change takes no tables (NULL, ksize ignored) and runs no pass.
+ *   A pass is clip8((2^21 + sum src * kk) >> 22) in int32; the horizontal pass runs first and is rounded to u8 before the vertical one.
+ *   mask_mode 1 (C = 1): src is {0, 1} and read as v * 255, out is (resized > 127.5) as {0, 1} - test_dam.py:552-553 in one call.
+ *   form: 0 = choose, 1 = LDS form (one launch: a workgroup runs the horizontal pass of the source rows of its 16 x 64 output tile into
+ *   LDS and the vertical pass from there; CDNET_E_ARG when those rows exceed 64 KB of LDS or when one axis alone changes), 2 = two-pass
+ *   form (the horizontal result goes through `workspace`; one launch and no workspace when one axis alone changes).  Equal sizes: a copy.
+ *   workspace: cdnet_resize_workspace_bytes(..., form) bytes (0: may be NULL).
+ * cdnet_resize_last_form: what the calling thread's last successful cdnet_resize_bilinear ran: 0 copy, 1 LDS form, 2 two-pass form.
+ * cdnet_label8_dilate: skimage.measure.label (8-connected, ids in raster order) of mask u8 [N][H][W] (non-zero = foreground), then
+ *   dilation(disk(radius)) - test_dam.py:561-563 / test.py:292-295: the last two stages of cdnet_cc_chain WITHOUT hole filling and
+ *   small-object removal, which the reference does not repeat after the resize.  label i32 (may be NULL), final i32, counts i32 [N]
+ *   (the number of components); workspace: cdnet_cc_workspace_bytes(N, H, W).
+ * cdnet_fill_remove_small: binary_fill_holes then remove_small_objects(min_area) of (pred == fg_value), pred u8 [N][H][W] -> small u8 {0, 1}
+ *   (test_dam.py:546-548, test.py:277-279): the first two stages of cdnet_cc_chain alone, its `small` output bit for bit, without the
+ *   chain's numbering, relabel and dilation - the mask the 'scale' transform resizes back.  workspace: cdnet_cc_workspace_bytes(N, H, W).
+ * Every entry checks its arguments and returns before any HIP call.
+ * ---------------------------------------------------------------------------------------------------- */
+size_t cdnet_resize_workspace_bytes(int N, int H, int W, int C, int oh, int ow, int form);
+int cdnet_resize_bilinear(const uint8_t *src, int N, int H, int W, int C, int oh, int ow, const int32_t *hbounds, const int32_t *hkk,
+                          int hksize, const int32_t *vbounds, const int32_t *vkk, int vksize, int mask_mode, int form, void *workspace,
+                          size_t workspace_bytes, uint8_t *out, void *stream);
+int cdnet_resize_last_form(void);
+int cdnet_fill_remove_small(const uint8_t *pred, int fg_value, int N, int H, int W, int min_area, void *workspace, size_t workspace_bytes,
+                            uint8_t *small, void *stream);
+int cdnet_label8_dilate(const uint8_t *mask, int N, int H, int W, int radius, void *workspace, size_t workspace_bytes, int32_t *label,
+                        int32_t *final_, int32_t *counts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
