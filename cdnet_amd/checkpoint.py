@@ -40,6 +40,93 @@ def save_checkpoint(state, epoch, is_best, save_dir, branch_value, cp_flag):
     return filename
 
 
+# ----------------------------------------------------------------------------------------------------------
+# ImageNet encoder weights: a torchvision vgg16_bn file into the `backbone` of a Unet-family model (model_unet_rev1.py:22-43, where the
+# reference calls models.vgg16_bn(pretrained=True).features).  Nothing is fetched: the file is on disk or it is not used.
+PRETRAINED_SEARCH = ('./pretrained_models/{name}/hub/checkpoints/{name}-*.pth', './pretrained_models/{name}/checkpoints/{name}-*.pth')
+
+
+def find_pretrained(name='vgg16_bn'):
+    """(first file under the reference's TORCH_HOME layout below the working directory or None, the patterns searched)"""
+    import glob
+    patterns = [p.format(name=name) for p in PRETRAINED_SEARCH]
+    for pat in patterns:
+        hits = sorted(glob.glob(pat))
+        if hits:
+            return hits[0], patterns
+    return None, patterns
+
+
+def _backbone_key(k):
+    """(name inside `backbone` or None, dropped unread?) of one key of the source"""
+    if k.startswith('classifier.'):
+        return None, True
+    for prefix in ('features.', 'backbone.'):
+        if k.startswith(prefix):
+            return k[len(prefix):], False
+    return (k, False) if k.split('.', 1)[0].isdigit() else (None, False)
+
+
+def load_encoder_state(backbone, source, strict=True):
+    """load_backbone_weights on the bare encoder module (what get_backbone holds before the model exists)"""
+    if not isinstance(source, dict):
+        path = os.fspath(source)
+        if not os.path.isfile(path):
+            raise FileNotFoundError("no encoder weights file at '{}'".format(path))
+        source = torch.load(path, map_location='cpu', weights_only=True)
+    want = backbone.state_dict()
+    found, dropped, extra, origin = {}, [], [], {}
+    for k, v in source.items():
+        name, drop = _backbone_key(k)
+        if drop:
+            dropped.append(k)
+        elif name is None or name not in want or name in found:
+            extra.append(k)
+        else:
+            found[name], origin[name] = v, k
+    # a file written before BatchNorm counted its batches has no num_batches_tracked at all: nn.BatchNorm2d reads such a file as zero
+    # counters (its _load_from_state_dict, version < 2), and so does this loader; one counter missing among others is a missing key
+    old_bn = not any(k.endswith('num_batches_tracked') for k in found)
+    defaulted = [n for n in want if n.endswith('num_batches_tracked') and n not in found] if old_bn else []
+    missing = [n for n in want if n not in found and n not in defaulted]
+    misshaped = [n for n in found if not torch.is_tensor(found[n]) or tuple(found[n].shape) != tuple(want[n].shape)]
+    if strict:
+        if missing:
+            raise ValueError('encoder weights: missing key backbone.{} ({} more missing)'.format(missing[0], len(missing) - 1))
+        if extra:
+            raise ValueError("encoder weights: unexpected key '{}' ({} more; only classifier.* is dropped)".format(extra[0], len(extra) - 1))
+        if misshaped:
+            n = misshaped[0]
+            raise ValueError("encoder weights: key '{}' has shape {} where backbone.{} has {}".format(
+                origin[n], tuple(getattr(found[n], 'shape', ())), n, tuple(want[n].shape)))
+    # validated: copy (the destinations are the module's own tensors - views of the trainer's flat buffer once a trainer exists)
+    loaded = []
+    with torch.no_grad():
+        for n, dst in want.items():
+            if n in found and n not in misshaped:
+                dst.copy_(found[n].to(dst.dtype))
+                loaded.append('backbone.' + n)
+            elif n in defaulted:
+                dst.zero_()
+    from . import runtime
+    runtime.WEIGHTS_EPOCH[0] += 1          # every packed weight copy and BatchNorm fold is stale (what Trainer.refresh_parameters does)
+    return {'loaded': loaded, 'dropped': dropped + extra, 'missing': ['backbone.' + n for n in missing + misshaped],
+            'zeroed': ['backbone.' + n for n in defaulted]}
+
+
+def load_backbone_weights(model, source, strict=True):
+    """Load a torchvision VGG16-BN file into `model.backbone` (any model of the Unet family).  `source`: a path (read with weights_only) or
+    a state dict, in one of three layouts: the whole torchvision model (`features.N.*`; `classifier.*` is dropped unread), the bare
+    `.features` dict (`N.*`), or this project's `backbone.N.*`.  Every weight, bias, running_mean, running_var and num_batches_tracked of
+    the backbone must be there with the model's shape; with `strict` a missing, unknown or mis-shaped entry raises ValueError naming the key
+    and the model is left untouched (everything is validated before the first copy).  Nothing outside `backbone.` is written.
+    Works before a trainer exists, after one exists (the parameters are then views of its flat buffer: the copy lands there) and on a
+    model that has already run: the weight epoch is bumped, so packs and BatchNorm folds are rebuilt on next use.
+    Returns {'loaded': model keys written, 'dropped': source keys not used, 'missing': model keys left as they were (strict=False only),
+    'zeroed': counters a pre-num_batches_tracked file does not have}."""
+    return load_encoder_state(model.backbone, source, strict=strict)
+
+
 def _numpy_safe_globals():
     """what unpickling a numpy scalar needs: numpy._core.multiarray.scalar, numpy.dtype and the dtype classes of the scalars
     the reference writes (float / int AverageMeter values)"""

@@ -9,11 +9,15 @@ forward() never calls them; every convolution / BatchNorm / ReLU / pool / concat
 kernels of libcdnet_hip.so through cdnet_amd.runtime (NHWC bf16 activations, fp32 accumulation).  There is no
 CPU or eager fallback: forward() on a non-CUDA tensor raises.
 """
+import logging
+
 import torch
 import torch.nn as nn
 
 from ... import _lib, runtime
 from ...runtime import ConvLayer, Src, pooled, pad_offsets
+
+_log = logging.getLogger(__name__)
 
 VGG16_CFG = [64, 64, 'M', 128, 128, 'M', 256, 256, 256, 'M', 512, 512, 512, 'M', 512, 512, 512, 'M']
 
@@ -37,11 +41,26 @@ class revAttention(nn.Module):                # model_unet_rev1.py:8-17 (weights
 
 
 def get_backbone(name, pretrained=True):
-    """model_unet_rev1.py:22-83 for the one backbone the CDNet path uses.  There is no network access for the
-    ImageNet weights: load them through load_state_dict (keys backbone.N.*)."""
+    """model_unet_rev1.py:22-83 for the one backbone the CDNet path uses.  `pretrained`: False - random initialisation; a path - the
+    torchvision vgg16_bn file there (checkpoint.load_backbone_weights' layouts; a missing file is an error); True - the first
+    vgg16_bn-*.pth under the reference's own cache layout below the working directory (./pretrained_models/vgg16_bn/hub/checkpoints/,
+    then ./pretrained_models/vgg16_bn/checkpoints/; :24-25 points TORCH_HOME there), and when there is none one logged line and the
+    random initialisation.  Nothing is ever fetched."""
     if name != 'vgg16_bn':
         raise NotImplementedError('{} backbone model is not implemented so far.'.format(name))
-    return vgg16_bn_features(), ['5', '12', '22', '32', '42'], '43'
+    backbone = vgg16_bn_features()
+    if pretrained:
+        from ... import checkpoint
+        path = None if isinstance(pretrained, int) else pretrained         # (True, or the options' 1)
+        if path is None:
+            path, searched = checkpoint.find_pretrained(name)
+            if path is None:
+                _log.warning('pretrained=True: no ImageNet weights file under %s - the encoder starts from its random initialisation '
+                             '(nothing is downloaded; pass pretrained=<path> / --pretrained-path FILE)', ' or '.join(searched))
+        if path is not None:
+            checkpoint.load_encoder_state(backbone, path)
+            _log.info('encoder %s: ImageNet weights loaded from %s', name, path)
+    return backbone, ['5', '12', '22', '32', '42'], '43'
 
 
 class UpsampleBlock(nn.Module):               # model_unet_rev1.py:86-143, parametric branch
@@ -157,8 +176,29 @@ class Unet(nn.Module):
         self._head_ver = None
 
     def freeze_encoder(self):
+        """model_unet_rev1.py:237-242: requires_grad = False on the backbone, the modules stay in train() - its BatchNorm layers keep
+        normalising with batch statistics and tracking them; its parameters get no gradient and no step (optim.FlatState puts them
+        behind the stepped range, the tape walk of cdnet_amd.trainer stops where no parameter upstream wants a gradient).  A trainer
+        reads the frozen set once, when it is built: freeze first."""
+        if getattr(self, '_trainer_bound', False):
+            raise RuntimeError('freeze_encoder() after a trainer was built for this model: the trainer laid out its flat buffers and '
+                               'optimiser state with the encoder trainable - freeze first, then build the trainer')
         for p in self.backbone.parameters():
             p.requires_grad = False
+
+    def _pretrained_names(self):
+        """the reference's rule (model_unet_rev1.py:307-320): every backbone parameter, but for a replaced ResNet stem ('conv1.weight')"""
+        return {'backbone.' + n for n, _ in self.backbone.named_parameters() if not (self.replaced_conv1 and n == 'conv1.weight')}
+
+    def get_pretrained_parameters(self):
+        """generator over the parameters an ImageNet file fills"""
+        names = self._pretrained_names()
+        return (p for n, p in self.named_parameters() if n in names)
+
+    def get_random_initialized_parameters(self):
+        """generator over every other parameter"""
+        names = self._pretrained_names()
+        return (p for n, p in self.named_parameters() if n not in names)
 
     # parameters that never take part in forward for 3-channel input (SURVEY 2.2a): no gradient, excluded from DDP
     UNUSED_PREFIXES = ('final_conv.', 'child0.', 'child_conv1.')

@@ -8,8 +8,9 @@ kernels (ragged sizes through its pad_offsets path included), the classifier on 
 cdnet_amd.trainer.BackboneUNetTrainer (the plain UNet's loss around the rev1 tape).  There is no CPU fallback.
 
 Only the 'vgg16_bn' backbone is built: the ResNet encoders (UNet_resnet50 / UNet_resnet101) need a 7x7 stride-2 stem, a 3x3 stride-2
-max-pool and strided bottlenecks this library has no kernels for.  `pretrained` is accepted and ignored: nothing is downloaded, ImageNet
-weights come through load_state_dict (keys backbone.N.*).
+max-pool and strided bottlenecks this library has no kernels for.  `pretrained` (False, True or a path) and `encoder_freeze` mean what
+they mean for models/dam/model_unet_rev1.Unet: a torchvision vgg16_bn file from disk into `backbone` (get_backbone; nothing is
+downloaded), and an encoder that gets no gradient and no step.
 """
 import ctypes as C
 
@@ -30,7 +31,7 @@ class Unet(_Rev1):
         if backbone_name != 'vgg16_bn':
             raise NotImplementedError("backbone '{}': only 'vgg16_bn' is built; the ResNet encoders of models/model_unet.py "
                                       '(UNet_resnet50 / UNet_resnet101) are not built'.format(backbone_name))
-        super().__init__(backbone_name=backbone_name, pretrained=False, encoder_freeze=encoder_freeze, classes=classes,
+        super().__init__(backbone_name=backbone_name, pretrained=pretrained, encoder_freeze=encoder_freeze, classes=classes,
                          decoder_filters=decoder_filters, parametric_upsampling=parametric_upsampling,
                          shortcut_features=shortcut_features, decoder_use_batchnorm=decoder_use_batchnorm)
         assert self.final_conv.in_channels == 16, 'cdnet_final_conv1x1_c16 serves the default decoder (16 channels at full resolution)'

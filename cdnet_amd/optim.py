@@ -7,7 +7,8 @@
   moment_scalars(rule, t, lr, wd)     the host scalars of step t of 'radam' / 'radam4s' / 'adamw' / 'ranger', computed in
                                       Python float like the reference's math.sqrt / ** (hhl_utils/radam.py, hhl_utils/ranger.py);
                                       cdnet_moment_step (csrc/optim.hip) takes them as float
-  moment_step_host / sgd_step_host    the two kernels restated over flat fp32 numpy vectors, operation for operation: what
+  adam_step_host,
+  moment_step_host / sgd_step_host    the kernels restated over flat fp32 numpy vectors, operation for operation: what
                                       the tests compare the kernels with, and how a trainer whose buffers live on the CPU steps
   LRSchedule                          the four torch schedulers of utils.py:941-957 over a one-parameter proxy optimiser
 """
@@ -98,6 +99,18 @@ def sgd_step_host(p, g, buf, t, lr, momentum, wd, grad_scale=1.0):
     p[:] = p + f(-lr) * buf
 
 
+def adam_step_host(p, g, m, v, t, lr, betas, eps, wd, grad_scale=1.0):
+    """adam_kernel (csrc/optim.hip) in numpy fp32, in place (the kernel's fused multiply-add of the weight decay through float64)"""
+    f = np.float32
+    p, g, m, v = _np32(p), _np32(g), _np32(m), _np32(v)
+    b1, b2 = f(betas[0]), f(betas[1])
+    bc1, bc2_sqrt = f(1.0 - float(betas[0]) ** t), f(math.sqrt(1.0 - float(betas[1]) ** t))
+    g = (np.float64(f(wd)) * p + np.float64(1.0) * (g * f(grad_scale))).astype(f)
+    m[:] = m + (g - m) * (f(1.0) - b1)
+    v[:] = v * b2 + (f(1.0) - b2) * g * g
+    p[:] = p - (f(lr) / bc1) * (m / (np.sqrt(v) / bc2_sqrt + f(eps)))
+
+
 # the order of cdnet_dam_head_backward's weight block (csrc/head_bwd.hip), which FlatState puts first
 HEAD_PARAMS = ['point_conv.weight', 'direction_conv.weight', 'mask_conv.weight', 'point_conv.bias',
                'direction_conv.bias', 'mask_conv.bias', 'directionAtt.Conv1x1.weight', 'maskAtt.Conv1x1.weight']
@@ -105,8 +118,9 @@ HEAD_PARAMS = ['point_conv.weight', 'direction_conv.weight', 'mask_conv.weight',
 
 class FlatState:
     """fp32 flat buffers: parameters, gradients, Adam moments.  Head parameters first (in the kernel's block layout),
-    then every other parameter that takes part in forward, then the reference's never-used parameters (no gradient,
-    never stepped - torch.optim.Adam skips parameters whose .grad is None).
+    then every other parameter that takes part in forward, then the frozen ones (requires_grad False), then the reference's
+    never-used parameters (no gradient, never stepped - torch.optim.Adam skips parameters whose .grad is None): `n_used` ends
+    in front of the frozen block.
     The state buffers follow the optimiser: M is the first moment (SGD: the momentum buffer), V the second moment (none for SGD),
     S Ranger's slow weights over the stepped parameters (none otherwise)."""
 
@@ -114,9 +128,14 @@ class FlatState:
         # a model that computes on zero-padded parameter copies (HRNet) hands those over; its own parameters stay views
         named = model.trainer_named_parameters() if hasattr(model, 'trainer_named_parameters') else dict(model.named_parameters())
         unused = [n for n in named if n.startswith(tuple(getattr(model, 'UNUSED_PREFIXES', ())))]
-        head = [n for n in HEAD_PARAMS if n in named and n not in unused]
-        rest = [n for n in named if n not in head and n not in unused]
-        self.order = head + rest + unused
+        # frozen parameters (requires_grad False, Unet.freeze_encoder): behind the stepped range like the never-used ones - no gradient, no
+        # step, no weight decay, no moments, no slow weights, in no all-reduce bucket.  Read here, once
+        real = dict(model.named_parameters())          # (the flag lives on the module's own parameters, not on padded compute copies)
+        frozen = [n for n in named if n in real and not real[n].requires_grad and n not in unused]
+        head = [n for n in HEAD_PARAMS if n in named and n not in unused and n not in frozen]
+        rest = [n for n in named if n not in head and n not in unused and n not in frozen]
+        self.frozen = frozen
+        self.order = head + rest + frozen + unused
         sizes = [named[n].numel() for n in self.order]
         total = sum(sizes)
         dev = next(model.parameters()).device
@@ -152,6 +171,8 @@ def stepper(tr, grad_scale):
     on_host = tr.dev.type == 'cpu'
     if rule == 'adam':
         def step(a, b):
+            if on_host:
+                return adam_step_host(f.P[a:b], f.G[a:b], f.M[a:b], f.V[a:b], t, tr.lr, tr.betas, tr.eps, tr.wd, grad_scale)
             _lib.call('cdnet_adam_step', _lib.ptr(f.P[a:b]), _lib.ptr(f.G[a:b]), _lib.ptr(f.M[a:b]), _lib.ptr(f.V[a:b]), b - a, tr.lr,
                       tr.betas[0], tr.betas[1], tr.eps, tr.wd, t, grad_scale, _lib.stream_ptr())
         return step
@@ -228,7 +249,7 @@ def state_dict(tr):
     if f.step_count > 0:
         for i, (n, p) in enumerate(params):
             if f.offsets[n][0] >= f.n_used:
-                continue                                        # the reference's never-used parameters: no gradient, no state
+                continue                                        # frozen and never-used parameters: no gradient, no state (listed in the group)
             st = {} if rule == 'sgd' else {'step': torch.tensor(float(f.step_count)) if rule == 'adam' else int(f.step_count)}
             for key, buf in _state_buffers(tr):
                 st[key] = _gather(tr, buf, n, p)

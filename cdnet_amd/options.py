@@ -48,7 +48,7 @@ class Options:
         self.model = dict(multi_class=True, in_c=3, out_c=3, direction=1, n_layers=6, growth_rate=24, drop_rate=0.1,
                           compress_ratio=0.5, is_hybrid=True, layer_type='basic', mean_std='mean_std', add_weightMap=1,
                           dice=1, boundary_loss=0, mseloss=1, modelName='UNet2RevA1_vgg16', backbone='None', pretrained=1,
-                          LossName='CE1_Dice1')
+                          LossName='CE1_Dice1', pretrained_path='', encoder_freeze=0)
         self.train = dict(branch=5, num_epochs=300, input_size=256, batch_size=8, val_overlap=40, seed=2022, early_stop=7,
                           scheduler='None', step=5, lr=0.001, lr_decay=0.995, weight_decay=1e-4, log_interval=15, workers=8,
                           gpu=[0], alpha=0.0, optimizer='adam', validation=0, checkpoint_freq=100, start_epoch=0,
@@ -100,6 +100,11 @@ class Options:
             p.add_argument('--weight-map', type=int, default=self.model['add_weightMap'])
             p.add_argument('--backbone', type=str, default=self.model['backbone'])
             p.add_argument('--pretrained', type=int, default=self.model['pretrained'])
+            p.add_argument('--pretrained-path', type=str, default=self.model['pretrained_path'],
+                           help='torchvision vgg16_bn weights file for the encoder of the Unet family (overrides the --pretrained 1 search '
+                                'under ./pretrained_models/vgg16_bn; nothing is downloaded)')
+            p.add_argument('--encoder-freeze', type=int, choices=(0, 1), default=self.model['encoder_freeze'],
+                           help='1: the encoder gets no gradient and no optimiser step (its BatchNorm statistics are still tracked)')
             p.add_argument('--LossName', type=str, default=self.model['LossName'])
             p.add_argument('--seed', type=int, default=self.train['seed'])
             p.add_argument('--early_stop', type=int, default=self.train['early_stop'])
@@ -148,6 +153,7 @@ class Options:
             t['num_epochs'], t['input_size'], t['val_overlap'], t['batch_size'] = a.epochs, a.input_size, a.val_overlap, a.batch_size
             m['add_weightMap'], m['backbone'], m['pretrained'], m['LossName'] = a.weight_map, a.backbone, a.pretrained, a.LossName
             t['seed'], t['early_stop'], t['scheduler'], t['step'], t['lr'], t['lr_decay'] = a.seed, a.early_stop, a.scheduler, a.step, a.lr, a.lr_decay
+            m['pretrained_path'], m['encoder_freeze'] = a.pretrained_path, a.encoder_freeze
             self.momentum = a.momentum
             t['optimizer'], t['alpha'], m['dice'], m['boundary_loss'] = a.optimizer, a.alpha, a.dice, a.boundary_loss
             t['log_interval'], t['gpu'], t['branch'], t['checkpoint'], t['validation'] = a.log_interval, list(a.gpu), a.branch, a.checkpoint_path, a.validation

@@ -111,6 +111,9 @@ def main(argv=None):
     if opt.model['modelName'] == 'UNet_vgg16' and opt.model['direction'] != 0:
         raise ValueError("--model-name UNet_vgg16 has one mask output and no direction branch: pass --direction 0 (got {})".format(
             opt.model['direction']))
+    # the model with its ImageNet encoder (--pretrained-path FILE, or --pretrained 1 and a file under ./pretrained_models/vgg16_bn: nothing
+    # is downloaded) and --encoder-freeze; a --checkpoint-path below is loaded over it.  With several ranks nothing more is needed: the
+    # trainer broadcasts rank 0's parameters and buffers when it is built
     model = utils.chooseModel(opt).to(dev)
     plain_unet = opt.model['modelName'] in ('UNet', 'FullNet', 'UNet_vgg16')        # a mask-only network: train_util's loop and scores
     trainer, scheduler = utils.get_optimizer(opt, model, world_size=world)       # train.py:191 (the plain UNet's trainer too)

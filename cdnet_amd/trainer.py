@@ -118,6 +118,13 @@ class Trainer:
         self.world = world_size
         self.bucket = int(float(bucket_mb) * (1 << 20) // 4)
         self.flat = FlatState(model, self.optimizer)
+        # the frozen set (Unet.freeze_encoder), read once: parameters outside the stepped range; _backward_tape finds the layers whose
+        # output no trainable parameter and no input upstream wants a gradient for, and the walk never reaches them
+        frozen = set(self.flat.frozen)
+        self._frozen_ids = frozenset(id(p) for n, p in model.named_parameters() if n in frozen)
+        self._nograd = set()
+        self.narrowed = {}                                 # layer -> output channels its backward-data launch stops at (None: the full launch stays)
+        model._trainer_bound = True                        # (freeze_encoder from here on raises)
         model._head_flat = self.flat.P[:self.flat.n_head] if self.flat.n_head == 855 else None
         self.dev = self.flat.P.device
         self._bufs = {}
@@ -448,6 +455,7 @@ class Trainer:
                 if sx.res is not None:
                     self._readers[id(sx.res)] = self._readers.get(id(sx.res), 0) + 1
             self._producer[id(Rt.out)] = Rt
+        self._nograd = self._no_grad_outputs()
         side = self._side_stream()
         self._side_active = side is not None
         if self._packb_pending:
@@ -480,6 +488,25 @@ class Trainer:
             torch.cuda.current_stream().wait_event(ev)
         else:
             self._flush_reduces()
+
+    def _no_grad_outputs(self):
+        """ids of the stored outputs nothing upstream of which wants a gradient - autograd's rule for requires_grad = False: the layer's own
+        parameters are all frozen and every source is the network's input or such an output itself (a frozen encoder: all of its layers).
+        Their readers' backward-data launches leave those sources out (_input_backward), so no gradient ever arrives and the walk issues
+        no BatchNorm-backward, weight-gradient, backward-data, pool-routing or pack launch for them"""
+        dead = set()
+        if not self._frozen_ids:
+            return dead
+        fr = self._frozen_ids
+        for Rt in self.tape:
+            if isinstance(Rt, runtime.FuseRecord):
+                continue
+            L = Rt.layer
+            ps = (L.weight, L.bias, None if L.bn is None else L.bn.weight, None if L.bn is None else L.bn.bias)
+            if all(p is None or id(p) in fr for p in ps) and \
+                    all(sx.res is None and (sx.is_input or id((sx.grad_to or (sx.x,))[0]) in dead) for sx in Rt.srcs):
+                dead.add(id(Rt.out))
+        return dead
 
     def _fuse_backward(self, R, grads, add):
         """a fuse node: gradient of the (slice of the) output -> one contribution per term"""
@@ -796,6 +823,19 @@ class Trainer:
                 _lib.call(_lib.entry('cdnet_bias_grad', g.dtype == torch.float32), _lib.ptr(g), g.numel() // Cout, Cout,
                           _lib.ptr(ws), ws.numel(), _lib.ptr(L.bias.grad), _lib.stream_ptr())
 
+    def _narrow_ok(self, L, g, wpb, cfgb, gin, H, W, c_live):
+        """may L's backward-data launch stop at output channel c_live?  The pack is laid out output-channel tile first (csrc/pack.hip), so
+        its leading tiles are the pack of the narrower convolution, and an output element's sum does not depend on the other channels -
+        as long as the same kernel family serves both launches (asked once per layer and shape; nothing is launched).  Otherwise the
+        full launch stays"""
+        key = ('narrow', L.name, tuple(g.shape), c_live, runtime.PRECISION, engine.CONV_DEBUG)
+        ok = self._bufs.get(key)
+        if ok is None:
+            q = [engine.conv_forward([Src(g)], wpb, c, cfgb, taps=L.taps, out=gin, H=H, W=W, query_ws=True) for c in (gin.shape[3], c_live)]
+            ok = self._bufs[key] = c_live % 8 == 0 and q[0] == q[1]
+            self.narrowed[L.name] = c_live if ok else None     # (for tools/bench_finetune.py and the tests' printout)
+        return ok
+
     def _input_backward(self, L, srcs, g, H, W, add):
         """g: the gradient w.r.t. the layer's raw output, or a prepared Src (BatchNorm-backward source of the fused path)"""
         if not L.needs_input_grad:
@@ -803,6 +843,10 @@ class Trainer:
         N = g.N if isinstance(g, Src) else g.shape[0]
         Cout = L.Cout
         cin_total = sum(s.C for s in srcs)
+        # sources whose gradient has no reader (a frozen encoder's skip tensors and output, _no_grad_outputs)
+        dead = [id((s.grad_to or (s.x,))[0]) in self._nograd for s in srcs] if self._nograd else [False] * len(srcs)
+        if all(dead):
+            return                                           # (the first decoder block's transposed convolution: nothing to compute)
         # input gradient: forward convolution with the backward-data pack
         wpb, cfgb = L.backward_pack(cin_total, H, W)
         if L.kind == 'conv3s2':
@@ -825,15 +869,20 @@ class Trainer:
                                     bns=(srcs[0].x, P.scale, P.shift, P.save_mean, P.save_invstd, part))
                 self._bn_partials[id(srcs[0].x)] = part
             else:
-                engine.conv_forward([g if isinstance(g, Src) else Src(g)], wpb, cin_total, cfgb, taps=L.taps, out=gin, H=H, W=W)
+                # torch.cat([x, skip]) -> conv2 with a dead skip: the launch computes the output channels [0, x.C) only - the leading
+                # output-channel tiles of the same pack, written into the same wide buffer, so the reader sees the bits and the strides
+                # of the full launch (_narrow_ok); the skip's channels of the buffer are neither written nor read
+                c_live = srcs[0].C if dead == [False, True] and not isinstance(g, Src) and self._narrow_ok(L, g, wpb, cfgb, gin, H, W, srcs[0].C) \
+                    else cin_total
+                engine.conv_forward([g if isinstance(g, Src) else Src(g)], wpb, c_live, cfgb, taps=L.taps, out=gin, H=H, W=W)
         else:
             # space-to-depth view of g [N,2H,2W,Cout]: two row-parity sources of 2*Cout channels each
             gin = self.buf(('din', L.name), (N, H, W, cin_total), runtime.act_dtype())
             views = [Src(g, view=(a * 2 * W * Cout, H, W, 2 * Cout, 4 * W * Cout)) for a in (0, 1)]
             engine.conv_forward(views, wpb, cin_total, cfgb, taps=(9 if L.kind == 'convT4' else 1), out=gin, H=H, W=W)
         coff = 0
-        for s in srcs:
-            if s.is_input:
+        for s, dead_s in zip(srcs, dead):
+            if s.is_input or dead_s:
                 coff += s.C
                 continue
             tgt, pool = s.grad_to or (s.x, int(s.pool))          # a materialised max-pool hands its gradient to the producer

@@ -17,20 +17,25 @@ from . import _lib
 
 def chooseModel(opt):
     name = opt.model['modelName']
+    # the reference hard-codes pretrained=True (an ImageNet download, utils.py:822-875); here the training entry passes --pretrained-path FILE
+    # or, with --pretrained 1, lets get_backbone look for the file under ./pretrained_models (nothing is fetched).  The test entries load
+    # a checkpoint over the model anyway: no search there, and nothing to freeze
+    train = getattr(opt, 'isTrain', False)                 # (a bare options object, as the tools build: the test entries' behaviour)
+    pretrained = (opt.model.get('pretrained_path') or bool(opt.model.get('pretrained', 0))) if train else False
+    freeze = bool(opt.model.get('encoder_freeze', 0)) if train else False
     if name == 'UNet':
         from .models.unet import UNet
         return UNet(num_classes=opt.model['out_c'], in_channels=opt.model['in_c'])
     if name == 'UNet2RevA1_vgg16':
         from .models.dam.model_unet_rev1 import Unet
-        # the reference hard-codes pretrained=True (ImageNet download); weights are supplied via load_state_dict here
-        return Unet(backbone_name='vgg16_bn', pretrained=False, encoder_freeze=False, classes=opt.model['out_c'])
+        return Unet(backbone_name='vgg16_bn', pretrained=pretrained, encoder_freeze=freeze, classes=opt.model['out_c'])
     if name == 'UNet_vgg16':                         # utils.py:822-824 (the ResNet backbones of :825-830 are not built)
         from .models.model_unet import Unet
-        return Unet(backbone_name='vgg16_bn', pretrained=False, encoder_freeze=False, classes=opt.model['out_c'])
+        return Unet(backbone_name='vgg16_bn', pretrained=pretrained, encoder_freeze=freeze, classes=opt.model['out_c'])
     if name in ('model_unet_MandD', 'model_unet_MandD4', 'model_unet_MandD16', 'model_unet_MandDandP'):      # utils.py:857-874
         import importlib
         mod = importlib.import_module('.models.dam.' + name, __package__)
-        return mod.Unet(backbone_name='vgg16_bn', pretrained=False, encoder_freeze=False, classes=opt.model['out_c'])
+        return mod.Unet(backbone_name='vgg16_bn', pretrained=pretrained, encoder_freeze=freeze, classes=opt.model['out_c'])
     if name == 'HRNet18_rev1':                       # utils.py:880-882
         from .models.dam.seg_hrnet_rev1 import HighResolutionNet
         return HighResolutionNet(opt)
