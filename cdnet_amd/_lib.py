@@ -246,6 +246,8 @@ SIGNATURES = {
     'cdnet_augment_batch': (_i, [_vp, _vp, _i, _i, _vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     'cdnet_augment_geo_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'cdnet_augment_batch_geo': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    'cdnet_augment_batch_c': (_i, [_vp, _vp, _i, _i, _vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i]),
+    'cdnet_augment_batch_geo_c': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i]),
     'cdnet_label_encoding': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     'cdnet_weight_map_radius': (_i, [C.c_double, C.c_double]),
     'cdnet_weight_map': (_i, [_vp, _i, _i, C.c_double, C.c_double, _vp, _vp]),

@@ -7,6 +7,10 @@
                                       restated OpenCV geometry; it serves TileBatches(device='cpu') and checks the device path
   Recipe                              which steps run, the elastic parameters (alpha, sigma, alpha_affine) and the crop size
 
+Grey-scale sources (img u8 [H, W], Pillow's mode L) take the same three functions: cdnet_augment_batch_c / cdnet_augment_batch_geo_c with
+channels = 1.  The parameters are drawn alike for both channel counts; on L the Color factor is drawn and ignored (Pillow's Color of an L
+image is the identity).
+
 Per sample, on the whole source image, in the order options.py:331-347 fixes: [random_resize] -> random_color -> [random_affine] ->
 horizontal / vertical flip -> random_elastic (random affine, then a Gaussian-smoothed displacement field) -> [random_rotation] ->
 random_chooseAug -> random_crop; the bracketed steps are off in the default recipe and go through cdnet_augment_batch_geo.  The contract is the same distributions and the same operation
@@ -260,7 +264,7 @@ def field_window(p, H, W, size):
 
 
 def colour_chain(img, color):
-    """random_color (my_transforms_direction.py:161-179) with given factors, through PIL itself"""
+    """random_color (my_transforms_direction.py:161-179) with given factors, through PIL itself (img u8 [H, W, 3], or [H, W]: mode L)"""
     from PIL import Image, ImageEnhance
     im = Image.fromarray(np.ascontiguousarray(img))
     for enh, f in zip((ImageEnhance.Color, ImageEnhance.Brightness, ImageEnhance.Contrast, ImageEnhance.Sharpness), color):
@@ -301,9 +305,9 @@ def _gather(planes, Y, X, ok):
 
 
 def augment_host(img, weight, label, p, size, field=None, origin=None):
-    """one sample through the whole chain on the host.  img u8 [H, W, 3], weight u8 [H, W], label u8 / i32 [H, W]; `field` (f32 [2, E, E],
+    """one sample through the whole chain on the host.  img u8 [H, W, 3] or [H, W] (mode L), weight u8 [H, W], label u8 / i32 [H, W]; `field` (f32 [2, E, E],
     as augment_batch returns it) replaces the host's own dx, dy when given, `origin` = the (row, column) of its first element in the
-    (resized) image (default: the crop origin - 6, the window without a rotation).  Returns the crop (img u8 [s, s, 3], weight u8 [s, s],
+    (resized) image (default: the crop origin - 6, the window without a rotation).  Returns the crop (img u8 [s, s, 3] or [s, s], weight u8 [s, s],
     label [s, s]) before the division by 255."""
     planes = [img, weight, label]
     if p.Hr:                                     # random_resize: OpenCV's nearest index rule
@@ -311,14 +315,15 @@ def augment_host(img, weight, label, p, size, field=None, origin=None):
         planes = [a[iy][:, ix] for a in planes]
     H, W = planes[1].shape
     im = colour_chain(planes[0], p.color)
-    planes = [im[..., c] for c in range(3)] + planes[1:]
+    nc = 1 if im.ndim == 2 else 3
+    planes = ([im] if nc == 1 else [im[..., c] for c in range(3)]) + planes[1:]
     if p.paff is not None:                       # random_affine: through PIL itself, per plane (my_transforms_direction.py:216-218)
         from PIL import Image
         rgb = Image.fromarray(np.ascontiguousarray(im)).transform((W, H), Image.AFFINE, p.paff)
         rest = [np.asarray(Image.fromarray(np.ascontiguousarray(a)).transform((W, H), Image.AFFINE, p.paff)).astype(a.dtype)
-                for a in planes[3:]]
+                for a in planes[nc:]]
         rgb = np.asarray(rgb)
-        planes = [rgb[..., c] for c in range(3)] + rest
+        planes = ([rgb] if nc == 1 else [rgb[..., c] for c in range(3)]) + rest
     if p.hflip:
         planes = [a[:, ::-1] for a in planes]
     if p.vflip:
@@ -344,9 +349,9 @@ def augment_host(img, weight, label, p, size, field=None, origin=None):
     warped = _gather(planes, Y, X, ok & inside)
     if p.rinv is not None:                       # random_rotation: warpAffine nearest, zero border
         warped = _gather(warped, *warp_source(p.rinv, H, W, qy, qx))
-    im = apply_filter(np.stack(warped[:3], -1), p.filter)
+    im = apply_filter(warped[0] if nc == 1 else np.stack(warped[:3], -1), p.filter)
     s = size
-    out = [im, warped[3], warped[4]]
+    out = [im, warped[nc], warped[nc + 1]]
     out = [a[p.y0:p.y0 + s, p.x0:p.x0 + s] for a in out]
     if out[1].shape != (s, s):
         out = [np.pad(a, ((0, s - a.shape[0]), (0, s - a.shape[1])) + ((0, 0),) * (a.ndim - 2)) for a in out]
@@ -356,11 +361,15 @@ def augment_host(img, weight, label, p, size, field=None, origin=None):
 # ---------------------------------------------------------------------------------------------------- device path
 
 class Source:
-    """one source image resident on the device: img u8 [H, W, 3], weight u8 [H, W], label u8 [H, W] (channel 0) or i32 [H, W]"""
+    """one source image resident on the device: img u8 [H, W, 3] or [H, W] (mode L), weight u8 [H, W], label u8 [H, W] (channel 0) or i32 [H, W]"""
 
     def __init__(self, img, weight, label, dev):
         self.H, self.W = weight.shape[:2]
-        self.img = torch.from_numpy(np.array(img, dtype=np.uint8, order='C')).to(dev)          # (a copy: PIL arrays are read-only)
+        img = np.array(img, dtype=np.uint8, order='C')                                         # (a copy: PIL arrays are read-only)
+        if not (img.shape == (self.H, self.W) or img.shape == (self.H, self.W, 3)):
+            raise ValueError('Source: img is u8 [H, W, 3] or [H, W] of the weight map\'s size {} x {}, got {}'.format(self.H, self.W, img.shape))
+        self.channels = 1 if img.ndim == 2 else 3
+        self.img = torch.from_numpy(img).to(dev)
         self.weight = torch.from_numpy(np.array(weight if weight.ndim == 2 else weight[:, :, 0], dtype=np.uint8, order='C')).to(dev)
         lab = label if label.ndim == 2 else label[:, :, 0]
         self.label_i32 = lab.dtype != np.uint8
@@ -394,7 +403,8 @@ def _geo_table(sources, params, size):
 def augment_batch(sources, params, size, normalize=None, want_field=False, want_origin=False):
     """the batch on the device (one call of cdnet_augment_batch, or of cdnet_augment_batch_geo when a sample has one of the optional
     steps; csrc/augment.hip).  sources: [Source], params: [Params].
-    Returns (image f32 [B, 3, s, s], weight u8 [B, s, s], label u8 / i32 [B, s, s], varied i32 [B][, field f32 [B, 2, E, E]][, origin
+    Sources of mode L ([H, W] images, all of the batch alike) go through the same calls' `_c` forms with channels = 1.
+    Returns (image f32 [B, 3, s, s] ([B, 1, s, s] on L; `normalize` then gives one mean and one std, or more of which the first is read), weight u8 [B, s, s], label u8 / i32 [B, s, s], varied i32 [B][, field f32 [B, 2, E, E]][, origin
     i64 [B, 2]]); varied[b] == 0: the label crop holds one value (re-draw).  The field window's edge E is s + 12 and its origin (y0 - 6,
     x0 - 6) unless the batch holds a rotation.  want_field keeps its five values; the origins, each sample's (row, column), are a
     separate request (want_origin) so that earlier callers of want_field stay as they are."""
@@ -402,12 +412,15 @@ def augment_batch(sources, params, size, normalize=None, want_field=False, want_
     assert B == len(params) and B > 0
     dev = sources[0].img.device
     label_i32 = int(sources[0].label_i32)
+    nc = sources[0].channels
+    if any(src.channels != nc for src in sources):
+        raise ValueError('augment_batch: RGB and L sources in one batch')
     table = (AugSample * B)()
     rmax = 0
     for t, src, p in zip(table, sources, params):
         t.minv[:] = p.minv
         t.img, t.weight, t.label = src.img.data_ptr(), src.weight.data_ptr(), src.label.data_ptr()
-        t.H, t.W, t.img_stride, t.weight_stride, t.label_stride, t.label_i32 = src.H, src.W, 3 * src.W, src.W, src.W, int(src.label_i32)
+        t.H, t.W, t.img_stride, t.weight_stride, t.label_stride, t.label_i32 = src.H, src.W, nc * src.W, src.W, src.W, int(src.label_i32)
         t.color[:] = p.color
         t.hflip, t.vflip, t.filter, t.y0, t.x0 = p.hflip, p.vflip, p.filter, p.y0, p.x0
         t.alpha, t.sigma, t.seed = p.alpha, p.sigma, p.seed
@@ -422,20 +435,22 @@ def augment_batch(sources, params, size, normalize=None, want_field=False, want_
         ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
         _WS[key] = ws
     table_dev = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
-    image = torch.empty((B, 3, size, size), dtype=torch.float32, device=dev)
+    image = torch.empty((B, nc, size, size), dtype=torch.float32, device=dev)
     weight = torch.empty((B, size, size), dtype=torch.uint8, device=dev)
     label = torch.empty((B, size, size), dtype=torch.int32 if label_i32 else torch.uint8, device=dev)
     varied = torch.empty((B,), dtype=torch.int32, device=dev)
     field = torch.zeros((B, 2, FS, FS), dtype=torch.float32, device=dev) if want_field else None
-    norm = (C.c_float * 6)(*(list(normalize[0]) + list(normalize[1]))) if normalize else None
+    norm = (C.c_float * (2 * nc))(*(list(normalize[0])[:nc] + list(normalize[1])[:nc])) if normalize else None
+    grey = () if nc == 3 else (nc,)                 # RGB keeps the calls it always made
+    suffix = '_c' if grey else ''
     if geo is None:
-        _lib.call('cdnet_augment_batch', _lib.ptr(table_dev), table, B, size, norm, _lib.ptr(ws), ws.numel(), _lib.ptr(image),
-                  _lib.ptr(weight), _lib.ptr(label), label_i32, _lib.ptr(varied), _lib.ptr(field), _lib.stream_ptr())
+        _lib.call('cdnet_augment_batch' + suffix, _lib.ptr(table_dev), table, B, size, norm, _lib.ptr(ws), ws.numel(), _lib.ptr(image),
+                  _lib.ptr(weight), _lib.ptr(label), label_i32, _lib.ptr(varied), _lib.ptr(field), _lib.stream_ptr(), *grey)
         origin = np.array([(p.y0 - HALO, p.x0 - HALO) for p in params], np.int64)
     else:
         geo_dev = torch.frombuffer(bytearray(bytes(geo)), dtype=torch.uint8).to(dev)
-        _lib.call('cdnet_augment_batch_geo', _lib.ptr(table_dev), table, _lib.ptr(geo_dev), geo, FS, B, size, norm, _lib.ptr(ws), ws.numel(),
-                  _lib.ptr(image), _lib.ptr(weight), _lib.ptr(label), label_i32, _lib.ptr(varied), _lib.ptr(field), _lib.stream_ptr())
+        _lib.call('cdnet_augment_batch_geo' + suffix, _lib.ptr(table_dev), table, _lib.ptr(geo_dev), geo, FS, B, size, norm, _lib.ptr(ws), ws.numel(),
+                  _lib.ptr(image), _lib.ptr(weight), _lib.ptr(label), label_i32, _lib.ptr(varied), _lib.ptr(field), _lib.stream_ptr(), *grey)
         origin = np.array([(g.fy0, g.fx0) for g in geo], np.int64)
     out = (image, weight, label, varied) + ((field,) if want_field else ()) + ((origin,) if want_origin else ())
     return out

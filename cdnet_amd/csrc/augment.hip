@@ -67,10 +67,23 @@ __device__ inline uint32_t clip8(float v) {
     return (uint32_t)(uint8_t)v;
 }
 
-// Color then Brightness of one source pixel (u8 RGB)
+// Color then Brightness of one source pixel (u8 RGB; NC = 1, mode L: Pillow's Color degenerate of an L image is the image itself, so
+// that blend returns the pixel for every factor and only Brightness is left)
+template <int NC>
 __device__ inline void color_bright(const uint8_t *p, const float *f, uint32_t *o) {
-    const uint32_t g = luma(p[0], p[1], p[2]);
-    for (int c = 0; c < 3; ++c) o[c] = blend(0, blend(g, p[c], f[0]), f[1]);
+    if constexpr (NC == 1) {
+        o[0] = blend(0, p[0], f[1]);
+    } else {
+        const uint32_t g = luma(p[0], p[1], p[2]);
+        for (int c = 0; c < 3; ++c) o[c] = blend(0, blend(g, p[c], f[0]), f[1]);
+    }
+}
+
+// what the Contrast degenerate averages: L of the brightness-adjusted pixel (mode L: the plane itself, no RGB -> L weights)
+template <int NC>
+__device__ inline uint32_t stat_value(const uint32_t *o) {
+    if constexpr (NC == 1) return o[0];
+    else return luma(o[0], o[1], o[2]);
 }
 
 // OpenCV 4 warpAffine, nearest: fixed point with AB_BITS = 10 and a half-step rounding delta (the host validates with the same function)
@@ -146,35 +159,37 @@ template <bool GEO> __device__ inline int raw_x(const Ctx &c, int x) {
 }
 
 // Color, Brightness, Contrast (degenerate `mean`) of stored pixel (y, x)
+template <int NC>
 __device__ inline void ccb(const cdnet_aug_sample &s, int y, int x, uint32_t mean, uint32_t *o) {
-    uint32_t t[3];
-    color_bright(s.img + (size_t)y * s.img_stride + 3 * x, s.color, t);
-    for (int c = 0; c < 3; ++c) o[c] = blend(mean, t[c], s.color[2]);
+    uint32_t t[NC];
+    color_bright<NC>(s.img + (size_t)y * s.img_stride + NC * x, s.color, t);
+    for (int c = 0; c < NC; ++c) o[c] = blend(mean, t[c], s.color[2]);
 }
 
 // the whole random_color chain at pixel (y, x): Sharpness blends with SMOOTH ([1 1 1; 1 5 1; 1 1 1] / 13) of the Contrast image,
 // whose outermost rows and columns are copied.  With GEO the pixel, its neighbours and the copied edge are the virtual image's: three
 // row and three column maps serve the nine reads.
-template <bool GEO>
+template <bool GEO, int NC>
 __device__ inline void color_chain(const Ctx &cx, int y, int x, uint32_t mean, uint32_t *o) {
     const cdnet_aug_sample &s = cx.s;
-    uint32_t mid[3];
-    ccb(s, raw_y<GEO>(cx, y), raw_x<GEO>(cx, x), mean, mid);
-    uint32_t deg[3] = {mid[0], mid[1], mid[2]};
+    uint32_t mid[NC];
+    ccb<NC>(s, raw_y<GEO>(cx, y), raw_x<GEO>(cx, x), mean, mid);
+    uint32_t deg[NC];
+    for (int c = 0; c < NC; ++c) deg[c] = mid[c];
     if (y >= 1 && y < s.H - 1 && x >= 1 && x < s.W - 1) {
         const int my[3] = {raw_y<GEO>(cx, y - 1), raw_y<GEO>(cx, y), raw_y<GEO>(cx, y + 1)};
         const int mx[3] = {raw_x<GEO>(cx, x - 1), raw_x<GEO>(cx, x), raw_x<GEO>(cx, x + 1)};
-        uint32_t nb[3][3][3];
+        uint32_t nb[3][3][NC];
         for (int dy = -1; dy <= 1; ++dy)
             for (int dx = -1; dx <= 1; ++dx) {
                 if (dy == 0 && dx == 0) {
-                    for (int c = 0; c < 3; ++c) nb[1][1][c] = mid[c];
+                    for (int c = 0; c < NC; ++c) nb[1][1][c] = mid[c];
                 } else {
-                    ccb(s, my[dy + 1], mx[dx + 1], mean, nb[dy + 1][dx + 1]);
+                    ccb<NC>(s, my[dy + 1], mx[dx + 1], mean, nb[dy + 1][dx + 1]);
                 }
             }
         const float k1 = 1.0f / 13.0f, k5 = 5.0f / 13.0f;
-        for (int c = 0; c < 3; ++c) {
+        for (int c = 0; c < NC; ++c) {
             float ss = 0.5f;
             for (int r = 2; r >= 0; --r) {          // Pillow sums the row below first
                 const float kc = r == 1 ? k5 : k1;
@@ -183,7 +198,7 @@ __device__ inline void color_chain(const Ctx &cx, int y, int x, uint32_t mean, u
             deg[c] = clip8(ss);
         }
     }
-    for (int c = 0; c < 3; ++c) o[c] = blend(deg[c], mid[c], s.color[3]);
+    for (int c = 0; c < NC; ++c) o[c] = blend(deg[c], mid[c], s.color[3]);
 }
 
 // pixel q of the last geometric step's output -> pixel of the unflipped, uncoloured (with GEO: virtual resized) image; false: outside
@@ -233,7 +248,7 @@ __device__ inline int label_at(const cdnet_aug_sample &s, int y, int x) {
 
 // with GEO the sum is over the virtual resized image (Contrast's mean is taken after random_resize): a workgroup walks whole rows, so
 // the row map is computed once per row
-template <bool GEO>
+template <bool GEO, int NC>
 __global__ void __launch_bounds__(256) aug_stats_kernel(const cdnet_aug_sample *samples, const cdnet_aug_geo *geo, unsigned long long *partial,
                                                         int32_t *varied) {
     const int b = blockIdx.y;
@@ -245,9 +260,9 @@ __global__ void __launch_bounds__(256) aug_stats_kernel(const cdnet_aug_sample *
         for (int y = blockIdx.x; y < s.H; y += gridDim.x) {
             const uint8_t *row = s.img + (size_t)raw_y<true>(c, y) * s.img_stride;
             for (int x = threadIdx.x; x < s.W; x += blockDim.x) {
-                uint32_t o[3];
-                color_bright(row + 3 * raw_x<true>(c, x), s.color, o);
-                acc += luma(o[0], o[1], o[2]);
+                uint32_t o[NC];
+                color_bright<NC>(row + NC * raw_x<true>(c, x), s.color, o);
+                acc += stat_value<NC>(o);
             }
         }
     } else {
@@ -255,9 +270,9 @@ __global__ void __launch_bounds__(256) aug_stats_kernel(const cdnet_aug_sample *
         const size_t n = (size_t)s.H * s.W;
         for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
             const int y = (int)(i / s.W), x = (int)(i % s.W);
-            uint32_t o[3];
-            color_bright(s.img + (size_t)y * s.img_stride + 3 * x, s.color, o);
-            acc += luma(o[0], o[1], o[2]);
+            uint32_t o[NC];
+            color_bright<NC>(s.img + (size_t)y * s.img_stride + NC * x, s.color, o);
+            acc += stat_value<NC>(o);
         }
     }
     __shared__ unsigned long long red[256];
@@ -365,7 +380,7 @@ __device__ inline uint8_t box5(uint32_t a, uint32_t b, uint32_t c, uint32_t d, u
     return (uint8_t)((((b + c + d) * BOX_WW) + (a + e) * BOX_FW + (1u << 23)) >> 24);
 }
 
-template <bool GEO>
+template <bool GEO, int NC>
 __global__ void __launch_bounds__(256) aug_tile_kernel(const cdnet_aug_sample *samples, const cdnet_aug_geo *geo, int size, int FS, int tiles_x,
                                                        const unsigned long long *partial, const float *field, Norm norm, float *image,
                                                        uint8_t *weight, void *label, int label_i32, int32_t *varied) {
@@ -373,7 +388,7 @@ __global__ void __launch_bounds__(256) aug_tile_kernel(const cdnet_aug_sample *s
     const Ctx ctx = make_ctx<GEO>(samples, geo, b, FS);
     const cdnet_aug_sample &s = ctx.s;                  // H, W: the image every step below works in (with GEO the virtual resized one)
     const int ty0 = (blockIdx.x / tiles_x) * T, tx0 = (blockIdx.x % tiles_x) * T;     // tile origin in the crop
-    __shared__ uint8_t A[3][WN][WN], Bf[3][WN][WN];
+    __shared__ uint8_t A[NC][WN][WN], Bf[NC][WN][WN];
     __shared__ uint32_t mean_s;
     __shared__ int ref_label;
     const float *fx = field + (size_t)b * 2 * FS * FS, *fy = fx + (size_t)FS * FS;
@@ -397,10 +412,10 @@ __global__ void __launch_bounds__(256) aug_tile_kernel(const cdnet_aug_sample *s
         const int qy = s.y0 + cy, qx = s.x0 + cx;
         if (qy < 0 || qy >= s.H || qx < 0 || qx >= s.W) continue;        // never read: the filters clamp to the image
         int ty, tx;
-        uint32_t v[3] = {0, 0, 0};
+        uint32_t v[NC] = {};
         const bool in = trace<GEO>(ctx, qy, qx, fx, fy, ty, tx);
-        if (in) color_chain<GEO>(ctx, ty, tx, mean, v);
-        for (int c = 0; c < 3; ++c) A[c][i][j] = (uint8_t)v[c];
+        if (in) color_chain<GEO, NC>(ctx, ty, tx, mean, v);
+        for (int c = 0; c < NC; ++c) A[c][i][j] = (uint8_t)v[c];
         if (i >= HALO && i < HALO + T && j >= HALO && j < HALO + T && cy < size && cx < size) {
             const size_t o = ((size_t)b * size + cy) * size + cx;
             const int my = in ? raw_y<GEO>(ctx, ty) : 0, mx = in ? raw_x<GEO>(ctx, tx) : 0;
@@ -442,7 +457,7 @@ __global__ void __launch_bounds__(256) aug_tile_kernel(const cdnet_aug_sample *s
                 const int y = wr0 + i, x = wc0 + j;
                 if (y < 0 || y >= s.H || x < 0 || x >= s.W) continue;
                 if (i - HALO + ty0 >= size + HALO || j - HALO + tx0 >= size + HALO) continue;
-                for (int c = 0; c < 3; ++c) {
+                for (int c = 0; c < NC; ++c) {
                     uint32_t t[5];
                     for (int d = -2; d <= 2; ++d) {
                         if (horiz) t[d + 2] = src[c][i][clampi(x + d, 0, s.W - 1) - wc0];
@@ -462,13 +477,13 @@ __global__ void __launch_bounds__(256) aug_tile_kernel(const cdnet_aug_sample *s
         const int cy = ty0 + idx / T, cx = tx0 + idx % T;
         if (cy >= size || cx >= size) continue;
         const int y = wr0 + i, x = wc0 + j;
-        uint32_t v[3] = {0, 0, 0};
+        uint32_t v[NC] = {};
         if (y < s.H && x < s.W) {
-            for (int c = 0; c < 3; ++c) v[c] = fin[c][i][j];
+            for (int c = 0; c < NC; ++c) v[c] = fin[c][i][j];
             if (s.filter == 1 && y >= 2 && y < s.H - 2 && x >= 2 && x < s.W - 2) {
                 // BLUR: the 5 x 5 ring / 16, Pillow's order (row below first, left to right), 2-px image edge copied
                 const float k = 1.0f / 16.0f;
-                for (int c = 0; c < 3; ++c) {
+                for (int c = 0; c < NC; ++c) {
                     float ss = 0.5f;
                     for (int dy = 2; dy >= -2; --dy) {
                         const bool ring = dy == 2 || dy == -2;
@@ -480,7 +495,7 @@ __global__ void __launch_bounds__(256) aug_tile_kernel(const cdnet_aug_sample *s
                 }
             } else if (s.filter == 3) {
                 // MedianFilter(3) of the edge-replicated image
-                for (int c = 0; c < 3; ++c) {
+                for (int c = 0; c < NC; ++c) {
                     uint32_t m[9];
                     int n = 0;
                     for (int dy = -1; dy <= 1; ++dy)
@@ -493,20 +508,39 @@ __global__ void __launch_bounds__(256) aug_tile_kernel(const cdnet_aug_sample *s
                 }
             }
         }
-        for (int c = 0; c < 3; ++c) {
+        for (int c = 0; c < NC; ++c) {
             float f = (float)v[c] / 255.0f;
             if (norm.on) f = (f - norm.mean[c]) / norm.std[c];
-            image[((size_t)b * 3 + c) * plane + (size_t)cy * size + cx] = f;
+            image[((size_t)b * NC + c) * plane + (size_t)cy * size + cx] = f;
         }
     }
 }
 
 constexpr int FIELD_EDGE_MAX = 16384;
 
-// the entry behind both ABI calls: geo == nullptr is the default recipe (field window: crop + HALO at the crop origin)
+// the stats launch and the tile launch of one batch for a plane count
+template <int NC>
+void launch_stats(const cdnet_aug_sample *samples, const cdnet_aug_geo *geo, int B, unsigned long long *partial, int32_t *varied, hipStream_t st) {
+    if (geo) aug_stats_kernel<true, NC><<<dim3(NSTAT, B), 256, 0, st>>>(samples, geo, partial, varied);
+    else aug_stats_kernel<false, NC><<<dim3(NSTAT, B), 256, 0, st>>>(samples, geo, partial, varied);
+}
+
+template <int NC>
+void launch_tile(const cdnet_aug_sample *samples, const cdnet_aug_geo *geo, int B, int size, int FS, const unsigned long long *partial, const float *fld,
+                 const Norm &norm, float *image, uint8_t *weight, void *label, int label_i32, int32_t *varied, hipStream_t st) {
+    const int tiles = cdnet::cdiv(size, T);
+    if (geo) aug_tile_kernel<true, NC><<<dim3(tiles * tiles, B), 256, 0, st>>>(samples, geo, size, FS, tiles, partial, fld, norm, image, weight, label, label_i32, varied);
+    else aug_tile_kernel<false, NC><<<dim3(tiles * tiles, B), 256, 0, st>>>(samples, geo, size, FS, tiles, partial, fld, norm, image, weight, label, label_i32, varied);
+}
+
+// the entry behind the ABI calls: geo == nullptr is the default recipe (field window: crop + HALO at the crop origin); NC = 3 (RGB) or 1 (L)
 int augment_batch(const char *who, const cdnet_aug_sample *samples, const cdnet_aug_sample *samples_host, const cdnet_aug_geo *geo,
                   const cdnet_aug_geo *geo_host, int FS, int B, int size, const float *norm_host, void *workspace, size_t workspace_bytes,
-                  float *image, uint8_t *weight, void *label, int label_i32, int32_t *varied, float *field, void *stream) {
+                  float *image, uint8_t *weight, void *label, int label_i32, int32_t *varied, float *field, void *stream, int NC) {
+    if (NC != 1 && NC != 3) {
+        cdnet::set_error("%s: channels is 1 (mode L) or 3 (RGB), got %d", who, NC);
+        return CDNET_E_ARG;
+    }
     CDNET_REQUIRE(samples && samples_host && image && weight && label && varied, "%s: null pointer", who);
     CDNET_REQUIRE((geo == nullptr) == (geo_host == nullptr), "%s: null pointer (geo table: device and host copy, or neither)", who);
     CDNET_REQUIRE(B >= 1 && B <= 4096 && size >= 1 && size <= 4096, "%s: B in 1..4096, size in 1..4096", who);
@@ -517,7 +551,7 @@ int augment_batch(const char *who, const cdnet_aug_sample *samples, const cdnet_
     for (int b = 0; b < B; ++b) {
         const cdnet_aug_sample &s = samples_host[b];
         CDNET_REQUIRE(s.img && s.weight && s.label, "%s: null pointer in sample %d", who, b);
-        CDNET_REQUIRE(s.H >= 1 && s.W >= 1 && s.img_stride >= 3 * s.W && s.weight_stride >= s.W && s.label_stride >= s.W,
+        CDNET_REQUIRE(s.H >= 1 && s.W >= 1 && s.img_stride >= NC * s.W && s.weight_stride >= s.W && s.label_stride >= s.W,
                       "%s: sample %d: bad size or row stride", who, b);
         CDNET_REQUIRE(s.label_i32 == label_i32, "%s: sample %d: label type differs from the batch's", who, b);
         CDNET_REQUIRE(s.filter >= 0 && s.filter <= 3, "%s: sample %d: filter code %d (0 none, 1 BLUR, 2 GaussianBlur, 3 MedianFilter)", who, b, s.filter);
@@ -581,21 +615,20 @@ int augment_batch(const char *who, const cdnet_aug_sample *samples, const cdnet_
     float *tmp = (float *)(ws + cdnet::align_up((size_t)B * NSTAT * 8, 256));
     float *fld = field ? field : (float *)((char *)tmp + cdnet::align_up((size_t)B * 2 * FS * (FS + 2 * rmax) * 4, 256));
     Norm norm = {norm_host != nullptr, {0, 0, 0}, {1, 1, 1}};
-    for (int c = 0; norm_host && c < 3; ++c) {
+    for (int c = 0; norm_host && c < NC; ++c) {
         norm.mean[c] = norm_host[c];
-        norm.std[c] = norm_host[3 + c];
+        norm.std[c] = norm_host[NC + c];
     }
     hipStream_t st = (hipStream_t)stream;
-    if (geo) aug_stats_kernel<true><<<dim3(NSTAT, B), 256, 0, st>>>(samples, geo, partial, varied);
-    else aug_stats_kernel<false><<<dim3(NSTAT, B), 256, 0, st>>>(samples, geo, partial, varied);
+    if (NC == 1) launch_stats<1>(samples, geo, B, partial, varied, st);
+    else launch_stats<3>(samples, geo, B, partial, varied, st);
     if (any_field) {
         const int vblocks = cdnet::cdiv(FS, VR) * cdnet::cdiv(FS + 2 * rmax, VC);
         aug_field_v_kernel<<<dim3(vblocks, 2, B), 256, (size_t)(VR + 2 * rmax) * VC * 4, st>>>(samples, geo, FS, rmax, tmp);
         aug_field_h_kernel<<<dim3(FS * cdnet::cdiv(FS, 256), 2, B), 256, 0, st>>>(samples, geo, FS, rmax, tmp, fld);
     }
-    const int tiles = cdnet::cdiv(size, T);
-    if (geo) aug_tile_kernel<true><<<dim3(tiles * tiles, B), 256, 0, st>>>(samples, geo, size, FS, tiles, partial, fld, norm, image, weight, label, label_i32, varied);
-    else aug_tile_kernel<false><<<dim3(tiles * tiles, B), 256, 0, st>>>(samples, geo, size, FS, tiles, partial, fld, norm, image, weight, label, label_i32, varied);
+    if (NC == 1) launch_tile<1>(samples, geo, B, size, FS, partial, fld, norm, image, weight, label, label_i32, varied, st);
+    else launch_tile<3>(samples, geo, B, size, FS, partial, fld, norm, image, weight, label, label_i32, varied, st);
     return cdnet::check_launch(who);
 }
 
@@ -612,11 +645,32 @@ extern "C" size_t cdnet_augment_workspace_bytes(int B, int size, int max_radius)
     return cdnet_augment_geo_workspace_bytes(B, size, max_radius, crop_field_edge(size));
 }
 
+extern "C" int cdnet_augment_batch_c(const cdnet_aug_sample *samples, const cdnet_aug_sample *samples_host, int B, int size, const float *norm_host,
+                                     void *workspace, size_t workspace_bytes, float *image, uint8_t *weight, void *label, int label_i32,
+                                     int32_t *varied, float *field, void *stream, int channels) {
+    return augment_batch("cdnet_augment_batch_c", samples, samples_host, nullptr, nullptr, crop_field_edge(size > 0 ? size : 1), B, size, norm_host,
+                         workspace, workspace_bytes, image, weight, label, label_i32, varied, field, stream, channels);
+}
+
+extern "C" int cdnet_augment_batch_geo_c(const cdnet_aug_sample *samples, const cdnet_aug_sample *samples_host, const cdnet_aug_geo *geo,
+                                         const cdnet_aug_geo *geo_host, int field_edge, int B, int size, const float *norm_host, void *workspace,
+                                         size_t workspace_bytes, float *image, uint8_t *weight, void *label, int label_i32, int32_t *varied,
+                                         float *field, void *stream, int channels) {
+    if (channels != 1 && channels != 3) {
+        cdnet::set_error("cdnet_augment_batch_geo_c: channels is 1 (mode L) or 3 (RGB), got %d", channels);
+        return CDNET_E_ARG;
+    }
+    CDNET_REQUIRE(geo && geo_host, "cdnet_augment_batch_geo_c: null pointer (geo table)");
+    return augment_batch("cdnet_augment_batch_geo_c", samples, samples_host, geo, geo_host, field_edge, B, size, norm_host, workspace,
+                         workspace_bytes, image, weight, label, label_i32, varied, field, stream, channels);
+}
+
+// the RGB entries: the channels = 3 call
 extern "C" int cdnet_augment_batch(const cdnet_aug_sample *samples, const cdnet_aug_sample *samples_host, int B, int size, const float *norm_host,
                                    void *workspace, size_t workspace_bytes, float *image, uint8_t *weight, void *label, int label_i32,
                                    int32_t *varied, float *field, void *stream) {
     return augment_batch("cdnet_augment_batch", samples, samples_host, nullptr, nullptr, crop_field_edge(size > 0 ? size : 1), B, size, norm_host,
-                         workspace, workspace_bytes, image, weight, label, label_i32, varied, field, stream);
+                         workspace, workspace_bytes, image, weight, label, label_i32, varied, field, stream, 3);
 }
 
 extern "C" int cdnet_augment_batch_geo(const cdnet_aug_sample *samples, const cdnet_aug_sample *samples_host, const cdnet_aug_geo *geo,
@@ -625,5 +679,5 @@ extern "C" int cdnet_augment_batch_geo(const cdnet_aug_sample *samples, const cd
                                        float *field, void *stream) {
     CDNET_REQUIRE(geo && geo_host, "cdnet_augment_batch_geo: null pointer (geo table)");
     return augment_batch("cdnet_augment_batch_geo", samples, samples_host, geo, geo_host, field_edge, B, size, norm_host, workspace,
-                         workspace_bytes, image, weight, label, label_i32, varied, field, stream);
+                         workspace_bytes, image, weight, label, label_i32, varied, field, stream, 3);
 }

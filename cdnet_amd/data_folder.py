@@ -12,7 +12,8 @@
                                       when the transform dict holds them, in one cdnet_augment_batch[_geo] call per batch,
                                       the sources resident there)
 
-Samples leave TileBatches in the layout train_util_dam.train expects: (input f32 [B,3,H,W], weight u8 [B,1,H,W],
+Samples leave TileBatches in the layout train_util_dam.train expects: (input f32 [B,3,H,W] - [B,1,H,W] for a one-channel dataset, whose
+images are u8 [H,W] -, weight u8 [B,1,H,W],
 label i64 [B,1,H,W] in {0,127,255}, point f16 [B,H,W], direction u8 [B,H,W]).  Without `augment` the photometric / elastic
 augmentations of the reference (my_transforms_direction.py:155-473) are skipped and logged; crop and flips are drawn with a numpy
 RandomState.  Neither path reproduces the reference's random streams (Python random, np.random, albumentations' RandomState over
@@ -29,8 +30,22 @@ def is_image_file(filename):
     return filename.lower().endswith(IMG_EXTENSIONS)
 
 
-def img_loader(path, num_channels):
-    """PIL image of a png / jpg, or of the 'inst_map' of a .mat / the array of a .npy (data_folder.py:20-41)"""
+def grey_image(img, path):
+    """the image of a grey-scale dataset (in_c = 1) as 8-bit mode L: L stays as it is, P / RGB / RGBA are converted (a grey-scale dataset
+    stored in colour); the modes that hold more than eight bits (I, I;16, F) raise a ValueError that names the file - sixteen-bit sources
+    are outside this pipeline.  Anything else comes back as it is."""
+    mode = getattr(img, 'mode', None)
+    if mode in ('P', 'RGB', 'RGBA'):
+        return img.convert('L')
+    if mode is not None and (mode == 'F' or mode.startswith('I')):
+        raise ValueError('{}: mode {} holds more than 8 bits per pixel; one-channel images are read as 8-bit L'.format(path, mode))
+    return img
+
+
+def img_loader(path, num_channels, grey=False):
+    """PIL image of a png / jpg, or of the 'inst_map' of a .mat / the array of a .npy (data_folder.py:20-41).  One channel: the file as it
+    is - what the weight maps of every dataset are read with; `grey` (the image of a grey-scale dataset, DataFolder's slot 0 with one
+    channel): through grey_image."""
     from PIL import Image
     if path.endswith('.mat'):
         import scipy.io as scio
@@ -39,7 +54,9 @@ def img_loader(path, num_channels):
     if path.endswith('.npy'):
         return Image.fromarray(np.load(path).astype(np.uint8))
     img = Image.open(path)
-    return img if num_channels == 1 else img.convert('RGB')
+    if num_channels != 1:
+        return img.convert('RGB')
+    return grey_image(img, path) if grey else img
 
 
 def get_imgs_list(dir_list, post_fix=None):
@@ -81,7 +98,10 @@ class DataFolder(torch.utils.data.Dataset):
         self.data_transform, self.num_channels, self.loader = data_transform, num_channels, loader
 
     def load(self, index):
-        return [self.loader(p, c) for p, c in zip(self.img_list[index], self.num_channels)]
+        out = [self.loader(p, c) for p, c in zip(self.img_list[index], self.num_channels)]
+        if self.num_channels[0] == 1:                # a grey-scale dataset: its image as 8-bit L (the weight map's slot is read as ever)
+            out[0] = grey_image(out[0], self.img_list[index][0])
+        return out
 
     def __getitem__(self, index):
         sample = self.load(index)
@@ -195,10 +215,12 @@ class TileBatches:
 
     def _host_batch(self, idx):
         crops = [self._draw(*self.items[i]) for i in idx]
-        img = torch.from_numpy(np.stack([c[0] for c in crops])).to(self.dev).permute(0, 3, 1, 2).float().div(255)
+        img = torch.from_numpy(np.stack([c[0] for c in crops])).to(self.dev)
+        img = (img.unsqueeze(1) if img.dim() == 3 else img.permute(0, 3, 1, 2)).float().div(255)        # [H, W] images: one channel
         if self.normalize:
-            mean, std = self.normalize
-            img = (img - torch.tensor(mean, device=self.dev).view(1, 3, 1, 1)) / torch.tensor(std, device=self.dev).view(1, 3, 1, 1)
+            nc = img.shape[1]
+            mean, std = (torch.tensor(v[:nc], device=self.dev).view(1, nc, 1, 1) for v in self.normalize)      # the first in_c entries
+            img = (img - mean) / std
         weight = torch.from_numpy(np.stack([c[1] if c[1].ndim == 2 else c[1][:, :, 0] for c in crops])).to(self.dev)
         lab0 = torch.from_numpy(np.stack([c[2] if c[2].ndim == 2 else c[2][:, :, 0] for c in crops])).to(self.dev)
         return img, weight, lab0

@@ -134,6 +134,10 @@ class _RU:
 
 
 class Unet(nn.Module):
+    # input channels: 3, or 1 after set_input_channels(1) (child0 as the first encoder layer).  Note that an EVAL forward without a bound
+    # trainer follows x.shape[1] as the reference does and so changes the model: input_channels, the per-instance UNUSED_PREFIXES and the
+    # runtime's first layer switch with it - a trainer built afterwards lays itself out for the stem of that last forward; call
+    # set_input_channels before building one.
     # head wiring: 'rev1' = the direction-aware-mask head of CDNet; the ablation models of models/dam/model_unet_MandD*.py reuse
     # this class with VARIANT 'MandD' (mask + direction, no gates, no point branch) / 'MandDandP' (plus the point branch); 'plain' is the
     # backbone U-Net of models/model_unet.py: no head modules at all, `final_conv` on the decoder's 16-channel feature
@@ -156,7 +160,8 @@ class Unet(nn.Module):
                                                       parametric=parametric_upsampling, use_bn=decoder_use_batchnorm))
         self.final_conv = nn.Conv2d(decoder_filters[-1], classes, kernel_size=(1, 1))          # never used (:213)
         self.replaced_conv1 = False
-        self.child0 = nn.Conv2d(1, 64, kernel_size=(3, 3), stride=(1, 1), padding=(1, 1))       # never used (:220)
+        self.child0 = nn.Conv2d(1, 64, kernel_size=(3, 3), stride=(1, 1), padding=(1, 1))       # the one-channel stem (:220; set_input_channels)
+        self.input_channels = 3
         self.child_conv1 = nn.Conv2d(1, 64, kernel_size=(7, 7), stride=(2, 2), padding=(3, 3), bias=False)
         if self.VARIANT != 'plain':
             self.mask_feature = ResidualUnit(decoder_filters[-1], 64)
@@ -186,6 +191,27 @@ class Unet(nn.Module):
         for p in self.backbone.parameters():
             p.requires_grad = False
 
+    def set_input_channels(self, c):
+        """the channel count of the input, 3 (RGB) or 1 (a grey-scale dataset, options' in_c = 1).  With 1 the first encoder convolution is
+        `child0` (Conv2d(1, 64, 3, padding=1)) in place of backbone child '0', as the reference's forward_backbone does for
+        x.shape[1] != 3 (model_unet_rev1.py `forward_backbone`, model_unet.py:206-207); backbone child '1', its BatchNorm, and everything
+        behind stay.  child0 runs on the zero-extended pack of the RGB stem (ConvLayer.prepare's Cin_pad, 1 -> 16): no kernel of its own.
+        The instance then carries its own UNUSED_PREFIXES: the class tuple without 'child0.', plus 'backbone.0.' (which gets no gradient
+        and no step in the reference; a pretrained file still fills it).  State-dict keys do not change.  A trainer lays out its flat
+        buffers from that tuple once: set the count first (the rule of freeze_encoder)."""
+        if c not in (1, 3):
+            raise ValueError('set_input_channels: 1 or 3 input channels, got {}'.format(c))
+        if getattr(self, '_trainer_bound', False):
+            raise RuntimeError('set_input_channels() after a trainer was built for this model: the trainer laid out its flat buffers and '
+                               'optimiser state for the other stem - set the channel count first, then build the trainer')
+        if c == self.input_channels:
+            return
+        self.input_channels = c
+        self.__dict__.pop('UNUSED_PREFIXES', None)
+        if c == 1:
+            self.UNUSED_PREFIXES = tuple(p for p in type(self).UNUSED_PREFIXES if p != 'child0.') + ('backbone.0.',)
+        self._rt = None                                  # the encoder's first layer changes
+
     def _pretrained_names(self):
         """the reference's rule (model_unet_rev1.py:307-320): every backbone parameter, but for a replaced ResNet stem ('conv1.weight')"""
         return {'backbone.' + n for n, _ in self.backbone.named_parameters() if not (self.replaced_conv1 and n == 'conv1.weight')}
@@ -209,6 +235,10 @@ class Unet(nn.Module):
         mods = list(self.backbone.children())
         while i < len(mods):
             if isinstance(mods[i], nn.Conv2d):
+                if i == 0 and self.input_channels == 1:      # the one-channel stem in place of child '0'; its BatchNorm is child '1' still
+                    enc.append(('conv', ConvLayer('child0', 'conv3', self.child0.weight, self.child0.bias, mods[1]), '2'))
+                    i += 3
+                    continue
                 enc.append(('conv', ConvLayer('backbone.%d' % i, 'conv3', mods[i].weight, mods[i].bias, mods[i + 1]), str(i + 2)))
                 i += 3
             else:
@@ -261,11 +291,15 @@ class Unet(nn.Module):
             self._build_runtime()
         if not x.is_cuda:
             raise RuntimeError('cdnet_amd.models.dam.model_unet_rev1.Unet runs on the MI355X only (no CPU fallback)')
-        assert x.shape[1] == 3, 'the CDNet path feeds 3-channel tiles (child0/child_conv1 branches are never taken)'
+        if x.shape[1] != self.input_channels:
+            # eval mode without a trainer follows the input as the reference does (x.shape[1] != 3 -> child0); a training step never switches
+            if training or getattr(self, '_trainer_bound', False) or x.shape[1] not in (1, 3):
+                raise ValueError('input with {} channels for a model set to {} (set_input_channels; 1 or 3)'.format(x.shape[1], self.input_channels))
+            self.set_input_channels(int(x.shape[1]))
         return self.forward_features_packed(runtime.input_pack(x.float()), training)
 
     def forward_features_packed(self, x16, training):
-        """x16: bf16 NHWC [N,H,W,16] (3 real channels) - the form cdnet_input_pack / cdnet_window_pack produce"""
+        """x16: bf16 NHWC [N,H,W,16] (input_channels real channels, the rest 0) - the form cdnet_input_pack / cdnet_window_pack produce"""
         if self._rt is None:
             self._build_runtime()
         t = Src(x16, is_input=True)

@@ -145,6 +145,7 @@ class Options:
                            help="the 'scale' test transform: resize the smaller image edge to N before the network (0 = off)")
         a = p.parse_args(argv)
         self.dataset = a.dataset
+        self.model['in_c'] = 1 if a.dataset == 'BBBC039V1' else 3        # options.py:41,319,431: the fluorescence set is grey-scale
         self.model['modelName'] = a.model_name
         self.all_img_test = a.all_img_test
         self.model['direction'], self.model['mseloss'] = a.direction, a.mseloss

@@ -83,7 +83,7 @@ def check_tiles(r):
 def infer_image(model, image, opt=None, tta=True, all_img_test=1, patch_size=256, overlap=40, classes=9, min_area=20,
                 radius=2, want_stages=False, defer=False, postproc=0, model_mode='Unet_rev1', restore=None):
     """The reference's per-image inference (test_dam.py:297-563) for one image tensor [3,H,W] float32 on the GPU
-    (already ToTensor'd / normalised): the eight dihedral views (TTA) through the network - whole image
+    (already ToTensor'd / normalised; [1,H,W] for a model set to one input channel, whose windows are packed with C = 1): the eight dihedral views (TTA) through the network - whole image
     (all_img_test == 1, options.py:35) or 256/40 sliding windows (utils.split_forward_dam) - softmax / gated direction
     argmax per view (get_probmaps), per-view direction-difference maps, their mean, the point-guided boundary boost, argmax,
     fill holes, remove small objects, label, dilate.  Returns dict(final int32 [H,W], count, pred, ...).
@@ -100,7 +100,13 @@ def infer_image(model, image, opt=None, tta=True, all_img_test=1, patch_size=256
     dilated (postproc.restore_chain): `final`, `counts` and `count` are at the original size, `pred` and `prob_mean` stay at the scaled
     size, where the reference saves them.  With postproc=1 a ValueError.  None: the path above, unchanged.
     With 'scale' in opt.transform['test'] and no `restore`, `image` is the transformed image at its ORIGINAL size - what test_dam.main and
-    test_dam.process_image hand over - and the transform's Scale step runs here, on the device (scale_transformed)."""
+    test_dam.process_image hand over - and the transform's Scale step runs here, on the device (scale_transformed).
+    With opt.model['in_c'] == 1 (a grey-scale dataset) a THREE-plane `image` is taken to be what test_dam.main and test_dam.process_image
+    hand over - the file read as RGB, / 255.0 and normalised per opt.transform['test'] - and is converted to Pillow's mode L here, on
+    the device (grey_transformed: its bytes are recovered by rounding, so a three-plane tensor that is not such an image is quantised to
+    bytes).  The entry module keeps its loader: cdnet_amd/test_dam.py falls under the repository's rule that a feature change leaves
+    existing test_*.py files as they are.  A caller who loads the file itself hands over [1,H,W] (pipeline.host_input(..., in_c=1), as
+    cdnet_amd.test does): one plane goes through untouched."""
     from . import postproc as postproc_mod, utils                         # (`postproc` is the reference's option name here)
     if opt is not None:
         tta, all_img_test = opt.test['tta'], opt.all_img_test
@@ -109,6 +115,7 @@ def infer_image(model, image, opt=None, tta=True, all_img_test=1, patch_size=256
         postproc, model_mode = int(opt.post['postproc']), opt.model['modelName']
     if (restore is not None or _has_scale(opt)) and int(postproc) == 1:
         raise ValueError(postproc_mod.SCALE_POSTPROC1)
+    image = grey_transformed(image, opt)                       # in_c = 1 and an image the entry read as RGB: Pillow's convert('L'), on the device
     if restore is None and _has_scale(opt):
         image, restore = scale_transformed(image, opt.transform['test'])
     assert not model.training and image.dim() == 3
@@ -190,7 +197,7 @@ def infer_tiles_mask(model, x, min_area=20, radius=2, post_stream=None, want_sta
 def infer_image_mask(model, image, opt=None, tta=True, all_img_test=1, patch_size=256, overlap=40, min_area=20, radius=2, postproc=0,
                      model_mode='UNet', want_prob=False, defer=False, restore=None):
     """The reference's per-image procedure of test.py:213-296 for one image tensor [3,H,W] float32 on the GPU (already ToTensor'd /
-    normalised) and a network with one mask output: the eight dihedral views (TTA) - whole image (all_img_test == 1) or sliding windows
+    normalised; [1,H,W] for a one-channel network) and a network with one mask output: the eight dihedral views (TTA) - whole image (all_img_test == 1) or sliding windows
     (utils.split_forward, :627) - stitched into ONE buffer, then ONE launch for every view's softmax, the mean and the class
     (postproc.mask_views_argmax), then
       postproc == 0: fill holes, remove small objects, 8-connected label, dilate (cc_chain on pred == 1, :277-295);
@@ -242,12 +249,14 @@ _NORM = {}
 
 def scaled_input(img_u8, transform, device=None):
     """The test transform of an image with the 'scale' key on the device (test_transform((img,)) of test_dam.py:297 / test.py:213: Scale ->
-    ToTensor -> Normalize).  img_u8: uint8 [H,W,3] tensor, on the host (uploaded as bytes through pinned memory) or already on the device.
+    ToTensor -> Normalize).  img_u8: uint8 [H,W,3] tensor - [H,W] for a grey-scale dataset (mode L: resize.hip's one-channel form, the first
+    entry of mean and std, x float32 [1,h,w]) -, on the host (uploaded as bytes through pinned memory) or already on the device.
     The image is resized there with Pillow's bilinear filter (resize.resize_bilinear, the size by resize.scaled_size), then converted and
     normalised with the fp32 operations of the host path (`/ 255.0`, `(x - mean) / std`).  Returns (x float32 [3,h,w] on the device,
     restore): restore = (H, W) for infer_image / infer_image_mask when the size changed, else None.  Nothing is read back."""
     from . import resize
-    assert img_u8.dtype == torch.uint8 and img_u8.dim() == 3 and img_u8.shape[2] == 3
+    assert img_u8.dtype == torch.uint8 and (img_u8.dim() == 2 or (img_u8.dim() == 3 and img_u8.shape[2] == 3))
+    nc = 1 if img_u8.dim() == 2 else 3
     H, W = int(img_u8.shape[0]), int(img_u8.shape[1])
     if not img_u8.is_cuda:
         dev = torch.device('cuda', torch.cuda.current_device()) if device is None else device
@@ -261,14 +270,54 @@ def scaled_input(img_u8, transform, device=None):
     #  for some bytes)
     if ('255', img_u8.device) not in _NORM:
         _NORM[('255', img_u8.device)] = torch.full((1,), 255.0, dtype=torch.float32, device=img_u8.device)
-    x = img_u8.permute(2, 0, 1).contiguous().float() / _NORM[('255', img_u8.device)]
+    x = (img_u8[None] if nc == 1 else img_u8.permute(2, 0, 1)).contiguous().float() / _NORM[('255', img_u8.device)]
+    if 'normalize' in transform:
+        x = (x - _norm_pair(transform, nc, x.device)[0]) / _norm_pair(transform, nc, x.device)[1]
+    return x, restore
+
+
+def _norm_pair(transform, nc, device):
+    """(mean, std) of the `normalize` transform as f32 [nc,1,1] device tensors: its first nc entries, uploaded once (a pageable copy would
+    wait for the images in flight)"""
+    mean, std = (list(v)[:nc] for v in transform['normalize'])
+    key = (tuple(float(v) for v in mean), tuple(float(v) for v in std), device)
+    if key not in _NORM:
+        _NORM[key] = tuple(torch.tensor(v, dtype=torch.float32).view(nc, 1, 1).to(device) for v in (mean, std))
+    return _NORM[key]
+
+
+def host_input(image, transform, in_c=3):
+    """ToTensor -> Normalize of the test transform on the host, as the entries always did it for RGB: a PIL image -> float32 [in_c,H,W]
+    (in_c = 1: converted to mode L, the first entry of mean and std)"""
+    nc, mode = (1, 'L') if in_c == 1 else (3, 'RGB')
+    img = np.asarray(image.convert(mode), dtype=np.float32) / 255.0
+    x = torch.from_numpy(img[:, :, None] if nc == 1 else img).permute(2, 0, 1).contiguous()
     if 'normalize' in transform:
         mean, std = transform['normalize']
-        key = (tuple(float(v) for v in mean), tuple(float(v) for v in std), x.device)
-        if key not in _NORM:                                   # (uploaded once: a pageable copy would wait for the images in flight)
-            _NORM[key] = tuple(torch.tensor(v, dtype=torch.float32).view(3, 1, 1).to(x.device) for v in (mean, std))
-        x = (x - _NORM[key][0]) / _NORM[key][1]
-    return x, restore
+        x = (x - torch.tensor(mean[:nc], dtype=torch.float32).view(nc, 1, 1)) / torch.tensor(std[:nc], dtype=torch.float32).view(nc, 1, 1)
+    return x
+
+
+def grey_transformed(image, opt):
+    """A grey-scale dataset (opt.model['in_c'] == 1) whose image was read as RGB and went through the test transform at its original
+    size - what test_dam.main and test_dam.process_image hand over: image float32 [3,H,W] on the device = bytes / 255.0 [- mean) / std].
+    Returns what loading the file with convert('L') gives, float32 [1,H,W]: the bytes are recovered (exact, as in scale_transformed),
+    Pillow's L = (R * 19595 + G * 38470 + B * 7471 + 0x8000) >> 16 is taken in integers (the identity for a grey image stored as RGB),
+    and the result is converted and normalised with the first entry of mean and std.  Anything else comes back as it is."""
+    if opt is None or opt.model.get('in_c', 3) != 1 or image.dim() != 3 or image.shape[0] != 3:
+        return image
+    transform = getattr(opt, 'transform', {}).get('test', {})
+    x = image.float()
+    if 'normalize' in transform:
+        x = x * _norm_pair(transform, 3, x.device)[1] + _norm_pair(transform, 3, x.device)[0]
+    b = torch.round(x * 255.0).clamp_(0, 255).to(torch.int32)
+    grey = ((b[0] * 19595 + b[1] * 38470 + b[2] * 7471 + 0x8000) >> 16).to(torch.uint8)
+    if ('255', x.device) not in _NORM:
+        _NORM[('255', x.device)] = torch.full((1,), 255.0, dtype=torch.float32, device=x.device)
+    x = grey[None].float() / _NORM[('255', x.device)]
+    if 'normalize' in transform:
+        x = (x - _norm_pair(transform, 1, x.device)[0]) / _norm_pair(transform, 1, x.device)[1]
+    return x
 
 
 def _has_scale(opt):
@@ -282,20 +331,17 @@ def scale_transformed(image, transform):
     then go through scaled_input, whose result has the bits of Scale -> ToTensor -> Normalize on the original bytes.  Returns (x, restore);
     the image itself and None when Scale leaves its size alone.  Nothing is read back."""
     from . import resize
-    assert image.is_cuda and image.dtype == torch.float32 and image.dim() == 3 and image.shape[0] == 3
+    assert image.is_cuda and image.dtype == torch.float32 and image.dim() == 3 and image.shape[0] in (1, 3)
+    nc = int(image.shape[0])
     H, W = int(image.shape[1]), int(image.shape[2])
     new = resize.scaled_size(W, H, transform['scale'])
     if new is None or (new[1], new[0]) == (H, W):
         return image, None
     x = image
     if 'normalize' in transform:
-        mean, std = transform['normalize']
-        key = (tuple(float(v) for v in mean), tuple(float(v) for v in std), x.device)
-        if key not in _NORM:
-            _NORM[key] = tuple(torch.tensor(v, dtype=torch.float32).view(3, 1, 1).to(x.device) for v in (mean, std))
-        x = x * _NORM[key][1] + _NORM[key][0]
-    img_u8 = torch.round(x * 255.0).clamp_(0, 255).to(torch.uint8).permute(1, 2, 0).contiguous()
-    return scaled_input(img_u8, transform)
+        x = x * _norm_pair(transform, nc, x.device)[1] + _norm_pair(transform, nc, x.device)[0]
+    img_u8 = torch.round(x * 255.0).clamp_(0, 255).to(torch.uint8)
+    return scaled_input(img_u8[0].contiguous() if nc == 1 else img_u8.permute(1, 2, 0).contiguous(), transform)
 
 
 def scale_inputs(image, opt, ori_size=None):
@@ -304,7 +350,8 @@ def scale_inputs(image, opt, ori_size=None):
     already transformed: with `ori_size=(ori_h, ori_w)` it was also scaled by the caller (the reference's Scale on the host) and the mask
     is resized back to ori_size; without it, it is at its original size and the Scale step runs here (scale_transformed)."""
     if not torch.is_tensor(image):
-        image = torch.from_numpy(np.array(image if isinstance(image, np.ndarray) else image.convert('RGB'), dtype=np.uint8))
+        mode = 'L' if opt.model.get('in_c', 3) == 1 else 'RGB'
+        image = torch.from_numpy(np.array(image if isinstance(image, np.ndarray) else image.convert(mode), dtype=np.uint8))
     if image.dtype == torch.uint8:
         return scaled_input(image, opt.transform['test'])
     x = image.cuda().float()

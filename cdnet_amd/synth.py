@@ -307,12 +307,12 @@ def nuclei_batch(B, H, W, seed, n=60, rmin=5, rmax=12):
     return x, lab, dirn, point, weight, insts
 
 
-def synthetic_batch(B, dev, seed=2022, H=256, W=256):
-    """SURVEY 8d recipe: uniform RGB tiles, ellipse instances -> 3-class label / centripetal classes / point map,
-    constant weight map 20."""
+def synthetic_batch(B, dev, seed=2022, H=256, W=256, channels=3):
+    """SURVEY 8d recipe: uniform RGB tiles (`channels` = 1: grey ones), ellipse instances -> 3-class label / centripetal classes / point
+    map, constant weight map 20."""
     import torch
     rs = np.random.RandomState(seed)
-    x = (rs.randint(0, 256, size=(B, 3, H, W)).astype(np.float32) / 255.0)
+    x = (rs.randint(0, 256, size=(B, channels, H, W)).astype(np.float32) / 255.0)
     lab = np.zeros((B, H, W), np.uint8)
     dirn = np.zeros((B, H, W), np.uint8)
     point = np.zeros((B, H, W), np.float16)

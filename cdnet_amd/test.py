@@ -144,20 +144,17 @@ def _run_shard(opt, trusted, mine):
     dev = torch.device('cuda', torch.cuda.current_device())
     copy_stream = torch.cuda.Stream(device=dev)
     rows = {}
+    in_c = opt.model.get('in_c', 3)                    # 1: a grey-scale dataset, read as mode L
 
     def launch(f):
         if 'scale' in opt.transform['test']:
             # the decoded bytes go up as they are; resize, conversion and normalisation run on the device (pipeline.scaled_input), and the
             # mask comes back at the original size (restore); the probability map stays at the scaled size, where the reference saves it
-            raw = torch.from_numpy(np.array(Image.open(os.path.join(img_dir, f)).convert('RGB'), dtype=np.uint8))
+            raw = torch.from_numpy(np.array(Image.open(os.path.join(img_dir, f)).convert('L' if in_c == 1 else 'RGB'), dtype=np.uint8))
             x, restore = pipeline.scaled_input(raw, opt.transform['test'], dev)
             r = pipeline.infer_image_mask(model, x, opt, want_prob=save_flag, defer=True, restore=restore)
         else:
-            img = np.asarray(Image.open(os.path.join(img_dir, f)).convert('RGB'), dtype=np.float32) / 255.0
-            x = torch.from_numpy(img).permute(2, 0, 1).contiguous()
-            if 'normalize' in opt.transform['test']:
-                mean, std = opt.transform['test']['normalize']
-                x = (x - torch.tensor(mean, dtype=torch.float32).view(3, 1, 1)) / torch.tensor(std, dtype=torch.float32).view(3, 1, 1)
+            x = pipeline.host_input(Image.open(os.path.join(img_dir, f)), opt.transform['test'], in_c)
             r = pipeline.infer_image_mask(model, x.pin_memory().to(dev, non_blocking=True), opt, want_prob=save_flag, defer=True)
         dev_out = {'final': r['final']}
         if save_flag:

@@ -28,10 +28,10 @@ from .options import Options
 class _SyntheticLoader:
     """`n` batches of the SURVEY 8d recipe in the sample layout of the reference's DataLoader"""
 
-    def __init__(self, n_batches, batch, dev, seed, size=256):
+    def __init__(self, n_batches, batch, dev, seed, size=256, channels=3):
         self.items = []
         for k in range(n_batches):
-            x, lab, dirn, point, weight = synth.synthetic_batch(batch, dev, seed=seed + k, H=size, W=size)
+            x, lab, dirn, point, weight = synth.synthetic_batch(batch, dev, seed=seed + k, H=size, W=size, channels=channels)
             target0 = (lab.to(torch.int64) * 127 + (lab == 2).to(torch.int64)).unsqueeze(1)      # {0,127,255} as ToTensor emits
             self.items.append((x, weight.unsqueeze(1), target0, point, dirn))
 
@@ -128,14 +128,15 @@ def main(argv=None):
         else:
             logger.info("=> no checkpoint found at '{}'".format(opt.train['checkpoint']))
     B = opt.train['batch_size']
+    in_c = opt.model['in_c']                               # 1 for a grey-scale dataset (--dataset BBBC039V1), else 3
     if own.synthetic > 0:
-        loader = _SyntheticLoader(own.synthetic, B, dev, seed=opt.train['seed'] + 1000 * rank)
+        loader = _SyntheticLoader(own.synthetic, B, dev, seed=opt.train['seed'] + 1000 * rank, channels=in_c)
     else:
         # train.py:262-290 without validation split: <img_dir>/train, <weight_map_dir>/train, <label_dir>/train
         from .data_folder import DataFolder, TileBatches
         dir_list, post_fix = _dataset_layout(opt, 'train', logger)
         _prepare_weight_maps(dir_list, post_fix, own.make_weight_maps, rank, world, dev, logger)
-        dset = DataFolder(dir_list, post_fix, [3, 1, 3])
+        dset = DataFolder(dir_list, post_fix, [in_c, 1, 3])
         elastic = dict(elastic_alpha=own.elastic_alpha, elastic_sigma=own.elastic_sigma, elastic_alpha_affine=own.elastic_alpha_affine)
         loader = TileBatches(dset, opt.transform['train'], B, dev, seed=opt.train['seed'] + 1000 * rank, logger=logger,
                              augment=own.device_augment, elastic=elastic)
@@ -144,14 +145,14 @@ def main(argv=None):
     val_loader = None
     if opt.train['validation'] == 1:
         if own.synthetic > 0:
-            val_loader = _SyntheticLoader(max(1, own.synthetic_val), B, dev, seed=opt.train['seed'] + 777 + 1000 * rank)
+            val_loader = _SyntheticLoader(max(1, own.synthetic_val), B, dev, seed=opt.train['seed'] + 777 + 1000 * rank, channels=in_c)
         else:
             from .data_folder import DataFolder, TileBatches
             vdirs, vfix = _dataset_layout(opt, 'val', logger)
             if os.path.isdir(vdirs[0]):
                 _prepare_weight_maps(vdirs, vfix, own.make_weight_maps, rank, world, dev, logger)
             if all(os.path.isdir(d) for d in vdirs):
-                vset = DataFolder(vdirs, vfix, [3, 1, 3])
+                vset = DataFolder(vdirs, vfix, [in_c, 1, 3])          # (the reference keeps [3, 1, 3] here: DESIGN.md section 8)
                 # options.py:358: the validation transform is {label_encoding, to_tensor, normalize} - no crop: every epoch scores the same
                 # whole images (validate() runs them whole or through split_forward_dam with input_size / val_overlap, train_util_dam.py:474)
                 vt = opt.transform.get('val') or {k: v for k, v in opt.transform['train'].items() if k in ('label_encoding', 'to_tensor', 'normalize')}

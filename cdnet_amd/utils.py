@@ -23,20 +23,27 @@ def chooseModel(opt):
     train = getattr(opt, 'isTrain', False)                 # (a bare options object, as the tools build: the test entries' behaviour)
     pretrained = (opt.model.get('pretrained_path') or bool(opt.model.get('pretrained', 0))) if train else False
     freeze = bool(opt.model.get('encoder_freeze', 0)) if train else False
+    in_c = opt.model.get('in_c', 3)                  # 1: a grey-scale dataset (--dataset BBBC039V1); the Unet family then runs child0
+
+    def stem(model):
+        model.set_input_channels(in_c)
+        return model
     if name == 'UNet':
         from .models.unet import UNet
         return UNet(num_classes=opt.model['out_c'], in_channels=opt.model['in_c'])
     if name == 'UNet2RevA1_vgg16':
         from .models.dam.model_unet_rev1 import Unet
-        return Unet(backbone_name='vgg16_bn', pretrained=pretrained, encoder_freeze=freeze, classes=opt.model['out_c'])
+        return stem(Unet(backbone_name='vgg16_bn', pretrained=pretrained, encoder_freeze=freeze, classes=opt.model['out_c']))
     if name == 'UNet_vgg16':                         # utils.py:822-824 (the ResNet backbones of :825-830 are not built)
         from .models.model_unet import Unet
-        return Unet(backbone_name='vgg16_bn', pretrained=pretrained, encoder_freeze=freeze, classes=opt.model['out_c'])
+        return stem(Unet(backbone_name='vgg16_bn', pretrained=pretrained, encoder_freeze=freeze, classes=opt.model['out_c']))
     if name in ('model_unet_MandD', 'model_unet_MandD4', 'model_unet_MandD16', 'model_unet_MandDandP'):      # utils.py:857-874
         import importlib
         mod = importlib.import_module('.models.dam.' + name, __package__)
-        return mod.Unet(backbone_name='vgg16_bn', pretrained=pretrained, encoder_freeze=freeze, classes=opt.model['out_c'])
+        return stem(mod.Unet(backbone_name='vgg16_bn', pretrained=pretrained, encoder_freeze=freeze, classes=opt.model['out_c']))
     if name == 'HRNet18_rev1':                       # utils.py:880-882
+        if in_c != 3:
+            raise ValueError('HRNet18_rev1 has a fixed three-channel stem (in the reference too): in_c = {} is not served'.format(in_c))
         from .models.dam.seg_hrnet_rev1 import HighResolutionNet
         return HighResolutionNet(opt)
     if name == 'FullNet':                            # utils.py:833-838 (whose `dilations` entry options.py leaves commented out: the class default)
@@ -58,7 +65,7 @@ def window_grid(h0, w0, size, overlap):
 
 
 def split_forward_views(model, image, size, overlap, xforms=(0,), direction_classes=9, max_batch=128, out=None):
-    """Sliding-window forward of one image [3,H,W] (cuda float32) for several TTA views at once.
+    """Sliding-window forward of one image [3,H,W] (cuda float32; [1,H,W] for a one-channel model) for several TTA views at once.
     Returns a list (one entry per view) of the stitched logits of every output `model.forward_packed` returns: (mask [3,hv,wv], point [1,hv,wv],
     direction [9,hv,wv]) for the DAM networks, (mask [K,hv,wv], direction) for the model_unet_MandD* heads, (mask [K,hv,wv],) for UNet.
     `out` = one buffer per output, e.g. (mask f32 [V,3,H*W], point f32 [V,1,H*W], direction f32 [V,K,H*W]): the views are stitched straight

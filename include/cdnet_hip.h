@@ -1000,6 +1000,23 @@ int cdnet_augment_batch_geo(const cdnet_aug_sample *samples, const cdnet_aug_sam
                             size_t workspace_bytes, float *image, uint8_t *weight, void *label, int label_i32, int32_t *varied, float *field,
                             void *stream);
 
+/* The same two calls for a plane count: channels = 3 (RGB) is what cdnet_augment_batch / cdnet_augment_batch_geo compute, byte for byte;
+ * channels = 1 is Pillow's mode L (grey-scale datasets); anything else is CDNET_E_ARG before any HIP call.
+ *   img u8 [H][W][channels] (img_stride in bytes, >= channels * W), image f32 [B][channels][size][size], norm_host NULL or
+ *   f32 [2 * channels] = mean[channels], std[channels].  The structs, the workspace entries, the geometry, the flips, the label / weight planes,
+ *   the re-draw flag and the field are those of the RGB calls.
+ * Mode L as Pillow computes it: ImageEnhance.Color is the identity for every factor (its degenerate image is the image itself; color[0]
+ *   is ignored), Brightness blends with 0, Contrast's degenerate value is int(mean + 0.5) of the brightness-adjusted plane itself (no
+ *   RGB -> L weights; u64 sum, divided in double), Sharpness blends with SMOOTH of the one plane (same summation order, 0.5 start, copied
+ *   edge rows and columns), BLUR / GaussianBlur(2) / MedianFilter(3) work on the one plane. */
+int cdnet_augment_batch_c(const cdnet_aug_sample *samples, const cdnet_aug_sample *samples_host, int B, int size, const float *norm_host,
+                          void *workspace, size_t workspace_bytes, float *image, uint8_t *weight, void *label, int label_i32, int32_t *varied,
+                          float *field, void *stream, int channels);
+int cdnet_augment_batch_geo_c(const cdnet_aug_sample *samples, const cdnet_aug_sample *samples_host, const cdnet_aug_geo *geo,
+                              const cdnet_aug_geo *geo_host, int field_edge, int B, int size, const float *norm_host, void *workspace,
+                              size_t workspace_bytes, float *image, uint8_t *weight, void *label, int label_i32, int32_t *varied, float *field,
+                              void *stream, int channels);
+
 /* ------------------------------------------------------------------------------------------------------
  * Training-target generation.  Replaces my_transforms_direction.py:687-885 `LabelEncoding.__call__` (3-class-PNG input,
  * do_direction = 1) with get_centerpoint2 (:650-685), Sobel.kernel (SegFix_offset_helper.py:97-132) and

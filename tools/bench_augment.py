@@ -1,12 +1,12 @@
 """Rate of the device training augmentation (cdnet_amd/augment.py, csrc/augment.hip) against its host implementation.
 
-    python tools/bench_augment.py [--batch 16] [--src 1000] [--size 256] [--iters 50] [--host-samples 2] [--recipe full]
+    python tools/bench_augment.py [--batch 16] [--src 1000] [--size 256] [--iters 50] [--host-samples 2] [--recipe full] [--channels 1]
 
 Prints one JSON line: ms per batch of B sources of src x src into size x size tiles for augmentation alone (default recipe: alpha 1,
 sigma 50), augmentation + label encoding, and the host implementation (PIL + numpy + scipy, one core) per batch (extrapolated from
 --host-samples samples), with the box record (device name, clocks as torch reports them).  With --recipe full the nine-step recipe
 (random_resize [1, 2], random_affine 0.3 and random_rotation added) is timed beside the default one in the same process, and the line
-carries both times and their ratio."""
+carries both times and their ratio.  --channels 1 times the mode-L path (grey-scale sources, the channels = 1 entries) the same way."""
 import argparse
 import json
 import os
@@ -66,6 +66,7 @@ def main():
     ap.add_argument('--host-samples', type=int, default=2)
     ap.add_argument('--recipe', choices=('default', 'full'), default='default',
                     help='full: also time all nine steps (resize, affine and rotation added) beside the default recipe')
+    ap.add_argument('--channels', type=int, choices=(1, 3), default=3, help='1: mode-L sources (a grey-scale dataset), the channels = 1 entries')
     ap.add_argument('--epoch-rate', action='store_true',
                     help='also: tiles/s of `python -m cdnet_amd.train` epochs over a folder of --batch x 2 sources, with and without --device-augment')
     a = ap.parse_args()
@@ -77,7 +78,8 @@ def main():
     for k in range(a.batch):
         inst = synth.ellipse_instances(a.src, a.src, 300, rs, 6, 14, 8)
         lab = np.where(inst > 0, 255, 0).astype(np.uint8)
-        items.append((rs.randint(0, 256, (a.src, a.src, 3)).astype(np.uint8), np.full((a.src, a.src), 20, np.uint8), lab))
+        img = rs.randint(0, 256, (a.src, a.src, 3)).astype(np.uint8)
+        items.append((img if a.channels == 3 else np.ascontiguousarray(img[..., 0]), np.full((a.src, a.src), 20, np.uint8), lab))
     srcs = [augment.Source(*it, dev) for it in items]
     rec = augment.Recipe(size=a.size)
     params = [[augment.draw_params(rs, a.src, a.src, rec) for _ in srcs] for _ in range(a.iters)]
@@ -110,9 +112,11 @@ def main():
     for k in range(a.host_samples):
         augment.augment_host(*items[k], params[0][k], a.size)
     host_ms = (time.perf_counter() - t0) / a.host_samples * a.batch * 1e3
+    if a.epoch_rate and a.channels != 3:
+        raise SystemExit('--epoch-rate renders an RGB folder for the default dataset: run it with --channels 3')
     epochs = epoch_rates(a, items) if a.epoch_rate else None
     p = torch.cuda.get_device_properties(0)
-    print(json.dumps({'tool': 'bench_augment', 'batch': a.batch, 'src': a.src, 'size': a.size, 'iters': a.iters,
+    print(json.dumps({'tool': 'bench_augment', 'batch': a.batch, 'src': a.src, 'size': a.size, 'iters': a.iters, 'channels': a.channels,
                       'augment_ms_per_batch': round(aug_ms, 4), 'augment_label_encoding_ms_per_batch': round(aug_le_ms, 4),
                       'tiles_per_s': round(a.batch / aug_le_ms * 1e3, 1), 'host_ms_per_batch': round(host_ms, 1),
                       'host_over_device': round(host_ms / aug_le_ms, 1), 'epoch_tiles_per_s': epochs, 'full_recipe': full,
